@@ -16,17 +16,31 @@ configs[4], ONE synthetic 20M-triangle mesh (3162 x 3162 cells, 10.0M DoF)
 split in row blocks over the N ranks (xfk_problem_create_dist): each rank
 assembles its rows, the PCG exchanges halo slices (RCCL send/recv) before
 every SpMV and all-reduces its inner-product partials once per iteration
-(RCCL all-reduce over xGMI).  "scaling": "strong" (the mesh is fixed).  After
-the timed region rank 0 solves the same mesh alone on its GPU, so the line
-carries the measured same-mesh speedup.  --mode replicas instead solves one
+(RCCL all-reduce over xGMI).  "scaling": "strong" (the mesh is fixed).  With
+--full, after the timed region rank 0 solves the same mesh alone on its GPU,
+so the line carries the measured same-mesh speedup.  --mode replicas instead solves one
 independent 2M-tri problem per GPU (parameter sweep; no collective, "weak").
 The host barrier / max-over-ranks and the RCCL unique-id broadcast use
 torch.distributed (gloo) on scalars only.
 
+A plain run (bench.py --gpus 1 --steps N --warmup W) does only what the
+headline figure needs: set-up, W warm-up steps, the N timed steps, the output
+dump if asked for, and the result line.  Everything else below that takes a
+run of its own is measured with --full only.
+
+--dump-outputs DIR writes what the last timed step computed -- A at every
+node, as a caller of Static2DProblem.solution() receives it -- to DIR/A.npy
+(float64; at N > 1 with --mode replicas one A_rank<r>.npy per rank) right after
+the timed region.  The inputs are a pure function of the arguments, so two
+builds can be compared output for output.  An output above the 64 MB budget
+is stored as a fixed sample (seeded index set, ascending).
+
 Output: one JSON line (rank 0) with
   roofline       the PCG SpMV (k_cg_spmv): HIP-event timing inside the timed
                  region, algorithmic bytes per launch, PMC traffic from the
-                 committed rocprof summary; roofline.phases = every AMG setup
+                 committed rocprof summary;
+and with --full also
+  roofline.phases  every AMG setup
                  step and every launch of one PCG iteration (xfk_phase_profile,
                  after the timed region), annotated with the rocprof duration,
                  the PMC traffic and the bound (cache / hbm / latency) of the
@@ -44,7 +58,9 @@ Output: one JSON line (rank 0) with
   fsolver_cold_process  bin/fsolver as a fresh child process per analysis
                  (the reference's command-line use), start to exit;
   sharded_diagnosis  (sharded runs) time inside each kind of collective on
-                 every rank, the per-rank phases and their maximum over ranks.
+                 every rank, the per-rank phases and their maximum over ranks;
+  config.same_mesh_1gpu  (sharded runs, N > 1) rank 0's single-GPU solve of
+                 the sharded mesh and the speedup over it.
 """
 import argparse
 import ctypes
@@ -89,6 +105,24 @@ class stdout_to_stderr:
     def __exit__(self, *exc):
         os.dup2(self.saved, 1)
         os.close(self.saved)
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # all files of one --dump-outputs run together stay below 64 MB
+
+
+def dump_output(directory, name, a, n_files=1):
+    """--dump-outputs: one array of the last timed step as directory/name.npy
+    (float64).  n_files arrays share the budget; one above its share is stored
+    as a fixed sample: the entries at a seeded, ascending index set that
+    depends on the array's size only."""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    cap = DUMP_BUDGET_BYTES // (8 * n_files)
+    if a.size > cap:
+        idx = np.sort(np.random.default_rng(20240229).choice(a.size, cap, replace=False))
+        a = a[idx]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def host_cpu():
@@ -710,6 +744,13 @@ def main():
                          "processes itself (default: WORLD_SIZE, else 1)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything that takes runs of its own: the per-phase "
+                         "table, cold first solve, FSolver end to end and as a child process, the configs[3] / "
+                         "configs[4] secondaries, the CPU baseline, the sharded diagnosis and same-mesh 1-GPU "
+                         "solve (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the solution of the last timed step to DIR/A.npy (float64)")
     ap.add_argument("--cells", type=int, default=1000, help="cells per side (2*cells^2 triangles)")
     ap.add_argument("--nonlinear", action="store_true", help="M-19 B-H steel (configs[3])")
     ap.add_argument("--cpu-cells", type=int, default=1000,
@@ -743,6 +784,9 @@ def main():
     ap.add_argument("--no-same-mesh-1gpu", action="store_true",
                     help="skip rank 0's single-GPU solve of the sharded mesh")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
 
     if args.force_sharded and args.local_ranks > 1:
         print(json.dumps(local_ranks_run(args)), flush=True)
@@ -762,7 +806,7 @@ def main():
               file=sys.stderr, flush=True)
     local = int(os.environ.get("LOCAL_RANK", "0"))
     cold_process = None
-    if world == 1 and not args.no_fsolver and not args.force_sharded:
+    if full and world == 1 and not args.no_fsolver and not args.force_sharded:
         cold_process = fsolver_cold_process(args)   # (before this process touches the GPU)
     dist = None
     if world > 1:
@@ -814,6 +858,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        A = P.solution()                        # (collective on a sharded problem: every rank calls it)
+        if sharded or world == 1:
+            if rank == 0:
+                dump_output(args.dump_outputs, "A", A)
+        else:
+            dump_output(args.dump_outputs, "A_rank%d" % rank, A, n_files=world)
+        del A
+
     # roofline of the dominant kernel (the CSR SpMV of the PCG), measured live
     spmv_ms = sum(r["spmv_ms_avg"] * r["spmv_samples"] for r in results) / max(
         1, sum(r["spmv_samples"] for r in results))
@@ -832,7 +885,7 @@ def main():
     # launch of one PCG iteration, HIP events on the solve stream
     phases = None
     phases_src = None
-    if amg and not sharded and world == 1 and not args.no_phases:
+    if full and amg and not sharded and world == 1 and not args.no_phases:
         iters = max(1, pcg_iters)
         phases = []
         for ph in P.phase_profile(iters=iters, setup=True):
@@ -846,10 +899,10 @@ def main():
             phases.append(row)
         phases_src = annotate_phases(phases)
 
-    diagnosis = sharded_diagnosis(P, comm, dist, rank, world) if sharded else None
+    diagnosis = sharded_diagnosis(P, comm, dist, rank, world) if full and sharded else None
 
     same_mesh = None
-    if sharded and world > 1 and not args.no_same_mesh_1gpu:
+    if full and sharded and world > 1 and not args.no_same_mesh_1gpu:
         # strong-scaling reference: rank 0 alone on the same mesh (after the timed region)
         P.close()
         if rank == 0:
@@ -935,18 +988,18 @@ def main():
         out["config"]["same_mesh_1gpu"] = same_mesh
     if diagnosis is not None:
         out["sharded_diagnosis"] = diagnosis
-    if rank == 0 and world == 1 and not sharded:
+    if full and rank == 0 and world == 1 and not sharded:
         out["cold_first_solve"] = cold_first_solve(local, args, kw)
         if not args.no_fsolver:
             out["fsolver_end_to_end"] = fsolver_end_to_end(local, args)
             out["fsolver_cold_process"] = cold_process
-    if rank == 0 and world == 1 and not sharded and not args.nonlinear and not args.no_secondary:
+    if full and rank == 0 and world == 1 and not sharded and not args.nonlinear and not args.no_secondary:
         P.close()
         out["secondary"] = [nonlinear_secondary(local, args)]
         if not args.no_configs4:
             out["secondary"].append(configs4_secondary(local, args))
             out["secondary"].append(configs4_rank0_of_8(local, args))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_cells, args.nonlinear)
     if rank == 0:
         print(json.dumps(out), flush=True)
