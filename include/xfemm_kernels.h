@@ -430,6 +430,105 @@ int xfk_get_circuits_complex(xfk_problem *prob, int *ccase, double *J, double *d
 /* Assembled complex system after all boundary conditions (val, b interleaved). */
 int xfk_get_csr_complex(xfk_problem *prob, int *rowptr, int *col, double *val, double *b);
 
+/* ---------------------------------------------------------------------------
+ * Electrostatic problems: ESolver::AnalyzeProblem
+ * (cfemm/esolver/esolver.cpp:389-646) over the same assembly, boundary maps
+ * and AMG-PCG as the static magnetics path, and ESolver::ChargeOnConductor
+ * (esolver.cpp:797-844).  Single device.
+ *
+ * The descriptors carry the state ESolver::LoadProblemFile and LoadMesh leave
+ * behind: coordinates in mm, 0-based indices, -1 for "none".
+ *
+ * Prescribed-voltage conductors (CircType 1) fix their nodes; a floating
+ * conductor (CircType 0, a prescribed total charge) is one unknown: its nodes
+ * are merged onto the conductor's lowest-numbered node, whose row carries
+ * 1e9 c q (c = 1e-6 / eo) on its right-hand side, and take that node's value
+ * after the solve (bit-equal).  xfk_get_csr shows the merged system: the
+ * other nodes of a floating conductor are identity rows.  The reference's
+ * bordered form replaces the conductor's diagonal by minus its off-diagonal
+ * row sum (esolver.cpp:625-628), which drops the stiffness towards directly
+ * adjacent fixed nodes and any mixed-boundary terms from it, and assigns
+ * 1e9 c q to its right-hand side over what the elements left there; the
+ * merged row keeps both.  The two agree when free nodes in charge-free
+ * material surround the conductor.
+ * ------------------------------------------------------------------------- */
+/* CMaterialProp of esolver (CMaterialProp.h): relative permittivities, C/m^3. */
+typedef struct {
+    double ex, ey;
+    double qv;
+} xfk_es_block_desc;
+
+/* CSBlockLabel. */
+typedef struct {
+    int block;                  /* index into blocks */
+    int is_external;            /* axisymmetric: conformally mapped exterior region */
+} xfk_es_label_desc;
+
+/* CSBoundaryProp. */
+typedef struct {
+    int format;                 /* BdryFormat: 0 fixed V, 1 mixed, 2 surface charge, 3 periodic, 4 antiperiodic */
+    double V;
+    double qs;                  /* C/m^2 */
+    double c0, c1;
+} xfk_es_line_desc;
+
+/* CSPointProp: qp == 0 fixes V at the node, else a point charge qp (C/m; C when axisymmetric). */
+typedef struct {
+    double V, qp;
+} xfk_es_point_desc;
+
+/* CSCircuit. */
+typedef struct {
+    int type;                   /* CircType: 1 prescribed voltage V, 0 prescribed total charge q */
+    double V, q;
+} xfk_es_conductor_desc;
+
+typedef struct {
+    int n_nodes;
+    const double *x, *y;        /* node coordinates, mm (ESolver::LoadMesh) */
+    const int *marker;          /* point-prop index or -1 (may be NULL) */
+    const int *conductor;       /* conductor index or -1 (may be NULL) */
+    int n_elems;
+    const int *p;               /* 3 per element */
+    const int *e;               /* 3 per element: boundary-prop index or -1 (may be NULL) */
+    const int *lbl;             /* block label of each element */
+    int n_blocks;      const xfk_es_block_desc *blocks;
+    int n_labels;      const xfk_es_label_desc *labels;
+    int n_lines;       const xfk_es_line_desc *lines;
+    int n_points;      const xfk_es_point_desc *points;
+    int n_conductors;  const xfk_es_conductor_desc *conductors;
+    int n_pbc;         const int *pbc;   /* 3 per pair: node, node, type (0 periodic, 1 anti) */
+    double precision;           /* [Precision] */
+    int length_units;           /* femm::LengthUnit */
+    int problem_type;           /* XFK_PLANAR or XFK_AXISYMMETRIC (x is r, y is z) */
+    double depth;               /* [Depth], user units (planar) */
+    double ext_zo, ext_ro, ext_ri;   /* [extZo] [extRo] [extRi], user units */
+} xfk_es_problem_desc;
+
+/* Upload an electrostatic problem.  The descriptor is checked before the
+ * device is touched (XFK_ERR_ARG with a message naming the cause): indices
+ * out of range, a non-positive depth on a planar problem, a point property on
+ * a node of a floating conductor, a node both in a floating conductor and
+ * fixed by a line or point property.  xfk_get_csr, xfk_set_option,
+ * xfk_problem_memory and xfk_problem_destroy work on the problem;
+ * xfk_static2d and xfk_harmonic2d refuse it (XFK_ERR_ARG). */
+int xfk_problem_create_electrostatic(const xfk_es_problem_desc *desc, int device, xfk_problem **out);
+/* ESolver::AnalyzeProblem on the device; flags and result as xfk_static2d
+ * (one linear solve).  The charges of the prescribed-voltage conductors are
+ * integrated after the solve, as the reference does.  xfk_get_solution then
+ * returns V at every node, unscaled.  XFK_ERR_ARG on a magnetics problem. */
+int xfk_electrostatic(xfk_problem *prob, int flags, xfk_result *res);
+/* Per conductor after xfk_electrostatic: V the prescribed (CircType 1) or
+ * solved (CircType 0) potential -- the .res conductor line's first column,
+ * L.V[NumNodes + i] -- and q the integrated (CircType 1) or prescribed
+ * (CircType 0) charge, C.  Either array may be NULL. */
+int xfk_get_conductors(xfk_problem *prob, double *V, double *q);
+/* ChargeOnConductor(conductor) of the last solution, any conductor type:
+ * the sum over the elements touching a node of the conductor, in element
+ * order within fixed workgroup chunks and over the chunks in order, so two
+ * runs give the same bits. */
+int xfk_conductor_charge(xfk_problem *prob, int conductor, double *q);
+
 /* Device views for the bench / tests (stream-ordered on the problem's stream). */
 int xfk_get_csr(xfk_problem *prob, int *rowptr, int *col, double *val, double *b);
 long long xfk_get_nnz(xfk_problem *prob);

@@ -1169,7 +1169,8 @@ static int assemble(xfk_problem *P, int iter)
     A.dv_el = pre ? P->dv_el.p : nullptr;
     A.on_el = pre ? P->on_el.p : nullptr;
     A.n_el = P->NE;
-    launch_assemble_rows(s, P->NR, A);   // writes every entry of val and b (assembled rows)
+    if (P->electro) launch_electro_rows(s, P);   // (xfk_electro.hip: a row gather of its own)
+    else launch_assemble_rows(s, P->NR, A);   // writes every entry of val and b (assembled rows)
     std::swap(P->mu1.p, P->mu1b.p);     // the state just written is read next iteration
     std::swap(P->mu1.n, P->mu1b.n);
     std::swap(P->mu2.p, P->mu2b.p);
@@ -1831,7 +1832,7 @@ int xfk_device_init(int device)
     XFK_CHECK(hipSetDevice(device));
     XFK_CHECK(hipFree(nullptr));
     for (hipError_t (*w)() : {warm_module_device, warm_module_pcg, warm_module_amg, warm_module_harmonic,
-                              warm_module_sort, warm_module_comm})
+                              warm_module_sort, warm_module_comm, warm_module_electro})
         XFK_CHECK(w());
     hipStream_t s[3] = {};   // a problem's solve stream, the AMG's side stream and the sort's
     for (hipStream_t &q : s) XFK_CHECK(stream_acquire(&q));
@@ -2451,7 +2452,7 @@ int build_local(const xfk_problem_desc *d, const GlobalPrep &G, const PartPlan *
 // than half of the device's free memory, and a failed one is dropped (the
 // HIP error cleared) -- creation never fails on it, so the ranks of a sharded
 // problem cannot disagree about it.
-static int reserve_first_solve(xfk_problem **out)
+int reserve_first_solve(xfk_problem **out)
 {
     xfk_problem *P = *out;
     static const long long per_row = [] {
@@ -2619,13 +2620,13 @@ void problem_recycle(xfk_problem *P)
     if (P->amg) P->amg->sync_streams();
     P->arena.recycle();
 }
-static int static2d_run(xfk_problem *P, int flags, xfk_result *res);
 }  // namespace xfk
 
 extern "C" {
 
 int xfk_static2d(xfk_problem *P, int flags, xfk_result *res)
 {
+    XFK_REQUIRE(!(P && P->electro), XFK_ERR_ARG, "electrostatic problem: use xfk_electrostatic");
     ArenaScope arena_scope(P ? &P->arena : nullptr);
     const int rc = static2d_run(P, flags, res);
     problem_recycle(P);
@@ -2635,7 +2636,7 @@ int xfk_static2d(xfk_problem *P, int flags, xfk_result *res)
 }  // extern "C"
 
 namespace xfk {
-static int static2d_run(xfk_problem *P, int flags, xfk_result *res)
+int static2d_run(xfk_problem *P, int flags, xfk_result *res)
 {
     ArenaScope arena_scope(P ? &P->arena : nullptr);
     XFK_REQUIRE(P, XFK_ERR_ARG, "null problem");
@@ -2831,6 +2832,7 @@ int xfk_get_solution(xfk_problem *P, double *A)
     hipStream_t s = P->stream;
     if (!P->comm) {
         XFK_CHECK(d2h(A, P->V.p, sizeof(double) * P->N, s));
+        if (P->electro) return XFK_OK;   // V itself (esolver.cpp:760)
         for (int i = 0; i < P->N; ++i) A[i] = A[i] * kC;   // L.b[i] = L.V[i]*c (static2d.cpp:1018-1021)
         if (P->axi)   // flux 2 pi r A, Webers (staticaxi.cpp:774-779)
             for (int i = 0; i < P->N; ++i) A[i] *= (P->axi_x[i] * 0.01 * 2 * kPI);

@@ -105,6 +105,18 @@ struct DevCirc {
     int type, ccase;
 };
 
+// Electrostatic tables (xfk_electro.hip), as ESolver::AnalyzeProblem reads them.
+struct EsBlock {
+    double ex, ey, qv;
+};
+struct EsLabel {
+    int blk, external;
+};
+struct EsLine {
+    double c0, c1, qs;
+    int format, pad;
+};
+
 // Scalars of one PCG solve, device resident (written by the last-arriving
 // block of each reduction kernel, read by the next launch).
 struct PcgScalars {
@@ -290,6 +302,7 @@ hipError_t stream_acquire(hipStream_t *s);
 hipError_t warm_module_amg();
 hipError_t warm_module_comm();
 hipError_t warm_module_device();
+hipError_t warm_module_electro();
 hipError_t warm_module_harmonic();
 hipError_t warm_module_pcg();
 hipError_t warm_module_sort();
@@ -537,6 +550,28 @@ struct xfk_problem {
     xfk::DBuf<xfk::CcgState> hc_state;
     xfk::CcgState *hc_host = nullptr;            // pinned mirror
 
+    // electrostatic problem (xfk_problem_create_electrostatic, xfk_electro.hip):
+    // p_raw holds the MERGED connectivity (every node of a floating conductor
+    // replaced by the conductor's representative node), which the symbolic
+    // phase and the row gather index rows and columns by; es_p the mesh's own
+    // connectivity, which gives the element geometry and the charge integral
+    bool electro = false;
+    double es_depth = 0;                         // Depth in mm (planar)
+    xfk::DBuf<int> es_p;                         // 3 * NE, mesh connectivity
+    xfk::DBuf<xfk::EsBlock> es_blocks;
+    xfk::DBuf<xfk::EsLabel> es_labels;
+    xfk::DBuf<xfk::EsLine> es_lines;
+    xfk::DBuf<unsigned char> es_slave;           // N: 1 for a merged-away node (identity row)
+    xfk::DBuf<int> es_slave_node, es_slave_rep;  // merged-away nodes and their representatives
+    int es_nslave = 0;
+    std::vector<xfk_es_conductor_desc> es_cond;  // host: the conductor table (q of CircType 1 filled by the solve)
+    std::vector<int> es_cond_rep;                // host: representative node of a floating conductor, else -1
+    std::vector<int> es_cel_ptr;                 // host: conductor -> [ptr, ptr + 1) into es_cel
+    xfk::DBuf<int> es_cel;                       // elements touching a node of each conductor, ascending
+    xfk::DBuf<int> es_node_cond;                 // N: conductor of each node or -1
+    xfk::DBuf<double> es_qpart;                  // per-workgroup partials of the charge integral, then the sum
+    bool es_solved = false;
+
     // live SpMV launch timing (XFK_TIME_SPMV)
     bool time_spmv = false;
     std::vector<hipEvent_t> spmv_ev;   // pairs
@@ -632,6 +667,14 @@ int prepare_magdir(const xfk_problem_desc *d, GlobalPrep &G);
 int build_local(const xfk_problem_desc *d, const GlobalPrep &G, const PartPlan *plan, int device, xfk_comm *comm,
                 xfk_problem **out);
 int build_symbolic(xfk_problem *P);
+// FSolver::Static2D's driver (symbolic phase, assembly, boundary conditions,
+// PCG); xfk_electrostatic runs it for its one linear pass
+int static2d_run(xfk_problem *P, int flags, xfk_result *res);
+void problem_recycle(xfk_problem *P);
+// the first solve's device footprint, reserved in the problem's arena
+int reserve_first_solve(xfk_problem **out);
+// xfk_electro.hip: the electrostatic row gather (writes every entry of val and b)
+void launch_electro_rows(hipStream_t s, xfk_problem *P);
 // sum of a host scalar over the ranks of P's communicator (no-op on one device)
 int allreduce_host(xfk_problem *P, double &v);
 int allreduce_host_n(xfk_problem *P, double *v, int n);   // n doubles summed over the ranks (host in, host out)

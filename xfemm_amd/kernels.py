@@ -55,6 +55,7 @@ EXPORTED = (
     "xfk_comm_time", "xfk_comm_timing",
     "xfk_partition_plan", "xfk_partition_plan_coupled", "xfk_problem_create_dist", "xfk_dist_get_info",
     "xfk_magdir_eval", "xfk_magdir_eval_labels", "xfk_lua_run", "xfk_sort_elements",
+    "xfk_problem_create_electrostatic", "xfk_electrostatic", "xfk_get_conductors", "xfk_conductor_charge",
 )
 
 
@@ -108,6 +109,40 @@ class ProblemDesc(C.Structure):
 
 XFK_PLANAR = 0
 XFK_AXISYMMETRIC = 1
+
+
+class EsBlockDesc(C.Structure):
+    _fields_ = [("ex", C.c_double), ("ey", C.c_double), ("qv", C.c_double)]
+
+
+class EsLabelDesc(C.Structure):
+    _fields_ = [("block", C.c_int), ("is_external", C.c_int)]
+
+
+class EsLineDesc(C.Structure):
+    _fields_ = [("format", C.c_int), ("V", C.c_double), ("qs", C.c_double), ("c0", C.c_double), ("c1", C.c_double)]
+
+
+class EsPointDesc(C.Structure):
+    _fields_ = [("V", C.c_double), ("qp", C.c_double)]
+
+
+class EsConductorDesc(C.Structure):
+    _fields_ = [("type", C.c_int), ("V", C.c_double), ("q", C.c_double)]
+
+
+class EsProblemDesc(C.Structure):
+    """xfk_es_problem_desc: the state ESolver::LoadProblemFile / LoadMesh leave behind."""
+    _fields_ = [("n_nodes", C.c_int), ("x", dptr), ("y", dptr), ("marker", iptr), ("conductor", iptr),
+                ("n_elems", C.c_int), ("p", iptr), ("e", iptr), ("lbl", iptr),
+                ("n_blocks", C.c_int), ("blocks", C.POINTER(EsBlockDesc)),
+                ("n_labels", C.c_int), ("labels", C.POINTER(EsLabelDesc)),
+                ("n_lines", C.c_int), ("lines", C.POINTER(EsLineDesc)),
+                ("n_points", C.c_int), ("points", C.POINTER(EsPointDesc)),
+                ("n_conductors", C.c_int), ("conductors", C.POINTER(EsConductorDesc)),
+                ("n_pbc", C.c_int), ("pbc", iptr),
+                ("precision", C.c_double), ("length_units", C.c_int), ("problem_type", C.c_int),
+                ("depth", C.c_double), ("ext_zo", C.c_double), ("ext_ro", C.c_double), ("ext_ri", C.c_double)]
 
 
 class Result(C.Structure):
@@ -196,6 +231,10 @@ def load_library(path: str = KERNELS_SO):
                                              C.POINTER(DistInfo), iptr, iptr, iptr, iptr]
     L.xfk_problem_create_dist.argtypes = [C.POINTER(ProblemDesc), C.c_int, vp, C.POINTER(vp)]
     L.xfk_dist_get_info.argtypes = [vp, C.POINTER(DistInfo)]
+    L.xfk_problem_create_electrostatic.argtypes = [C.POINTER(EsProblemDesc), C.c_int, C.POINTER(C.c_void_p)]
+    L.xfk_electrostatic.argtypes = [C.c_void_p, C.c_int, C.POINTER(Result)]
+    L.xfk_get_conductors.argtypes = [C.c_void_p, dptr, dptr]
+    L.xfk_conductor_charge.argtypes = [C.c_void_p, C.c_int, dptr]
     L.xfk_sort_elements.argtypes = [C.c_int, C.POINTER(C.c_uint), C.c_int, iptr]
     L.xfk_magdir_eval.argtypes = [C.c_char_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_double, dptr]
     L.xfk_lua_run.argtypes = [C.c_char_p, C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong)]
@@ -561,6 +600,108 @@ class Static2DProblem:
             out.append(dict(name=ph.name.decode(), calls=ph.calls, ms_total=ph.ms_total,
                             us_per_call=1e3 * ph.ms_total / max(1, ph.calls), bytes_per_call=ph.bytes_per_call))
         return out
+
+
+class ElectrostaticProblem:
+    """One device-resident electrostatic problem (ESolver::AnalyzeProblem).
+
+    Arrays follow the reference's in-memory state after ESolver::LoadMesh and
+    LoadProblemFile: coordinates in mm, 0-based indices, -1 for "none".
+    blocks: ex, ey, qv; labels: block, is_external; lines: format (0 fixed V,
+    1 mixed, 2 surface charge), V, qs, c0, c1; points: V, qp; conductors:
+    type (1 prescribed V, 0 prescribed total charge q), V, q.  marker /
+    conductor: per node, the point property / conductor index.  depth and
+    ext_* in the problem's length units."""
+
+    def __init__(self, *, x, y, p, lbl, blocks: Sequence[dict], labels: Sequence[dict],
+                 lines: Sequence[dict] = (), points: Sequence[dict] = (), conductors: Sequence[dict] = (),
+                 marker=None, conductor=None, e=None, pbc=None, precision=1e-8, length_units=0,
+                 problem_type: int = 0, depth: float = 1.0, ext_zo: float = 0.0, ext_ro: float = 0.0,
+                 ext_ri: float = 0.0, device=0, precond: str = "amg"):
+        L = load_library()
+        keep = _Keep()
+        bl = (EsBlockDesc * max(1, len(blocks)))()
+        for k, b in enumerate(blocks):
+            bl[k].ex, bl[k].ey, bl[k].qv = b.get("ex", 1.0), b.get("ey", 1.0), b.get("qv", 0.0)
+        lb = (EsLabelDesc * max(1, len(labels)))()
+        for k, l in enumerate(labels):
+            lb[k].block, lb[k].is_external = l["block"], int(l.get("is_external", 0))
+        ln = (EsLineDesc * max(1, len(lines)))()
+        for k, l in enumerate(lines):
+            ln[k].format, ln[k].V, ln[k].qs = l.get("format", 0), l.get("V", 0.0), l.get("qs", 0.0)
+            ln[k].c0, ln[k].c1 = l.get("c0", 0.0), l.get("c1", 0.0)
+        pt = (EsPointDesc * max(1, len(points)))()
+        for k, q in enumerate(points):
+            pt[k].V, pt[k].qp = q.get("V", 0.0), q.get("qp", 0.0)
+        co = (EsConductorDesc * max(1, len(conductors)))()
+        for k, q in enumerate(conductors):
+            co[k].type, co[k].V, co[k].q = q.get("type", 1), q.get("V", 0.0), q.get("q", 0.0)
+        D = EsProblemDesc()
+        x = np.asarray(x, dtype=np.float64)
+        D.n_nodes = len(x)
+        D.x, D.y = keep.d(x), keep.d(y)
+        D.marker = keep.i(marker) if marker is not None else None
+        D.conductor = keep.i(conductor) if conductor is not None else None
+        p = np.asarray(p, dtype=np.int32).reshape(-1)
+        D.n_elems = len(p) // 3
+        D.p = keep.i(p)
+        D.e = keep.i(np.asarray(e, dtype=np.int32).reshape(-1)) if e is not None else None
+        D.lbl = keep.i(lbl)
+        D.n_blocks, D.blocks = len(blocks), bl
+        D.n_labels, D.labels = len(labels), lb
+        D.n_lines, D.lines = len(lines), ln
+        D.n_points, D.points = len(points), pt
+        D.n_conductors, D.conductors = len(conductors), co
+        if pbc is not None and len(pbc):
+            pb = np.asarray(pbc, dtype=np.int32).reshape(-1)
+            D.n_pbc, D.pbc = len(pb) // 3, keep.i(pb)
+        else:
+            D.n_pbc, D.pbc = 0, None
+        D.precision, D.length_units, D.problem_type = precision, int(length_units), int(problem_type)
+        D.depth, D.ext_zo, D.ext_ro, D.ext_ri = depth, ext_zo, ext_ro, ext_ri
+        keep.extend([bl, lb, ln, pt, co])
+        self._keep = keep
+        self.n_nodes = self.n_rows = D.n_nodes
+        self.n_elems = D.n_elems
+        self.n_conductors = len(conductors)
+        h = C.c_void_p()
+        _check(L.xfk_problem_create_electrostatic(C.byref(D), device, C.byref(h)))
+        self._h = h
+        self.set_option(XFK_OPT_PRECOND, PRECONDS[precond])
+        self.result: Optional[Result] = None
+
+    set_option = Static2DProblem.set_option
+    memory = Static2DProblem.memory
+    close = Static2DProblem.close
+    __del__ = Static2DProblem.__del__
+    csr = Static2DProblem.csr
+
+    def solve(self, rebuild_symbolic: bool = False) -> dict:
+        r = Result()
+        _check(_lib.xfk_electrostatic(self._h, XFK_REBUILD_SYMBOLIC if rebuild_symbolic else 0, C.byref(r)))
+        self.result = r
+        return r.as_dict()
+
+    def solution(self) -> np.ndarray:
+        """V at every node."""
+        V = np.zeros(self.n_nodes)
+        _check(_lib.xfk_get_solution(self._h, V.ctypes.data_as(dptr)))
+        return V
+
+    def conductors(self):
+        """(V, q) per conductor: the prescribed or solved potential, the
+        integrated or prescribed charge (xfk_get_conductors)."""
+        n = self.n_conductors
+        V = np.zeros(max(1, n))
+        q = np.zeros(max(1, n))
+        _check(_lib.xfk_get_conductors(self._h, V.ctypes.data_as(dptr), q.ctypes.data_as(dptr)))
+        return V[:n], q[:n]
+
+    def conductor_charge(self, i: int) -> float:
+        """ChargeOnConductor(i) of the last solution (xfk_conductor_charge)."""
+        q = C.c_double()
+        _check(_lib.xfk_conductor_charge(self._h, int(i), C.byref(q)))
+        return q.value
 
 
 class Phase(C.Structure):
