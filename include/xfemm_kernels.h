@@ -204,6 +204,7 @@ enum {
                                    the V-cycle's level-0 transfers (R, P~) store f32 values,
                                    products and sums in f64; 0: f64 values.  The sweeps and the
                                    PCG's own SpMV keep A in f64. */
+    XFK_OPT_HEAT_MAX_PASSES = 13, /* heat flow: the outer loop's pass cap (>= 1, default 100) */
     XFK_OPT_NEWTON_INEXACT = 12 /* 1 (default, unless XFK_NEWTON_INEXACT=0 is set): the nonlinear
                                    loop's passes before the last solve their linear system to a
                                    forcing tolerance (Eisenstat-Walker: eta times the last Newton
@@ -528,6 +529,123 @@ int xfk_get_conductors(xfk_problem *prob, double *V, double *q);
  * order within fixed workgroup chunks and over the chunks in order, so two
  * runs give the same bits. */
 int xfk_conductor_charge(xfk_problem *prob, int conductor, double *q);
+
+/* ---------------------------------------------------------------------------
+ * Heat flow (the reference's hsolver: HSolver::AnalyzeProblem,
+ * cfemm/hsolver/hsolver.cpp:458-852, and HSolver::ChargeOnConductor, 987-1035).
+ *
+ * The descriptors carry what HSolver::LoadProblemFile and LoadMesh leave
+ * behind, as the electrostatic ones do, except that HSolver works in metres:
+ * coordinates in m, depth and ext_* in the problem's length units (inches
+ * 0.0254 m, mm 0.001, cm 0.01, m 1, mils 2.54e-5, um 1e-6), 0-based indices,
+ * -1 for "none".
+ *
+ * The problem is nonlinear when the block of any element has a K(T) table or
+ * any edge carries a radiation property; xfk_heatflow then repeats assembly
+ * and solve until sqrt(sum (T - To)^2 / sum To^2) < 100 Precision, as the
+ * reference does.  Conductors behave as in electrostatics: CircType 1 fixes
+ * the temperature of its nodes, CircType 0 (a prescribed total heat flow q, W)
+ * is merged onto its lowest-numbered node (see above and INTEGRATION.md).
+ * ------------------------------------------------------------------------- */
+/* CHMaterialProp: conductivities W/(m K), volumetric heat capacity Kt
+ * J/(m^3 K), volume heating qv W/m^3, and the K(T) table (npts knots, the same
+ * value for both directions; npts == 0: kx, ky). */
+typedef struct {
+    double kx, ky;
+    double kt;
+    double qv;
+    int npts;
+    const double *T, *K;
+} xfk_hf_block_desc;
+
+/* CHBlockLabel. */
+typedef struct {
+    int block;                  /* index into blocks */
+    int is_external;            /* axisymmetric: conformally mapped exterior region */
+} xfk_hf_label_desc;
+
+/* CHBoundaryProp. */
+typedef struct {
+    int format;                 /* BdryFormat: 0 fixed T, 1 heat flux qs, 2 convection h (T - Tinf),
+                                   3 radiation beta ksb (T^4 - Tinf^4), 4 periodic, 5 antiperiodic */
+    double Tset;
+    double qs;                  /* W/m^2 */
+    double beta;
+    double h;                   /* W/(m^2 K) */
+    double Tinf;
+} xfk_hf_line_desc;
+
+/* CHPointProp: qp == 0 fixes T at the node, else a point source qp (W/m; W when axisymmetric). */
+typedef struct {
+    double T, qp;
+} xfk_hf_point_desc;
+
+/* CHConductor. */
+typedef struct {
+    int type;                   /* CircType: 1 prescribed temperature T, 0 prescribed total heat flow q */
+    double T, q;
+} xfk_hf_conductor_desc;
+
+typedef struct {
+    int n_nodes;
+    const double *x, *y;        /* node coordinates, m (HSolver::LoadMesh) */
+    const int *marker;          /* point-prop index or -1 (may be NULL) */
+    const int *conductor;       /* conductor index or -1 (may be NULL) */
+    int n_elems;
+    const int *p;               /* 3 per element */
+    const int *e;               /* 3 per element: boundary-prop index or -1 (may be NULL) */
+    const int *lbl;             /* block label of each element */
+    int n_blocks;      const xfk_hf_block_desc *blocks;
+    int n_labels;      const xfk_hf_label_desc *labels;
+    int n_lines;       const xfk_hf_line_desc *lines;
+    int n_points;      const xfk_hf_point_desc *points;
+    int n_conductors;  const xfk_hf_conductor_desc *conductors;
+    int n_pbc;         const int *pbc;   /* 3 per pair: node, node, type (0 periodic, 1 anti) */
+    double precision;           /* [Precision] */
+    int length_units;           /* femm::LengthUnit */
+    int problem_type;           /* XFK_PLANAR or XFK_AXISYMMETRIC (x is r, y is z) */
+    double depth;               /* [Depth], user units (planar) */
+    double ext_zo, ext_ro, ext_ri;   /* [extZo] [extRo] [extRi], user units */
+    double dt;                  /* [dT], s; 0: steady */
+    const double *t_prev;       /* n_nodes: the previous time step's solution (dt != 0) */
+} xfk_hf_problem_desc;
+
+/* Upload a heat-flow problem.  The descriptor is checked before the device is
+ * touched (XFK_ERR_ARG with a message naming the cause): what
+ * xfk_problem_create_electrostatic refuses, and dt != 0 without t_prev, dt < 0,
+ * a K(T) table with npts < 0 or without its arrays.  xfk_static2d,
+ * xfk_harmonic2d and xfk_electrostatic refuse the problem (XFK_ERR_ARG). */
+int xfk_problem_create_heatflow(const xfk_hf_problem_desc *desc, int device, xfk_problem **out);
+/* HSolver::AnalyzeProblem on the device; flags: XFK_REBUILD_SYMBOLIC (the
+ * timing flags of xfk_static2d are ignored).  Every pass
+ * assembles from the last solution (the first from T = 0) and warm-starts the
+ * PCG from it.  A linear problem runs one pass, a nonlinear one at least two
+ * (no test is made while sum To^2 == 0).  The loop also ends when the solution
+ * did not change at all (the reference would spin), and with XFK_ERR_NOCONV
+ * ("heat-flow iteration did not converge in N passes") at the pass cap,
+ * XFK_OPT_HEAT_MAX_PASSES (default 100).  res->newton_iters is the pass count,
+ * res->last_res the last change.  The heat flows of the prescribed-temperature
+ * conductors are integrated after the solve.  xfk_get_solution then returns T
+ * at every node.  XFK_ERR_ARG on any other kind of problem. */
+int xfk_heatflow(xfk_problem *prob, int flags, xfk_result *res);
+/* One pass's system assembled from the nodal temperatures T (n_nodes; NULL:
+ * zeros) without solving; xfk_get_csr then shows it.  The solution, if any,
+ * is kept. */
+int xfk_heatflow_assemble(xfk_problem *prob, const double *T);
+/* The time step: dt (0: steady) and the previous solution (n_nodes; may be
+ * NULL when dt == 0).  xfk_heatflow_advance copies the last solution into the
+ * previous-solution buffer on the device and sets dt, so a time-stepping loop
+ * uploads nothing and keeps its symbolic phase. */
+int xfk_heatflow_set_step(xfk_problem *prob, double dt, const double *t_prev);
+int xfk_heatflow_advance(xfk_problem *prob, double dt);
+/* Per conductor after xfk_heatflow: T the prescribed (CircType 1) or solved
+ * (CircType 0) temperature and q the integrated (CircType 1) or prescribed
+ * (CircType 0) heat flow, W.  Either array may be NULL. */
+int xfk_hf_get_conductors(xfk_problem *prob, double *T, double *q);
+/* ChargeOnConductor(conductor) of the last solution, any conductor type, with
+ * the conductivities at the solved temperatures; summed in a fixed order, so
+ * two runs give the same bits. */
+int xfk_hf_conductor_flow(xfk_problem *prob, int conductor, double *q);
 
 /* Device views for the bench / tests (stream-ordered on the problem's stream). */
 int xfk_get_csr(xfk_problem *prob, int *rowptr, int *col, double *val, double *b);

@@ -1170,6 +1170,7 @@ static int assemble(xfk_problem *P, int iter)
     A.on_el = pre ? P->on_el.p : nullptr;
     A.n_el = P->NE;
     if (P->electro) launch_electro_rows(s, P);   // (xfk_electro.hip: a row gather of its own)
+    else if (P->heat) launch_heat_rows(s, P);    // (xfk_heat.hip: likewise)
     else launch_assemble_rows(s, P->NR, A);   // writes every entry of val and b (assembled rows)
     std::swap(P->mu1.p, P->mu1b.p);     // the state just written is read next iteration
     std::swap(P->mu1.n, P->mu1b.n);
@@ -1686,6 +1687,13 @@ static int pcg_solve(xfk_problem *P, int flag, long long max_iters)
     return rc;
 }
 
+// (xfk_heat.hip's outer loop: the two halves of one pass of static2d_run)
+int static_assemble_pass(xfk_problem *P, int iter) { return assemble(P, iter); }
+int static_pcg_pass(xfk_problem *P, int flag)
+{
+    return pcg_solve(P, flag, std::max<long long>(100000, 20LL * P->N));
+}
+
 }  // namespace xfk
 
 using namespace xfk;
@@ -1832,7 +1840,7 @@ int xfk_device_init(int device)
     XFK_CHECK(hipSetDevice(device));
     XFK_CHECK(hipFree(nullptr));
     for (hipError_t (*w)() : {warm_module_device, warm_module_pcg, warm_module_amg, warm_module_harmonic,
-                              warm_module_sort, warm_module_comm, warm_module_electro})
+                              warm_module_sort, warm_module_comm, warm_module_electro, warm_module_heat})
         XFK_CHECK(w());
     hipStream_t s[3] = {};   // a problem's solve stream, the AMG's side stream and the sort's
     for (hipStream_t &q : s) XFK_CHECK(stream_acquire(&q));
@@ -2627,6 +2635,7 @@ extern "C" {
 int xfk_static2d(xfk_problem *P, int flags, xfk_result *res)
 {
     XFK_REQUIRE(!(P && P->electro), XFK_ERR_ARG, "electrostatic problem: use xfk_electrostatic");
+    XFK_REQUIRE(!(P && P->heat), XFK_ERR_ARG, "heat-flow problem: use xfk_heatflow");
     ArenaScope arena_scope(P ? &P->arena : nullptr);
     const int rc = static2d_run(P, flags, res);
     problem_recycle(P);
@@ -2833,6 +2842,7 @@ int xfk_get_solution(xfk_problem *P, double *A)
     if (!P->comm) {
         XFK_CHECK(d2h(A, P->V.p, sizeof(double) * P->N, s));
         if (P->electro) return XFK_OK;   // V itself (esolver.cpp:760)
+        if (P->heat) return XFK_OK;      // T itself (hsolver.cpp:961)
         for (int i = 0; i < P->N; ++i) A[i] = A[i] * kC;   // L.b[i] = L.V[i]*c (static2d.cpp:1018-1021)
         if (P->axi)   // flux 2 pi r A, Webers (staticaxi.cpp:774-779)
             for (int i = 0; i < P->N; ++i) A[i] *= (P->axi_x[i] * 0.01 * 2 * kPI);
@@ -2969,6 +2979,10 @@ int xfk_set_option(xfk_problem *P, int option, double value)
     case XFK_OPT_NEWTON_INEXACT:
         XFK_REQUIRE(value == 0 || value == 1, XFK_ERR_ARG, "inexact Newton is 0 or 1");
         P->newton_inexact = (int)value;
+        return XFK_OK;
+    case XFK_OPT_HEAT_MAX_PASSES:
+        XFK_REQUIRE(value >= 1 && value == (int)value, XFK_ERR_ARG, "heat-flow pass cap must be a positive integer");
+        P->hf_max_passes = (int)value;
         return XFK_OK;
     case XFK_OPT_AMG_WLEVEL:
         XFK_REQUIRE(value >= -2 && value < kAmgMaxLevels && value == (int)value, XFK_ERR_ARG,

@@ -117,6 +117,16 @@ struct EsLine {
     int format, pad;
 };
 
+// Heat-flow tables (xfk_heat.hip), as HSolver::AnalyzeProblem reads them.
+struct HfBlock {
+    double kx, ky, kt, qv;
+    int npts, off;      // K(T) table: npts knots from hf_tk_T / hf_tk_K [off]
+};
+struct HfLine {
+    double qs, beta, h, tinf;
+    int format, pad;
+};
+
 // Scalars of one PCG solve, device resident (written by the last-arriving
 // block of each reduction kernel, read by the next launch).
 struct PcgScalars {
@@ -304,6 +314,7 @@ hipError_t warm_module_comm();
 hipError_t warm_module_device();
 hipError_t warm_module_electro();
 hipError_t warm_module_harmonic();
+hipError_t warm_module_heat();
 hipError_t warm_module_pcg();
 hipError_t warm_module_sort();
 void stream_release(hipStream_t s);   // idle streams only (the caller synchronised it)
@@ -572,6 +583,21 @@ struct xfk_problem {
     xfk::DBuf<double> es_qpart;                  // per-workgroup partials of the charge integral, then the sum
     bool es_solved = false;
 
+    // heat-flow problem (xfk_problem_create_heatflow, xfk_heat.hip): the mesh,
+    // merged-conductor and conductor-list buffers are the es_* ones above (the
+    // same meaning); the tables, the time step and the outer loop's state here
+    bool heat = false;
+    bool hf_nonlinear = false;                   // a K(T) table on some element's block, or a radiation edge
+    int hf_max_passes = 100;                     // XFK_OPT_HEAT_MAX_PASSES
+    double hf_dt = 0;                            // [dT], 0: steady
+    xfk::DBuf<xfk::HfBlock> hf_blocks;
+    xfk::DBuf<xfk::HfLine> hf_lines;
+    xfk::DBuf<double> hf_tk_T, hf_tk_K;          // the K(T) knots of all blocks
+    xfk::DBuf<double> hf_tprev;                  // N: the previous time step's solution
+    xfk::DBuf<double> hf_part;                   // per-workgroup partials of the change norm, then the two sums
+    const double *hf_vo = nullptr;               // the temperatures the next assembly reads (Vo)
+    std::vector<xfk_hf_conductor_desc> hf_cond;  // host: the conductor table (q of CircType 1 filled by the solve)
+
     // live SpMV launch timing (XFK_TIME_SPMV)
     bool time_spmv = false;
     std::vector<hipEvent_t> spmv_ev;   // pairs
@@ -675,6 +701,12 @@ void problem_recycle(xfk_problem *P);
 int reserve_first_solve(xfk_problem **out);
 // xfk_electro.hip: the electrostatic row gather (writes every entry of val and b)
 void launch_electro_rows(hipStream_t s, xfk_problem *P);
+// xfk_heat.hip: the heat-flow row gather (reads P->hf_vo; writes every entry of val and b)
+void launch_heat_rows(hipStream_t s, xfk_problem *P);
+// one pass of the static driver for xfk_heat.hip's outer loop: the numeric
+// assembly with its boundary conditions, and the PCG (flag != 0: from P->V)
+int static_assemble_pass(xfk_problem *P, int iter);
+int static_pcg_pass(xfk_problem *P, int flag);
 // sum of a host scalar over the ranks of P's communicator (no-op on one device)
 int allreduce_host(xfk_problem *P, double &v);
 int allreduce_host_n(xfk_problem *P, double *v, int n);   // n doubles summed over the ranks (host in, host out)

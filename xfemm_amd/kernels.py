@@ -38,6 +38,7 @@ XFK_OPT_AMG_COL16 = 9
 XFK_OPT_AMG_WLEVEL = 10
 XFK_OPT_AMG_F32 = 11
 XFK_OPT_NEWTON_INEXACT = 12
+XFK_OPT_HEAT_MAX_PASSES = 13
 
 # every symbol include/xfemm_kernels.h declares
 EXPORTED = (
@@ -56,6 +57,8 @@ EXPORTED = (
     "xfk_partition_plan", "xfk_partition_plan_coupled", "xfk_problem_create_dist", "xfk_dist_get_info",
     "xfk_magdir_eval", "xfk_magdir_eval_labels", "xfk_lua_run", "xfk_sort_elements",
     "xfk_problem_create_electrostatic", "xfk_electrostatic", "xfk_get_conductors", "xfk_conductor_charge",
+    "xfk_problem_create_heatflow", "xfk_heatflow", "xfk_heatflow_assemble", "xfk_heatflow_set_step",
+    "xfk_heatflow_advance", "xfk_hf_get_conductors", "xfk_hf_conductor_flow",
 )
 
 
@@ -143,6 +146,43 @@ class EsProblemDesc(C.Structure):
                 ("n_pbc", C.c_int), ("pbc", iptr),
                 ("precision", C.c_double), ("length_units", C.c_int), ("problem_type", C.c_int),
                 ("depth", C.c_double), ("ext_zo", C.c_double), ("ext_ro", C.c_double), ("ext_ri", C.c_double)]
+
+
+class HfBlockDesc(C.Structure):
+    _fields_ = [("kx", C.c_double), ("ky", C.c_double), ("kt", C.c_double), ("qv", C.c_double),
+                ("npts", C.c_int), ("T", dptr), ("K", dptr)]
+
+
+class HfLabelDesc(C.Structure):
+    _fields_ = [("block", C.c_int), ("is_external", C.c_int)]
+
+
+class HfLineDesc(C.Structure):
+    _fields_ = [("format", C.c_int), ("Tset", C.c_double), ("qs", C.c_double), ("beta", C.c_double),
+                ("h", C.c_double), ("Tinf", C.c_double)]
+
+
+class HfPointDesc(C.Structure):
+    _fields_ = [("T", C.c_double), ("qp", C.c_double)]
+
+
+class HfConductorDesc(C.Structure):
+    _fields_ = [("type", C.c_int), ("T", C.c_double), ("q", C.c_double)]
+
+
+class HfProblemDesc(C.Structure):
+    """xfk_hf_problem_desc: the state HSolver::LoadProblemFile / LoadMesh leave behind."""
+    _fields_ = [("n_nodes", C.c_int), ("x", dptr), ("y", dptr), ("marker", iptr), ("conductor", iptr),
+                ("n_elems", C.c_int), ("p", iptr), ("e", iptr), ("lbl", iptr),
+                ("n_blocks", C.c_int), ("blocks", C.POINTER(HfBlockDesc)),
+                ("n_labels", C.c_int), ("labels", C.POINTER(HfLabelDesc)),
+                ("n_lines", C.c_int), ("lines", C.POINTER(HfLineDesc)),
+                ("n_points", C.c_int), ("points", C.POINTER(HfPointDesc)),
+                ("n_conductors", C.c_int), ("conductors", C.POINTER(HfConductorDesc)),
+                ("n_pbc", C.c_int), ("pbc", iptr),
+                ("precision", C.c_double), ("length_units", C.c_int), ("problem_type", C.c_int),
+                ("depth", C.c_double), ("ext_zo", C.c_double), ("ext_ro", C.c_double), ("ext_ri", C.c_double),
+                ("dt", C.c_double), ("t_prev", dptr)]
 
 
 class Result(C.Structure):
@@ -235,6 +275,13 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_electrostatic.argtypes = [C.c_void_p, C.c_int, C.POINTER(Result)]
     L.xfk_get_conductors.argtypes = [C.c_void_p, dptr, dptr]
     L.xfk_conductor_charge.argtypes = [C.c_void_p, C.c_int, dptr]
+    L.xfk_problem_create_heatflow.argtypes = [C.POINTER(HfProblemDesc), C.c_int, C.POINTER(C.c_void_p)]
+    L.xfk_heatflow.argtypes = [C.c_void_p, C.c_int, C.POINTER(Result)]
+    L.xfk_heatflow_assemble.argtypes = [C.c_void_p, dptr]
+    L.xfk_heatflow_set_step.argtypes = [C.c_void_p, C.c_double, dptr]
+    L.xfk_heatflow_advance.argtypes = [C.c_void_p, C.c_double]
+    L.xfk_hf_get_conductors.argtypes = [C.c_void_p, dptr, dptr]
+    L.xfk_hf_conductor_flow.argtypes = [C.c_void_p, C.c_int, dptr]
     L.xfk_sort_elements.argtypes = [C.c_int, C.POINTER(C.c_uint), C.c_int, iptr]
     L.xfk_magdir_eval.argtypes = [C.c_char_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_double, dptr]
     L.xfk_lua_run.argtypes = [C.c_char_p, C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong)]
@@ -701,6 +748,138 @@ class ElectrostaticProblem:
         """ChargeOnConductor(i) of the last solution (xfk_conductor_charge)."""
         q = C.c_double()
         _check(_lib.xfk_conductor_charge(self._h, int(i), C.byref(q)))
+        return q.value
+
+
+class HeatFlowProblem:
+    """One device-resident heat-flow problem (HSolver::AnalyzeProblem).
+
+    Arrays follow the reference's in-memory state after HSolver::LoadMesh and
+    LoadProblemFile: coordinates in m, 0-based indices, -1 for "none".
+    blocks: kx, ky, kt, qv and an optional K(T) table T, K; labels: block,
+    is_external; lines: format (0 fixed Tset, 1 flux qs, 2 convection h Tinf,
+    3 radiation beta Tinf), points: T, qp; conductors: type (1 prescribed T,
+    0 prescribed total heat flow q), T, q.  marker / conductor: per node, the
+    point property / conductor index.  depth and ext_* in the problem's length
+    units.  dt, t_prev: the time step and the previous solution (0: steady)."""
+
+    def __init__(self, *, x, y, p, lbl, blocks: Sequence[dict], labels: Sequence[dict],
+                 lines: Sequence[dict] = (), points: Sequence[dict] = (), conductors: Sequence[dict] = (),
+                 marker=None, conductor=None, e=None, pbc=None, precision=1e-8, length_units=0,
+                 problem_type: int = 0, depth: float = 1.0, ext_zo: float = 0.0, ext_ro: float = 0.0,
+                 ext_ri: float = 0.0, dt: float = 0.0, t_prev=None, device=0, precond: str = "amg"):
+        L = load_library()
+        keep = _Keep()
+        bl = (HfBlockDesc * max(1, len(blocks)))()
+        for k, b in enumerate(blocks):
+            bl[k].kx, bl[k].ky = b.get("kx", 1.0), b.get("ky", 1.0)
+            bl[k].kt, bl[k].qv = b.get("kt", 0.0), b.get("qv", 0.0)
+            bl[k].npts = int(b["npts"]) if "npts" in b else len(b.get("T", ()))
+            bl[k].T = keep.d(b["T"]) if b.get("T") is not None and len(b["T"]) else None
+            bl[k].K = keep.d(b["K"]) if b.get("K") is not None and len(b["K"]) else None
+        lb = (HfLabelDesc * max(1, len(labels)))()
+        for k, l in enumerate(labels):
+            lb[k].block, lb[k].is_external = l["block"], int(l.get("is_external", 0))
+        ln = (HfLineDesc * max(1, len(lines)))()
+        for k, l in enumerate(lines):
+            ln[k].format, ln[k].Tset, ln[k].qs = l.get("format", 0), l.get("Tset", 0.0), l.get("qs", 0.0)
+            ln[k].beta, ln[k].h, ln[k].Tinf = l.get("beta", 0.0), l.get("h", 0.0), l.get("Tinf", 0.0)
+        pt = (HfPointDesc * max(1, len(points)))()
+        for k, q in enumerate(points):
+            pt[k].T, pt[k].qp = q.get("T", 0.0), q.get("qp", 0.0)
+        co = (HfConductorDesc * max(1, len(conductors)))()
+        for k, q in enumerate(conductors):
+            co[k].type, co[k].T, co[k].q = q.get("type", 1), q.get("T", 0.0), q.get("q", 0.0)
+        D = HfProblemDesc()
+        x = np.asarray(x, dtype=np.float64)
+        D.n_nodes = len(x)
+        D.x, D.y = keep.d(x), keep.d(y)
+        D.marker = keep.i(marker) if marker is not None else None
+        D.conductor = keep.i(conductor) if conductor is not None else None
+        p = np.asarray(p, dtype=np.int32).reshape(-1)
+        D.n_elems = len(p) // 3
+        D.p = keep.i(p)
+        D.e = keep.i(np.asarray(e, dtype=np.int32).reshape(-1)) if e is not None else None
+        D.lbl = keep.i(lbl)
+        D.n_blocks, D.blocks = len(blocks), bl
+        D.n_labels, D.labels = len(labels), lb
+        D.n_lines, D.lines = len(lines), ln
+        D.n_points, D.points = len(points), pt
+        D.n_conductors, D.conductors = len(conductors), co
+        if pbc is not None and len(pbc):
+            pb = np.asarray(pbc, dtype=np.int32).reshape(-1)
+            D.n_pbc, D.pbc = len(pb) // 3, keep.i(pb)
+        else:
+            D.n_pbc, D.pbc = 0, None
+        D.precision, D.length_units, D.problem_type = precision, int(length_units), int(problem_type)
+        D.depth, D.ext_zo, D.ext_ro, D.ext_ri = depth, ext_zo, ext_ro, ext_ri
+        D.dt = dt
+        D.t_prev = keep.d(self._nodal(t_prev, D.n_nodes)) if t_prev is not None else None
+        keep.extend([bl, lb, ln, pt, co])
+        self._keep = keep
+        self.n_nodes = self.n_rows = D.n_nodes
+        self.n_elems = D.n_elems
+        self.n_conductors = len(conductors)
+        h = C.c_void_p()
+        _check(L.xfk_problem_create_heatflow(C.byref(D), device, C.byref(h)))
+        self._h = h
+        self.set_option(XFK_OPT_PRECOND, PRECONDS[precond])
+        self.result: Optional[Result] = None
+
+    set_option = Static2DProblem.set_option
+    memory = Static2DProblem.memory
+    close = Static2DProblem.close
+    __del__ = Static2DProblem.__del__
+    csr = Static2DProblem.csr
+
+    @staticmethod
+    def _nodal(v, n) -> np.ndarray:
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (n,):
+            raise ValueError("expected one value per node (%d), got shape %s" % (n, v.shape))
+        return v
+
+    def solve(self, rebuild_symbolic: bool = False) -> dict:
+        """The outer loop (xfk_heatflow); newton_iters of the result is the pass count."""
+        r = Result()
+        _check(_lib.xfk_heatflow(self._h, XFK_REBUILD_SYMBOLIC if rebuild_symbolic else 0, C.byref(r)))
+        self.result = r
+        return r.as_dict()
+
+    def assemble(self, T=None):
+        """One pass's system from the nodal temperatures T (None: zeros),
+        without solving; csr() then shows it (xfk_heatflow_assemble)."""
+        t = self._nodal(T, self.n_nodes) if T is not None else None
+        _check(_lib.xfk_heatflow_assemble(self._h, t.ctypes.data_as(dptr) if t is not None else None))
+
+    def solution(self) -> np.ndarray:
+        """T at every node."""
+        V = np.zeros(self.n_nodes)
+        _check(_lib.xfk_get_solution(self._h, V.ctypes.data_as(dptr)))
+        return V
+
+    def set_step(self, dt: float, t_prev=None):
+        """The time step and the previous solution (xfk_heatflow_set_step)."""
+        t = self._nodal(t_prev, self.n_nodes) if t_prev is not None else None
+        _check(_lib.xfk_heatflow_set_step(self._h, float(dt), t.ctypes.data_as(dptr) if t is not None else None))
+
+    def advance(self, dt: float):
+        """The last solution becomes the previous one, on the device (xfk_heatflow_advance)."""
+        _check(_lib.xfk_heatflow_advance(self._h, float(dt)))
+
+    def conductors(self):
+        """(T, q) per conductor: the prescribed or solved temperature, the
+        integrated or prescribed heat flow (xfk_hf_get_conductors)."""
+        n = self.n_conductors
+        T = np.zeros(max(1, n))
+        q = np.zeros(max(1, n))
+        _check(_lib.xfk_hf_get_conductors(self._h, T.ctypes.data_as(dptr), q.ctypes.data_as(dptr)))
+        return T[:n], q[:n]
+
+    def conductor_flow(self, i: int) -> float:
+        """ChargeOnConductor(i) of the last solution (xfk_hf_conductor_flow)."""
+        q = C.c_double()
+        _check(_lib.xfk_hf_conductor_flow(self._h, int(i), C.byref(q)))
         return q.value
 
 
