@@ -1124,12 +1124,16 @@ __device__ __forceinline__ void wave_lds_sync()
 // writes it at its rank.  The network and the scan are fixed, so the sums
 // are the same bits on every run.  Only the product list (12 B per product)
 // lives in LDS: several times more rows in flight than the hash kernels.
-// The row is written padded (row * CAP) with its length; k_spgemm_compact
-// moves it to its CSR place after the length scan.
+// The wavefront's W rows are written back to back into its slab
+// (blockIdx.x * W * CAP: the exclusive prefix of the W lengths, which the
+// wavefront holds in registers, places each row) with the row lengths and
+// the slab's length; k_spgemm_compact_slab moves each slab -- one dense run
+// on both sides -- to its CSR place after the length scan.  slab_n == null
+// (XFK_SPGEMM_SLAB=0): every row padded at row * CAP, moved by k_spgemm_compact.
 template <bool PMODE, int G, int CAP>
 __global__ void __launch_bounds__(64) k_spgemm_sort(int nrows, SgX X, SgY Y, int *__restrict__ cnt_out,
                                                     int *__restrict__ pcol, double *__restrict__ pval, int *ovf,
-                                                    int *need = nullptr)
+                                                    int *need, int *__restrict__ slab_n)
 {
     constexpr int W = 64 / G;
     constexpr int S = CAP / G;
@@ -1306,7 +1310,18 @@ __global__ void __launch_bounds__(64) k_spgemm_sort(int nrows, SgX X, SgY Y, int
         hin = 0;
     }
     const int cnt = __shfl(hpre, G - 1, G);
+    // slab layout: the wavefront's W rows back to back from blockIdx.x * W * CAP
+    // (inclusive scan of the W counts, every lane of a group holding its row's;
+    // a dead row counts 0)
+    int upto = cnt;
+#pragma unroll
+    for (int off = G; off < 64; off <<= 1) {
+        const int t = __shfl_up(upto, off, 64);
+        if ((int)threadIdx.x >= off) upto += t;
+    }
+    if (slab_n && threadIdx.x == 63) slab_n[blockIdx.x] = upto;
     if (!live) return;
+    const size_t base = slab_n ? (size_t)blockIdx.x * (W * CAP) + (upto - cnt) : (size_t)row * CAP;
     int h = hin;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -1318,8 +1333,8 @@ __global__ void __launch_bounds__(64) k_spgemm_sort(int nrows, SgX X, SgY Y, int
         const int nk = s + 1 < S ? key[s + 1] : __shfl_down(key[0], 1, G);
         const bool tail = key[s] != INT_MAX && (nk != key[s] || (s + 1 == S && l == G - 1));
         if (tail) {
-            pcol[(size_t)row * CAP + h - 1] = key[s];
-            pval[(size_t)row * CAP + h - 1] = tot;
+            pcol[base + h - 1] = key[s];
+            pval[base + h - 1] = tot;
         }
     }
     if (l == 0) cnt_out[row] = cnt;
@@ -1342,6 +1357,29 @@ __global__ void k_spgemm_compact(int nrows, int cap, const int *__restrict__ cro
     for (int m = l; m < n; m += L) {
         ccol[b + m] = pcol[(size_t)row * cap + m];
         cval[b + m] = pval[(size_t)row * cap + m];
+    }
+}
+
+// dense slabs (k_spgemm_sort: slab b holds rows b * W ... back to back, slab_n[b]
+// entries from b * stride) -> CSR.  A slab's rows are consecutive, so it lands
+// as one run at crow[b * W]: both sides are dense, whatever the row lengths.
+// kSlabLanes lanes per slab (slabs of level-0 products hold 40-100 entries),
+// a workgroup moves 16 slabs.
+constexpr int kSlabLanes = 16;
+__global__ void k_spgemm_compact_slab(int nrows, int nslab, int W, int stride, const int *__restrict__ crow,
+                                      const int *__restrict__ slab_n, const int *__restrict__ pcol,
+                                      const double *__restrict__ pval, int *__restrict__ ccol,
+                                      double *__restrict__ cval, int *nnz_out)
+{
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (t == 0 && nnz_out) *nnz_out = crow[nrows];
+    const int b = (int)(t / kSlabLanes), l = (int)(t % kSlabLanes);
+    if (b >= nslab) return;
+    const int d = crow[b * W], n = slab_n[b];
+    const size_t src = (size_t)b * stride;
+    for (int m = l; m < n; m += kSlabLanes) {
+        ccol[d + m] = pcol[src + m];
+        cval[d + m] = pval[src + m];
     }
 }
 
@@ -2781,10 +2819,29 @@ int read_flag(Amg &A, hipStream_t s, int idx, int &v)
 }
 
 // C = X Y (rowptr/col/val allocated here); XFK_ERR_UNSUPPORTED on LDS overflow
-void launch_compact(hipStream_t s, int nrows, int cap, const int *crow, const int *pc, const double *pv, int *ccol,
-                    double *cval, int *nnz_out)
+// XFK_SPGEMM_SLAB=0: the sub-wave SpGEMM writes padded rows (row * cap) and the
+// compaction moves them row by row (the layout before the dense slabs)
+static bool spgemm_slab_on()
 {
-    if (cap <= 16)
+    static const bool v = [] {
+        const char *e = std::getenv("XFK_SPGEMM_SLAB");
+        return !(e && std::atoi(e) == 0);
+    }();
+    return v;
+}
+
+// rows per k_spgemm_sort wavefront (64 / G of the instance launch_sort takes for `cap`)
+static int sort_rows_per_wave(int cap) { return cap == 16 ? 16 : cap <= 64 ? 8 : cap == 128 ? 4 : 2; }
+
+// slab_n: the slab lengths (null: padded rows)
+void launch_compact(hipStream_t s, int nrows, int cap, const int *crow, const int *slab_n, const int *pc,
+                    const double *pv, int *ccol, double *cval, int *nnz_out)
+{
+    if (slab_n) {
+        const int W = sort_rows_per_wave(cap), nslab = (nrows + W - 1) / W;
+        k_spgemm_compact_slab<<<(unsigned)(((long long)nslab * kSlabLanes + kB - 1) / kB), kB, 0, s>>>(
+            nrows, nslab, W, W * cap, crow, slab_n, pc, pv, ccol, cval, nnz_out);
+    } else if (cap <= 16)
         k_spgemm_compact<4><<<(unsigned)(((long long)nrows * 4 + kB - 1) / kB), kB, 0, s>>>(nrows, cap, crow, pc, pv,
                                                                                              ccol, cval, nnz_out);
     else if (cap <= 32)
@@ -2799,11 +2856,12 @@ template <bool PMODE>
 int spgemm(Amg &M, hipStream_t s, int nrows, const SgX &X, const SgY &Y, DBuf<int> &crow, DBuf<int> &ccol,
            DBuf<double> &cval, long long &cnnz, int key = -1, bool defer = true)
 {
-    AMG_CHECK(M.cnt.alloc((size_t)nrows + 1));
+    // (behind the row lengths: the slab lengths, at most one per two rows)
+    AMG_CHECK(M.cnt.alloc((size_t)nrows + 1 + ((size_t)nrows + 1) / 2));
     AMG_CHECK(crow.alloc((size_t)nrows + 1));
-    // single pass into padded rows of `cap` slots (sort-based), then scan +
-    // compaction; returns the overflow flag (rows with more products than
-    // slots), read back with the scan's own synchronisation
+    int *slab_n = spgemm_slab_on() ? M.cnt.p + nrows + 1 : nullptr;
+    // the sort kernel of the capacity class (rows of at most `cap` slots,
+    // nrows * cap slots in pad_col / pad_val in either layout)
     int *sovf = M.dev_int.p + 6;
     auto launch_sort = [&](int cap, int *ovf, int *need = nullptr) {
         int *pc = M.pad_col.p;
@@ -2812,15 +2870,20 @@ int spgemm(Amg &M, hipStream_t s, int nrows, const SgX &X, const SgY &Y, DBuf<in
             // few lanes per row, 4-8 sorted slots per lane: many rows per
             // wavefront to overlap their dependent gathers
             if (cap == 16)
-                k_spgemm_sort<PMODE, 4, 16><<<(nrows + 15) / 16, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need);
+                k_spgemm_sort<PMODE, 4, 16><<<(nrows + 15) / 16, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
+                                                                             slab_n);
             else if (cap == 32)
-                k_spgemm_sort<PMODE, 8, 32><<<(nrows + 7) / 8, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need);
+                k_spgemm_sort<PMODE, 8, 32><<<(nrows + 7) / 8, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
+                                                                             slab_n);
             else if (cap == 64)
-                k_spgemm_sort<PMODE, 8, 64><<<(nrows + 7) / 8, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need);
+                k_spgemm_sort<PMODE, 8, 64><<<(nrows + 7) / 8, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
+                                                                             slab_n);
             else if (cap == 128)
-                k_spgemm_sort<PMODE, 16, 128><<<(nrows + 3) / 4, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need);
+                k_spgemm_sort<PMODE, 16, 128><<<(nrows + 3) / 4, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
+                                                                             slab_n);
             else
-                k_spgemm_sort<PMODE, 32, 256><<<(nrows + 1) / 2, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need);
+                k_spgemm_sort<PMODE, 32, 256><<<(nrows + 1) / 2, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
+                                                                             slab_n);
         }
     };
     // single pass into padded rows of `cap` slots (sort-based), then scan +
@@ -2839,7 +2902,7 @@ int spgemm(Amg &M, hipStream_t s, int nrows, const SgX &X, const SgY &Y, DBuf<in
         AMG_CHECK(ccol.alloc((size_t)std::max(1LL, cnnz)));
         AMG_CHECK(cval.alloc((size_t)std::max(1LL, cnnz)));
         if (nrows > 0)
-            launch_compact(s, nrows, cap, crow.p, M.pad_col.p, M.pad_val.p, ccol.p, cval.p, nullptr);
+            launch_compact(s, nrows, cap, crow.p, slab_n, M.pad_col.p, M.pad_val.p, ccol.p, cval.p, nullptr);
         return XFK_OK;
     };
     // the slot capacity this product needed in the previous setup (same
@@ -2861,7 +2924,7 @@ int spgemm(Amg &M, hipStream_t s, int nrows, const SgX &X, const SgY &Y, DBuf<in
         int rc = scan_only(M, s, M.cnt.p, crow.p, nrows);
         if (rc != XFK_OK) return rc;
         if (nrows > 0)
-            launch_compact(s, nrows, cap, crow.p, M.pad_col.p, M.pad_val.p, ccol.p, cval.p, slot + 1);
+            launch_compact(s, nrows, cap, crow.p, slab_n, M.pad_col.p, M.pad_val.p, ccol.p, cval.p, slot + 1);
         else
             AMG_CHECK(hipMemsetAsync(slot + 1, 0, sizeof(int), s));
         M.def_target[M.def_n / 2] = &cnnz;
