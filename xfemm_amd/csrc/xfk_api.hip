@@ -1169,8 +1169,8 @@ static int assemble(xfk_problem *P, int iter)
     A.dv_el = pre ? P->dv_el.p : nullptr;
     A.on_el = pre ? P->on_el.p : nullptr;
     A.n_el = P->NE;
-    if (P->electro) launch_electro_rows(s, P);   // (xfk_electro.hip: a row gather of its own)
-    else if (P->heat) launch_heat_rows(s, P);    // (xfk_heat.hip: likewise)
+    if (P->electro) launch_electro_rows(s, P);   // (xfk_potential.h's row gather, the electrostatic element)
+    else if (P->heat) launch_heat_rows(s, P);    // (likewise, the heat-flow element)
     else launch_assemble_rows(s, P->NR, A);   // writes every entry of val and b (assembled rows)
     std::swap(P->mu1.p, P->mu1b.p);     // the state just written is read next iteration
     std::swap(P->mu1.n, P->mu1b.n);

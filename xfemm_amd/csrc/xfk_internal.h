@@ -105,12 +105,14 @@ struct DevCirc {
     int type, ccase;
 };
 
+// A block label of the scalar-potential problems (xfk_potential.h).
+struct PotLabel {
+    int blk, external;
+};
+
 // Electrostatic tables (xfk_electro.hip), as ESolver::AnalyzeProblem reads them.
 struct EsBlock {
     double ex, ey, qv;
-};
-struct EsLabel {
-    int blk, external;
 };
 struct EsLine {
     double c0, c1, qs;
@@ -561,31 +563,32 @@ struct xfk_problem {
     xfk::DBuf<xfk::CcgState> hc_state;
     xfk::CcgState *hc_host = nullptr;            // pinned mirror
 
-    // electrostatic problem (xfk_problem_create_electrostatic, xfk_electro.hip):
+    // scalar-potential problems, electrostatic or heat flow (xfk_potential.h):
     // p_raw holds the MERGED connectivity (every node of a floating conductor
     // replaced by the conductor's representative node), which the symbolic
-    // phase and the row gather index rows and columns by; es_p the mesh's own
-    // connectivity, which gives the element geometry and the charge integral
-    bool electro = false;
-    double es_depth = 0;                         // Depth in mm (planar)
-    xfk::DBuf<int> es_p;                         // 3 * NE, mesh connectivity
-    xfk::DBuf<xfk::EsBlock> es_blocks;
-    xfk::DBuf<xfk::EsLabel> es_labels;
-    xfk::DBuf<xfk::EsLine> es_lines;
-    xfk::DBuf<unsigned char> es_slave;           // N: 1 for a merged-away node (identity row)
-    xfk::DBuf<int> es_slave_node, es_slave_rep;  // merged-away nodes and their representatives
-    int es_nslave = 0;
-    std::vector<xfk_es_conductor_desc> es_cond;  // host: the conductor table (q of CircType 1 filled by the solve)
-    std::vector<int> es_cond_rep;                // host: representative node of a floating conductor, else -1
-    std::vector<int> es_cel_ptr;                 // host: conductor -> [ptr, ptr + 1) into es_cel
-    xfk::DBuf<int> es_cel;                       // elements touching a node of each conductor, ascending
-    xfk::DBuf<int> es_node_cond;                 // N: conductor of each node or -1
-    xfk::DBuf<double> es_qpart;                  // per-workgroup partials of the charge integral, then the sum
-    bool es_solved = false;
+    // phase and the row gather index rows and columns by; pot_p the mesh's own
+    // connectivity, which gives the element geometry and the conductor integral
+    double pot_depth = 0;                        // Depth in the solver's length unit (planar)
+    xfk::DBuf<int> pot_p;                        // 3 * NE, mesh connectivity
+    xfk::DBuf<xfk::PotLabel> pot_labels;
+    xfk::DBuf<unsigned char> pot_slave;          // N: 1 for a merged-away node (identity row)
+    xfk::DBuf<int> pot_slave_node, pot_slave_rep;   // merged-away nodes and their representatives
+    int pot_nslave = 0;
+    std::vector<int> pot_cond_rep;               // host: representative node of a floating conductor, else -1
+    std::vector<int> pot_cel_ptr;                // host: conductor -> [ptr, ptr + 1) into pot_cel
+    xfk::DBuf<int> pot_cel;                      // elements touching a node of each conductor, ascending
+    xfk::DBuf<int> pot_node_cond;                // N: conductor of each node or -1
+    bool pot_solved = false;                     // V holds a solution, the conductor tables their integrals
 
-    // heat-flow problem (xfk_problem_create_heatflow, xfk_heat.hip): the mesh,
-    // merged-conductor and conductor-list buffers are the es_* ones above (the
-    // same meaning); the tables, the time step and the outer loop's state here
+    // electrostatic problem (xfk_problem_create_electrostatic, xfk_electro.hip)
+    bool electro = false;
+    xfk::DBuf<xfk::EsBlock> es_blocks;
+    xfk::DBuf<xfk::EsLine> es_lines;
+    std::vector<xfk_es_conductor_desc> es_cond;  // host: the conductor table (q of CircType 1 filled by the solve)
+    xfk::DBuf<double> es_qpart;                  // per-workgroup partials of the charge integral, then the sum
+
+    // heat-flow problem (xfk_problem_create_heatflow, xfk_heat.hip): the
+    // tables, the time step and the outer loop's state
     bool heat = false;
     bool hf_nonlinear = false;                   // a K(T) table on some element's block, or a radiation edge
     int hf_max_passes = 100;                     // XFK_OPT_HEAT_MAX_PASSES
@@ -699,9 +702,9 @@ int static2d_run(xfk_problem *P, int flags, xfk_result *res);
 void problem_recycle(xfk_problem *P);
 // the first solve's device footprint, reserved in the problem's arena
 int reserve_first_solve(xfk_problem **out);
-// xfk_electro.hip: the electrostatic row gather (writes every entry of val and b)
+// xfk_electro.hip: xfk_potential.h's row gather with the electrostatic element (writes every entry of val and b)
 void launch_electro_rows(hipStream_t s, xfk_problem *P);
-// xfk_heat.hip: the heat-flow row gather (reads P->hf_vo; writes every entry of val and b)
+// xfk_heat.hip: the same with the heat-flow element (reads P->hf_vo; writes every entry of val and b)
 void launch_heat_rows(hipStream_t s, xfk_problem *P);
 // one pass of the static driver for xfk_heat.hip's outer loop: the numeric
 // assembly with its boundary conditions, and the PCG (flag != 0: from P->V)
