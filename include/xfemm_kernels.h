@@ -647,6 +647,76 @@ int xfk_hf_get_conductors(xfk_problem *prob, double *T, double *q);
  * two runs give the same bits. */
 int xfk_hf_conductor_flow(xfk_problem *prob, int conductor, double *q);
 
+/* ---------------------------------------------------------------------------
+ * Post-processing of a solved electrostatic or heat-flow problem on the
+ * device: what the reference's epproc and hpproc compute (getElementD,
+ * getNodalD, blockIntegral types 0-4, getPointValues), in the reference's
+ * operation order.  Lengths are the problem's own length units, as the
+ * reference's post-processors read them.
+ *
+ * Every function returns XFK_ERR_ARG with a message naming the cause on a
+ * magnetics problem, on a problem without a solution, on a NULL argument it
+ * needs and on a negative point count.  The mesh tables (node -> element
+ * lists of the mesh's own connectivity in counter-clockwise order, the cell
+ * grid of the point search) are built at the first call that needs them and
+ * kept; the element and corner fields are cached until the next solve or
+ * xfk_pot_set_solution.  xfk_problem_memory counts all of them.
+ * ------------------------------------------------------------------------- */
+/* Load a nodal solution (n_nodes values: V, or T) into a potential problem
+ * and mark it solved: post-processing of a loaded .res / .anh.  The charges
+ * (heat flows) of the prescribed-value conductors are integrated from it, as
+ * after a solve, so xfk_get_conductors / xfk_hf_get_conductors describe the
+ * loaded solution. */
+int xfk_pot_set_solution(xfk_problem *prob, const double *V);
+/* Per element D (C/m^2) and E (V/m), or F (W/m^2) and G (K/m): x and y
+ * components interleaved, 2 n_elems each.  Either may be NULL. */
+int xfk_pot_element_fields(xfk_problem *prob, double *D, double *E);
+/* The smoothed D (F) at the three corners of every element: 6 n_elems
+ * (element, corner, component). */
+int xfk_pot_corner_fields(xfk_problem *prob, double *d);
+/* Block integrals over the elements whose label is selected (one byte per
+ * block label), every type 0-4 in one pass:
+ *   out7[0]     type 0: stored energy, J (electrostatics); average T, K (heat flow)
+ *   out7[1]     type 1: cross-section area, m^2
+ *   out7[2]     type 2: volume, m^3
+ *   out7[3..4]  type 3: average D (F), x and y
+ *   out7[5..6]  type 4: average E (G), x and y
+ * summed in a fixed order, so two runs give the same bits.
+ * xfk_pot_block_integral returns one type in the reference's numbering
+ * (out2[1] is 0 for the scalar types) and refuses types 5 and 6, the weighted
+ * stress tensor integrals. */
+int xfk_pot_block_integrals(xfk_problem *prob, const unsigned char *label_selected, double *out7);
+int xfk_pot_block_integral(xfk_problem *prob, const unsigned char *label_selected, int type, double *out2);
+/* getPointValues at n points.  elem[i] is the lowest-numbered element that
+ * contains point i by the reference's InTriangleTest, or -1 when none does;
+ * out holds 8 doubles per point --
+ *   electrostatics: V, Dx, Dy, Ex, Ey, ex, ey, nrg
+ *   heat flow:      T, Fx, Fy, Kx, Ky, Gx, Gy, 0
+ * -- all NaN for a point outside the mesh.  smooth != 0 blends the smoothed
+ * corner values instead of taking the element's D (F). */
+int xfk_pot_point_values(xfk_problem *prob, int n, const double *x, const double *y, int smooth, int *elem,
+                         double *out);
+
+/* Diagnostics of the post-processor, for tests and the lab probe; not part of
+ * the interface a caller should build on.
+ * xfk_pot_corner_branches: which case of getNodalD each (element, corner)
+ * took, 3 n_elems bytes: 0 the least-squares fit, 1-5 the reference's five
+ * "punt" cases in its order (5: the 10.0001 degree rule), 6 a singular fit
+ * (det == 0).  Runs the corner kernel again.
+ * xfk_pot_grid_info: the cell grid of the point search (built if need be):
+ * origin x0, y0, cells per length unit in x and y, cells nx, ny, the number of
+ * oversize elements, the total length of the cell lists.
+ * xfk_pot_time: HIP-event times in ms, each the median of `repeats` runs after
+ * a warm-up, of [1] the cell-grid build (count, scan, fill), [2] the
+ * element-field launch, [3] the corner-field launch, [4] the block-integral
+ * launch and its sum, [5], [6] the point kernel on the n given points with
+ * smoothing off and on; [0] is the host build of the mesh tables (wall clock).
+ * *tests_per_point: the mean number of elements a point is tested against. */
+int xfk_pot_corner_branches(xfk_problem *prob, unsigned char *branch);
+int xfk_pot_grid_info(xfk_problem *prob, double *out8);
+int xfk_pot_time(xfk_problem *prob, int n, const double *x, const double *y, int repeats, double *ms7,
+                 double *tests_per_point);
+
 /* Device views for the bench / tests (stream-ordered on the problem's stream). */
 int xfk_get_csr(xfk_problem *prob, int *rowptr, int *col, double *val, double *b);
 long long xfk_get_nnz(xfk_problem *prob);

@@ -150,6 +150,16 @@ static int conductor_charge(xfk_problem *P, int c, double *q_host)
     });
 }
 
+// the charge of the prescribed-voltage conductors from the solution in V
+// (esolver.cpp:641-643); also after xfk_pot_set_solution
+int electro_conductor_integrals(xfk_problem *P)
+{
+    int rc = XFK_OK;
+    for (int c = 0; c < (int)P->es_cond.size() && rc == XFK_OK; ++c)
+        if (P->es_cond[c].type == 1) rc = conductor_charge(P, c, &P->es_cond[c].q);
+    return rc;
+}
+
 // ESolver's units[] (esolver.cpp:65): user length units -> mm
 static const double kEsUnits[] = {25.4, 1., 10., 1000., 0.0254, 0.001};
 
@@ -204,12 +214,11 @@ int xfk_electrostatic(xfk_problem *P, int flags, xfk_result *res)
     XFK_REQUIRE(P && P->electro, XFK_ERR_ARG, "not an electrostatic problem (xfk_problem_create_electrostatic)");
     ArenaScope arena_scope(&P->arena);
     P->pot_solved = false;
+    pp_invalidate(P);
     int rc = static2d_run(P, flags, res);
     if (rc == XFK_OK) {
         launch_pot_set_slaves(P, 0);
-        // the charge of the prescribed-voltage conductors (esolver.cpp:641-643)
-        for (int c = 0; c < (int)P->es_cond.size() && rc == XFK_OK; ++c)
-            if (P->es_cond[c].type == 1) rc = conductor_charge(P, c, &P->es_cond[c].q);
+        rc = electro_conductor_integrals(P);
         if (rc == XFK_OK && hipStreamSynchronize(P->stream) != hipSuccess) {
             set_error("electrostatic post-processing failed");
             rc = XFK_ERR_HIP;

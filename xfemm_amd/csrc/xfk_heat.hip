@@ -23,34 +23,6 @@ namespace xfk {
 
 constexpr double kKsb = 5.67032e-8;   // Stefan-Boltzmann constant, W/(m^2 K^4) (femmconstants.h)
 
-// CHMaterialProp::GetK (CMaterialProp.cpp:1388-1409): Kx in kx, Ky in ky.  A
-// table gives both directions the same value: the first K at or below the
-// first knot, the last at or above the last, else the FIRST interval with
-// T[i] <= t <= T[i+1]; a t no rule catches (NaN, a table that is not
-// ascending) falls through to Kx, Ky as the reference does.
-__device__ __forceinline__ void hf_getk(const HfBlock &bp, const double *__restrict__ tkT,
-                                        const double *__restrict__ tkK, double t, double &kx, double &ky)
-{
-    kx = bp.kx;
-    ky = bp.ky;
-    const int npts = bp.npts;
-    if (npts == 0) return;
-    const double *T = tkT + bp.off, *K = tkK + bp.off;
-    if (npts == 1 || t <= T[0]) {
-        kx = ky = K[0];
-        return;
-    }
-    if (t >= T[npts - 1]) {
-        kx = ky = K[npts - 1];
-        return;
-    }
-    for (int i = 0, j = 1; j < npts; ++i, ++j)
-        if (t >= T[i] && t <= T[j]) {
-            kx = ky = K[i] + (K[j] - K[i]) * (t - T[i]) / (T[j] - T[i]);
-            return;
-        }
-}
-
 // One element of HSolver::AnalyzeProblem (hsolver.cpp:546-722), in the
 // reference's operation order; lengths in m.
 struct HfPhys {
@@ -246,6 +218,16 @@ static int conductor_flow(xfk_problem *P, int c, double *q_host)
                                                    P->hf_blocks.p, P->hf_tk_T.p, P->hf_tk_K.p, P->x.p, P->y.p,
                                                    P->V.p, P->pot_node_cond.p, P->axi ? 1 : 0, P->pot_depth, part);
     });
+}
+
+// the heat flow of the prescribed-temperature conductors from the solution in
+// V (hsolver.cpp:846-848); also after xfk_pot_set_solution
+int heat_conductor_integrals(xfk_problem *P)
+{
+    int rc = XFK_OK;
+    for (int c = 0; c < (int)P->hf_cond.size() && rc == XFK_OK; ++c)
+        if (P->hf_cond[c].type == 1) rc = conductor_flow(P, c, &P->hf_cond[c].q);
+    return rc;
 }
 
 // HSolver's units[] (hsolver.cpp:65): user length units -> m
@@ -467,11 +449,10 @@ int xfk_heatflow(xfk_problem *P, int flags, xfk_result *res)
     XFK_REQUIRE(P && P->heat, XFK_ERR_ARG, "not a heat-flow problem (xfk_problem_create_heatflow)");
     ArenaScope arena_scope(&P->arena);
     P->pot_solved = false;
+    pp_invalidate(P);
     int rc = heat_run(P, flags, res);
     if (rc == XFK_OK) {
-        // the heat flow of the prescribed-temperature conductors (hsolver.cpp:846-848)
-        for (int c = 0; c < (int)P->hf_cond.size() && rc == XFK_OK; ++c)
-            if (P->hf_cond[c].type == 1) rc = conductor_flow(P, c, &P->hf_cond[c].q);
+        rc = heat_conductor_integrals(P);
         if (rc == XFK_OK && hipStreamSynchronize(P->stream) != hipSuccess) {
             set_error("heat-flow post-processing failed");
             rc = XFK_ERR_HIP;

@@ -318,6 +318,7 @@ hipError_t warm_module_electro();
 hipError_t warm_module_harmonic();
 hipError_t warm_module_heat();
 hipError_t warm_module_pcg();
+hipError_t warm_module_postproc();
 hipError_t warm_module_sort();
 void stream_release(hipStream_t s);   // idle streams only (the caller synchronised it)
 void stream_pool_drain();
@@ -580,6 +581,28 @@ struct xfk_problem {
     xfk::DBuf<int> pot_node_cond;                // N: conductor of each node or -1
     bool pot_solved = false;                     // V holds a solution, the conductor tables their integrals
 
+    // post-processing of a scalar-potential problem (xfk_postproc.hip), in the
+    // problem's length units as the reference's post-processors work.  The
+    // mesh tables are built at the first post-processing call and kept; the
+    // fields follow the solution (pp_invalidate: a new solve, xfk_pot_set_solution)
+    std::vector<int> pot_qmark;                  // host, N: the reference's L.Q (-2 free, -1 fixed, else the conductor)
+    int pot_length_units = 0;
+    double pot_unit = 1;                         // user length unit -> the solver's
+    double pot_depth_user = 0, pot_ext_user[3] = {0, 0, 0};   // [Depth], [extRo] [extRi] [extZo], user units
+    bool pp_mesh_ready = false, pp_grid_ready = false, pp_fields_ready = false, pp_corner_ready = false;
+    xfk::DBuf<double> pp_x, pp_y;                // N: coordinates in user units
+    xfk::DBuf<int> pp_q;                         // N: pot_qmark
+    xfk::DBuf<int> pp_n2e_ptr, pp_n2e;           // node -> elements of the mesh's own connectivity, counter-clockwise
+    xfk::DBuf<int> pp_class;                     // block -> its "same material" class
+    xfk::DBuf<double> pp_D, pp_E, pp_d;          // 2 NE, 2 NE: element fields; 6 NE: smoothed corner values
+    xfk::DBuf<int> pp_cell_ptr, pp_cell_el, pp_big;   // the cell grid: lists per cell, and the oversize elements
+    int pp_nx = 0, pp_ny = 0, pp_nbig = 0;
+    double pp_x0 = 0, pp_y0 = 0, pp_ihx = 0, pp_ihy = 0;   // grid origin, cells per length
+    xfk::DBuf<double> pp_part;                   // block-integral partials and sums
+    xfk::DBuf<unsigned char> pp_sel;             // the selection mask of the last block integral
+    xfk::DBuf<double> pp_pts;                    // point batches: x, y in, 8 values out
+    xfk::DBuf<int> pp_pel;                       // ... and the element of each point
+
     // electrostatic problem (xfk_problem_create_electrostatic, xfk_electro.hip)
     bool electro = false;
     xfk::DBuf<xfk::EsBlock> es_blocks;
@@ -706,6 +729,11 @@ int reserve_first_solve(xfk_problem **out);
 void launch_electro_rows(hipStream_t s, xfk_problem *P);
 // xfk_heat.hip: the same with the heat-flow element (reads P->hf_vo; writes every entry of val and b)
 void launch_heat_rows(hipStream_t s, xfk_problem *P);
+// the integrals of the prescribed-value conductors from the solution in V, into the host conductor tables
+int electro_conductor_integrals(xfk_problem *P);
+int heat_conductor_integrals(xfk_problem *P);
+// xfk_postproc.hip: the cached fields no longer belong to the solution in V
+inline void pp_invalidate(xfk_problem *P) { P->pp_fields_ready = P->pp_corner_ready = false; }
 // one pass of the static driver for xfk_heat.hip's outer loop: the numeric
 // assembly with its boundary conditions, and the PCG (flag != 0: from P->V)
 int static_assemble_pass(xfk_problem *P, int iter);

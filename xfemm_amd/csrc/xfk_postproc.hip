@@ -1,0 +1,1116 @@
+// Post-processing of the scalar-potential problems on the device: what the
+// reference's epproc and hpproc compute from a solved electrostatic or
+// heat-flow problem, for MI355X (gfx950).
+//
+//   element fields    getElementD (epproc.cpp:735-763, hpproc.cpp:368-395) and
+//                     E(elem) (epproc.cpp:726, hpproc.cpp:851)
+//   corner fields     getNodalD (PostProcessor.cpp:894-1092)
+//   block integrals   blockIntegral types 0-4 (epproc.cpp:268-397,
+//                     hpproc.cpp:584-646)
+//   point values      InTriangleTest (PostProcessor.cpp:359-398), getPointD
+//                     (1153-1188), getPointValues (epproc.cpp:434-469,
+//                     hpproc.cpp:332-366) over a uniform cell grid
+//
+// The post-processors work in the problem's own length units with
+// LengthConv[] to metres; the solvers in mm (esolver) or m (hsolver).  The
+// coordinates are therefore divided back by the solver's unit once (pp_x,
+// pp_y) and everything below reads those.  All arithmetic is the reference's,
+// operation by operation, in double, without contraction into fused
+// multiply-adds.
+#include "xfk_potential.h"
+
+#include <chrono>
+#include <cstring>
+
+#pragma clang fp contract(off)
+
+namespace xfk {
+
+constexpr double kPpEo = 8.85418781762e-12;   // femmconstants.h:24
+// PostProcessor's LengthConv[]: user length units -> m
+static const double kPpLengthConv[] = {0.0254, 0.001, 0.01, 1., 2.54e-5, 1.e-6};
+constexpr int kPpMaxList = 20;    // getNodalD's cap on the neighbour list (q[21] with the node itself)
+// An element whose bounding box covers more cells than this goes on the
+// oversize list every point tests: the fill then writes at most this many
+// entries per element, whatever the mesh grading.  The cells are sized so
+// that the mean element's box spans about 2 x 2 of them; 64 is a box of 8 x 8.
+constexpr int kPpBigCells = 64;
+constexpr int kPpMaxCellsPerAxis = 4096;
+constexpr int kPpScanBlock = 1024;
+
+struct PpArgs {
+    const double *x, *y, *V;       // user length units; the solution
+    const int *p, *lbl;
+    const PotLabel *labels;
+    const EsBlock *es;             // electrostatics
+    const HfBlock *hf;             // heat flow
+    const double *tkT, *tkK;
+    int axi;
+    double lc;                     // LengthConv[LengthUnits]
+    double depth;                  // Depth in m
+    double ext_ro, ext_ri, ext_zo; // user units
+};
+
+// abs(CComplex) (femmcomplex.cpp:749-757)
+__host__ __device__ __forceinline__ double pp_cabs(double re, double im)
+{
+    if ((re == 0) && (im == 0)) return 0.;
+    if (fabs(re) > fabs(im)) return fabs(re) * sqrt(1. + (im / re) * (im / re));
+    return fabs(im) * sqrt(1. + (re / im) * (re / im));
+}
+
+// PostProcessor::Ctr: the thirds summed in corner order
+__device__ __forceinline__ void pp_ctr(const double (&X)[3], const double (&Y)[3], double &cx, double &cy)
+{
+    cx = 0.;
+    cy = 0.;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        cx += X[j] / 3.;
+        cy += Y[j] / 3.;
+    }
+}
+
+// AECF(elem) (PostProcessor.cpp:865-878)
+__device__ __forceinline__ double pp_aecf(const PpArgs &A, int external, double cx, double cy)
+{
+    if (!A.axi) return 1.;
+    if (!external) return 1;
+    const double r = pp_cabs(cx - 0., cy - A.ext_zo);
+    return (r * r) / (A.ext_ro * A.ext_ri);
+}
+
+// AECF(elem, p) (PostProcessor.cpp:881-891)
+__device__ __forceinline__ double pp_aecf_at(const PpArgs &A, int external, double cx, double cy, double px,
+                                             double py)
+{
+    if (!A.axi) return 1.;
+    if (!external) return 1;
+    const double r = pp_cabs(px - 0., py - A.ext_zo);
+    if (r == 0) return pp_aecf(A, external, cx, cy);
+    return (r * r) / (A.ext_ro * A.ext_ri);
+}
+
+struct PpElem {
+    int n[3];
+    double X[3], Y[3], V[3];
+    int lbl, blk, external;
+};
+
+__device__ __forceinline__ void pp_load(const PpArgs &A, int e, PpElem &E)
+{
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        E.n[j] = A.p[3 * e + j];
+        E.X[j] = A.x[E.n[j]];
+        E.Y[j] = A.y[E.n[j]];
+        E.V[j] = A.V[E.n[j]];
+    }
+    E.lbl = A.lbl[e];
+    const PotLabel lab = A.labels[E.lbl];
+    E.blk = lab.blk;
+    E.external = lab.external;
+}
+
+// the element's mean conductivities: kn += GetK(T_node) / 3. in corner order
+template <bool HEAT>
+__device__ __forceinline__ void pp_mean_k(const PpArgs &A, const PpElem &E, double &knx, double &kny)
+{
+    knx = 0.;
+    kny = 0.;
+    if (HEAT) {
+        const HfBlock bp = A.hf[E.blk];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double kx, ky;
+            hf_getk(bp, A.tkT, A.tkK, E.V[i], kx, ky);
+            knx += kx / 3.;
+            kny += ky / 3.;
+        }
+    }
+}
+
+// getElementD and E(elem) of one element
+template <bool HEAT>
+__device__ __forceinline__ void pp_element_fields(const PpArgs &A, const PpElem &E, double (&D)[2], double (&F)[2])
+{
+    double b[3], c[3];
+    b[0] = E.Y[1] - E.Y[2]; b[1] = E.Y[2] - E.Y[0]; b[2] = E.Y[0] - E.Y[1];
+    c[0] = E.X[2] - E.X[1]; c[1] = E.X[0] - E.X[2]; c[2] = E.X[1] - E.X[0];
+    const double da = (b[0] * c[1] - b[1] * c[0]);
+    double Ere = 0., Eim = 0.;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        Ere -= (E.V[i] * b[i]) / (da * A.lc);
+        Eim -= (E.V[i] * c[i]) / (da * A.lc);
+    }
+    double cx, cy;
+    pp_ctr(E.X, E.Y, cx, cy);
+    const double aecf = pp_aecf(A, E.external, cx, cy);
+    if (HEAT) {
+        double knx, kny;
+        pp_mean_k<true>(A, E, knx, kny);
+        D[0] = (Ere * knx) / aecf;
+        D[1] = (Eim * kny) / aecf;
+        F[0] = (D[0] / knx) * aecf;
+        F[1] = (D[1] / kny) * aecf;
+    } else {
+        const EsBlock bp = A.es[E.blk];
+        D[0] = (kPpEo * (Ere * bp.ex)) / aecf;
+        D[1] = (kPpEo * (Eim * bp.ey)) / aecf;
+        F[0] = ((D[0] / bp.ex) / kPpEo) * aecf;
+        F[1] = ((D[1] / bp.ey) / kPpEo) * aecf;
+    }
+}
+
+template <bool HEAT>
+__global__ void __launch_bounds__(kBlock) k_pp_element(int NE, PpArgs A, double *__restrict__ D,
+                                                       double *__restrict__ Ef)
+{
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= NE) return;
+    PpElem E;
+    pp_load(A, e, E);
+    double d[2], f[2];
+    pp_element_fields<HEAT>(A, E, d, f);
+    D[2 * e] = d[0];
+    D[2 * e + 1] = d[1];
+    Ef[2 * e] = f[0];
+    Ef[2 * e + 1] = f[1];
+}
+
+// getNodalD: one thread per (element, corner).  branch (may be null): which
+// case the corner took -- 0 nominal, 1-5 the punts in the reference's order,
+// 6 det == 0.
+template <bool HEAT>
+__global__ void __launch_bounds__(kBlock) k_pp_corner(int NE, PpArgs A, const int *__restrict__ Q,
+                                                      const int *__restrict__ n2e_ptr,
+                                                      const int *__restrict__ n2e, const int *__restrict__ cls,
+                                                      const double *__restrict__ D, double *__restrict__ d,
+                                                      unsigned char *__restrict__ branch)
+{
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= 3 * NE) return;
+    const int N = t / 3, i = t - 3 * N;
+    const int j = A.p[3 * N + i];
+    const int lblN = A.lbl[N];
+    const PotLabel labN = A.labels[lblN];
+    const int clsN = cls[labN.blk];
+    const int l0 = n2e_ptr[j], num = n2e_ptr[j + 1] - l0;
+    const int *con = n2e + l0;
+    const int Qj = Q[j];
+    int q[kPpMaxList + 1];
+    int lf = -1, rt = -1, qn = 0, eos;
+    for (eos = 0; eos < num; eos++)
+        if (con[eos] == N) break;
+    // (the element is in its own corner's list: eos < num)
+    // scan ccw
+    for (int k = 0, m = eos; k < num; k++) {
+        const int n = con[m];
+        if (cls[A.labels[A.lbl[n]].blk] != clsN) break;
+        int nos;
+        for (nos = 0; nos < 3; nos++)
+            if (A.p[3 * n + nos] == j) break;
+        if (nos == 3) break;
+        nos--;
+        if (nos < 0) nos = 2;
+        const int pn = A.p[3 * n + nos];
+        if (qn < kPpMaxList) q[qn++] = pn;
+        if ((Qj != -2) && (Q[pn] != -2)) {
+            rt = pn;
+            break;
+        }
+        m++;
+        if (m == num) m = 0;
+    }
+    // scan cw
+    for (int k = 0, m = eos; k < num; k++) {
+        const int n = con[m];
+        if (cls[A.labels[A.lbl[n]].blk] != clsN) break;
+        int nos;
+        for (nos = 0; nos < 3; nos++)
+            if (A.p[3 * n + nos] == j) break;
+        if (nos == 3) break;
+        nos++;
+        if (nos > 2) nos = 0;
+        const int pn = A.p[3 * n + nos];
+        if (qn < kPpMaxList) q[qn++] = pn;
+        if ((Qj != -2) && (Q[pn] != -2)) {
+            lf = pn;
+            break;
+        }
+        m--;
+        if (m < 0) m = num - 1;
+    }
+    const double xj = A.x[j], yj = A.y[j];
+    int br = 0;
+    if ((lf == rt) && (rt != -1) && (Qj != -2)) br = 1;
+    else if ((rt != -1) && (Qj != -2) && (lf == -1)) br = 2;
+    else if ((lf != -1) && (Qj != -2) && (rt == -1)) br = 3;
+    else if ((lf == -1) && (rt == -1) && (Qj != -2)) br = 4;
+    else if ((lf != -1) && (rt != -1) && (Qj != -2)) {
+        double xr = A.x[lf] - xj, xi_ = A.y[lf] - yj;
+        double ab = pp_cabs(xr, xi_);
+        xr /= ab;
+        xi_ /= ab;
+        double yr = xj - A.x[rt], yi_ = yj - A.y[rt];
+        ab = pp_cabs(yr, yi_);
+        yr /= ab;
+        yi_ /= ab;
+        // x / y (femmcomplex.cpp:456-474)
+        double c, ir, ii_;
+        if (fabs(yr) > fabs(yi_)) {
+            c = yi_ / yr;
+            ir = 1. / (yr * (1. + c * c));
+            ii_ = (-c) * ir;
+        } else {
+            c = yr / yi_;
+            ii_ = (-1.) / (yi_ * (1. + c * c));
+            ir = (-c) * ii_;
+        }
+        const double zr = xr * ir - xi_ * ii_, zi = xr * ii_ + xi_ * ir;
+        const double ang = ((zr == 0) && (zi == 0)) ? 0. : atan2(zi, zr);
+        if (fabs(ang) > 10.0001 * kPI / 180.) br = 5;
+    }
+    double dr = D[2 * N], di = D[2 * N + 1];
+    if (br == 0) {
+        double xi = 0, yi = 0, ii = 0, xx = 0, xy = 0, yy = 0, iv = 0, xv = 0, yv = 0;
+        q[qn++] = j;
+        const double Vj = A.V[j];
+        for (int k = 0; k < qn; k++) {
+            const double dx = A.x[q[k]] - xj;
+            const double dy = A.y[q[k]] - yj;
+            const double dv = Vj - A.V[q[k]];
+            ii += 1.;
+            xi += dx;
+            yi += dy;
+            xx += dx * dx;
+            xy += dx * dy;
+            yy += dy * dy;
+            iv += dv;
+            xv += dx * dv;
+            yv += dy * dv;
+        }
+        const double det = (-(ii * xy * xy) + 2 * xi * xy * yi - xx * yi * yi - xi * xi * yy + ii * xx * yy) * A.lc;
+        if (det == 0) br = 6;
+        else {
+            const double Ex = (iv * xy * yi - xv * yi * yi - ii * xy * yv + xi * yi * yv - iv * xi * yy + ii * xv * yy) / det;
+            const double Ey = (iv * xi * xy - ii * xv * xy + xi * xv * yi - iv * xx * yi - xi * xi * yv + ii * xx * yv) / det;
+            if (HEAT) {
+                double kx, ky;
+                hf_getk(A.hf[labN.blk], A.tkT, A.tkK, Vj, kx, ky);
+                dr = kx * Ex;
+                di = ky * Ey;
+            } else {
+                const EsBlock bp = A.es[labN.blk];
+                double X[3], Y[3], cx, cy;
+#pragma unroll
+                for (int v = 0; v < 3; ++v) {
+                    X[v] = A.x[A.p[3 * N + v]];
+                    Y[v] = A.y[A.p[3 * N + v]];
+                }
+                pp_ctr(X, Y, cx, cy);
+                const double aecf = pp_aecf_at(A, labN.external, cx, cy, xj, yj);
+                dr = (bp.ex * Ex * kPpEo) / aecf;
+                di = (bp.ey * Ey * kPpEo) / aecf;
+            }
+        }
+    }
+    d[2 * t] = dr;
+    d[2 * t + 1] = di;
+    if (branch) branch[t] = (unsigned char)br;
+}
+
+// blockIntegral types 0-4 at once: per selected element area, volume, the
+// energy (electrostatics) or volume-weighted T (heat flow), a D and a E(elem);
+// the workgroup's seven sums into part
+template <bool HEAT>
+__global__ void __launch_bounds__(kPotQBlock) k_pp_integrals(int NE, PpArgs A, const unsigned char *__restrict__ sel,
+                                                             const double *__restrict__ D,
+                                                             const double *__restrict__ Ef, double lc2,
+                                                             double *__restrict__ part)
+{
+    const int e = blockIdx.x * kPotQBlock + threadIdx.x;
+    double v[7] = {0., 0., 0., 0., 0., 0., 0.};
+    if (e < NE && sel[A.lbl[e]]) {
+        const int n[3] = {A.p[3 * e], A.p[3 * e + 1], A.p[3 * e + 2]};
+        const double X[3] = {A.x[n[0]], A.x[n[1]], A.x[n[2]]}, Y[3] = {A.y[n[0]], A.y[n[1]], A.y[n[2]]};
+        const double b0 = Y[1] - Y[2], b1 = Y[2] - Y[0], c0 = X[2] - X[1], c1 = X[0] - X[2];
+        const double a = ((b0 * c1 - b1 * c0) / 2.) * lc2;
+        double av = a;
+        if (A.axi) {
+            const double r0 = X[0] * A.lc, r1 = X[1] * A.lc, r2 = X[2] * A.lc;
+            const double R = (r0 + r1 + r2) / 3.;
+            av *= (2. * kPI * R);
+        } else {
+            av *= A.depth;
+        }
+        const double Dr = D[2 * e], Di = D[2 * e + 1], Er = Ef[2 * e], Ei = Ef[2 * e + 1];
+        if (HEAT) {
+            double T = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) T += A.V[n[k]] / 3.;
+            v[0] = av * T;
+        } else {
+            v[0] = av * (Dr * Er - Di * (-Ei)) / 2.;
+        }
+        v[1] = a;
+        v[2] = av;
+        v[3] = av * Dr;
+        v[4] = av * Di;
+        v[5] = av * Er;
+        v[6] = av * Ei;
+    }
+    block_sums<7>(v, part);
+}
+
+// --- the cell grid ----------------------------------------------------------
+
+struct PpGrid {
+    double x0, y0, ihx, ihy;
+    int nx, ny;
+};
+
+__device__ __forceinline__ int pp_cell1(double v, double v0, double ih, int n)
+{
+    const double f = floor((v - v0) * ih);
+    if (!(f > 0.)) return 0;
+    if (f >= (double)(n - 1)) return n - 1;
+    return (int)f;
+}
+
+// the cells an element's bounding box touches (the box widened by a hair, so
+// a point the edge tests accept through rounding finds the element too)
+__device__ __forceinline__ void pp_cells_of(const PpGrid &G, const double *__restrict__ x,
+                                            const double *__restrict__ y, const int *__restrict__ p, int e,
+                                            int &cx0, int &cx1, int &cy0, int &cy1)
+{
+    const double X[3] = {x[p[3 * e]], x[p[3 * e + 1]], x[p[3 * e + 2]]};
+    const double Y[3] = {y[p[3 * e]], y[p[3 * e + 1]], y[p[3 * e + 2]]};
+    const double xa = fmin(X[0], fmin(X[1], X[2])), xb = fmax(X[0], fmax(X[1], X[2]));
+    const double ya = fmin(Y[0], fmin(Y[1], Y[2])), yb = fmax(Y[0], fmax(Y[1], Y[2]));
+    const double ex = 1e-12 * fmax(fabs(xa), fabs(xb)), ey = 1e-12 * fmax(fabs(ya), fabs(yb));
+    cx0 = pp_cell1(xa - ex, G.x0, G.ihx, G.nx);
+    cx1 = pp_cell1(xb + ex, G.x0, G.ihx, G.nx);
+    cy0 = pp_cell1(ya - ey, G.y0, G.ihy, G.ny);
+    cy1 = pp_cell1(yb + ey, G.y0, G.ihy, G.ny);
+}
+
+// pass 0: count the elements per cell (and the oversize ones); pass 1: fill
+// (cnt then counts up again from zero).  The order inside a list is whatever
+// the atomics give: the search takes the lowest index, not the first hit.
+template <int PASS>
+__global__ void __launch_bounds__(kBlock) k_pp_grid(int NE, PpGrid G, const double *__restrict__ x,
+                                                    const double *__restrict__ y, const int *__restrict__ p,
+                                                    int *__restrict__ cnt, const int *__restrict__ ptr,
+                                                    int *__restrict__ cell_el, int *__restrict__ nbig,
+                                                    int *__restrict__ big)
+{
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= NE) return;
+    int cx0, cx1, cy0, cy1;
+    pp_cells_of(G, x, y, p, e, cx0, cx1, cy0, cy1);
+    if ((long long)(cx1 - cx0 + 1) * (cy1 - cy0 + 1) > kPpBigCells) {
+        const int k = atomicAdd(nbig, 1);
+        if (PASS == 1) big[k] = e;
+        return;
+    }
+    for (int cy = cy0; cy <= cy1; ++cy)
+        for (int cx = cx0; cx <= cx1; ++cx) {
+            const int c = cy * G.nx + cx;
+            const int k = atomicAdd(&cnt[c], 1);
+            if (PASS == 1) cell_el[ptr[c] + k] = e;
+        }
+}
+
+// exclusive scan of cnt[0 .. n) into ptr[0 .. n], one workgroup: a contiguous
+// run per thread, the runs' totals scanned in LDS
+__global__ void __launch_bounds__(kPpScanBlock) k_pp_scan(int n, const int *__restrict__ cnt, int *__restrict__ ptr)
+{
+    __shared__ int tot[kPpScanBlock];
+    const int per = (n + kPpScanBlock - 1) / kPpScanBlock;
+    const int a = min(n, (int)threadIdx.x * per), b = min(n, a + per);
+    int s = 0;
+    for (int i = a; i < b; ++i) s += cnt[i];
+    tot[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int k = 0; k < kPpScanBlock; ++k) {
+            const int v = tot[k];
+            tot[k] = run;
+            run += v;
+        }
+        ptr[n] = run;
+    }
+    __syncthreads();
+    s = tot[threadIdx.x];
+    for (int i = a; i < b; ++i) {
+        ptr[i] = s;
+        s += cnt[i];
+    }
+}
+
+// InTriangleTest (PostProcessor.cpp:359-398) as written: every edge oriented
+// from its lower-numbered node, < 0 rejecting one way and > 0 the other
+__device__ __forceinline__ bool pp_in_triangle(const double *__restrict__ xs, const double *__restrict__ ys,
+                                               const int *__restrict__ p, int i, double x, double y)
+{
+    const int n[3] = {p[3 * i], p[3 * i + 1], p[3 * i + 2]};
+    const double X[3] = {xs[n[0]], xs[n[1]], xs[n[2]]}, Y[3] = {ys[n[0]], ys[n[1]], ys[n[2]]};
+    bool in = true;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int k = (j + 1) % 3;
+        if (n[k] > n[j]) {
+            const double z = (X[k] - X[j]) * (y - Y[j]) - (Y[k] - Y[j]) * (x - X[j]);
+            if (z < 0) in = false;
+        } else {
+            const double z = (X[j] - X[k]) * (y - Y[k]) - (Y[j] - Y[k]) * (x - X[k]);
+            if (z > 0) in = false;
+        }
+    }
+    return in;
+}
+
+// getPointValues of n points: the lowest-numbered element containing each
+// (-1: none, its values NaN), then 8 values per point --
+//   electrostatics: V, Dx, Dy, Ex, Ey, ex, ey, nrg
+//   heat flow:      T, Fx, Fy, Kx, Ky, Gx, Gy, 0
+template <bool HEAT>
+__global__ void __launch_bounds__(kBlock) k_pp_points(int n, PpArgs A, PpGrid G, const int *__restrict__ ptr,
+                                                      const int *__restrict__ cell_el, int nbig,
+                                                      const int *__restrict__ big, const double *__restrict__ px,
+                                                      const double *__restrict__ py, int smooth,
+                                                      const double *__restrict__ D, const double *__restrict__ dc,
+                                                      int *__restrict__ elem, double *__restrict__ out,
+                                                      int *__restrict__ ntests)
+{
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const double x = px[t], y = py[t];
+    int k = 0x7fffffff;
+    if (x == x && y == y) {
+        const int c = pp_cell1(y, G.y0, G.ihy, G.ny) * G.nx + pp_cell1(x, G.x0, G.ihx, G.nx);
+        // (diagnostics: the elements this point is tested against)
+        if (ntests) ntests[t] = ptr[c + 1] - ptr[c] + nbig;
+        for (int m = ptr[c]; m < ptr[c + 1]; ++m) {
+            const int e = cell_el[m];
+            if (e < k && pp_in_triangle(A.x, A.y, A.p, e, x, y)) k = e;
+        }
+        for (int m = 0; m < nbig; ++m) {
+            const int e = big[m];
+            if (e < k && pp_in_triangle(A.x, A.y, A.p, e, x, y)) k = e;
+        }
+    }
+    double *o = out + 8 * (size_t)t;
+    if (ntests && !(x == x && y == y)) ntests[t] = 0;
+    if (k == 0x7fffffff) {
+        elem[t] = -1;
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+        for (int v = 0; v < 8; ++v) o[v] = nan;
+        return;
+    }
+    elem[t] = k;
+    PpElem E;
+    pp_load(A, k, E);
+    double a[3], b[3], c[3];
+    a[0] = E.X[1] * E.Y[2] - E.X[2] * E.Y[1];
+    a[1] = E.X[2] * E.Y[0] - E.X[0] * E.Y[2];
+    a[2] = E.X[0] * E.Y[1] - E.X[1] * E.Y[0];
+    b[0] = E.Y[1] - E.Y[2]; b[1] = E.Y[2] - E.Y[0]; b[2] = E.Y[0] - E.Y[1];
+    c[0] = E.X[2] - E.X[1]; c[1] = E.X[0] - E.X[2]; c[2] = E.X[1] - E.X[0];
+    const double da = (b[0] * c[1] - b[1] * c[0]);
+    double Dr, Di;
+    if (!smooth) {
+        Dr = D[2 * k];
+        Di = D[2 * k + 1];
+    } else {
+        Dr = 0;
+        Di = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double w = (a[i] + b[i] * x + c[i] * y);
+            Dr += (dc[6 * k + 2 * i] * w) / da;
+            Di += (dc[6 * k + 2 * i + 1] * w) / da;
+        }
+    }
+    double V = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) V += E.V[i] * (a[i] + b[i] * x + c[i] * y) / (da);
+    double cx, cy;
+    pp_ctr(E.X, E.Y, cx, cy);
+    const double aecf = pp_aecf_at(A, E.external, cx, cy, x, y);
+    o[0] = V;
+    o[1] = Dr;
+    o[2] = Di;
+    if (HEAT) {
+        double kx, ky;
+        hf_getk(A.hf[E.blk], A.tkT, A.tkK, V, kx, ky);
+        kx /= aecf;
+        ky /= aecf;
+        o[3] = kx;
+        o[4] = ky;
+        o[5] = Dr / (kx);
+        o[6] = Di / (ky);
+        o[7] = 0.;
+    } else {
+        const EsBlock bp = A.es[E.blk];
+        const double ex = bp.ex / aecf, ey = bp.ey / aecf;
+        const double Er = Dr / (ex * kPpEo), Ei = Di / (ey * kPpEo);
+        o[3] = Er;
+        o[4] = Ei;
+        o[5] = ex;
+        o[6] = ey;
+        o[7] = (Dr * Er - Di * (-Ei)) / 2.;
+    }
+}
+
+// --- host side ---------------------------------------------------------------
+
+static PpArgs pp_args(xfk_problem *P)
+{
+    PpArgs A = {};
+    A.x = P->pp_x.p;
+    A.y = P->pp_y.p;
+    A.V = P->V.p;
+    A.p = P->pot_p.p;
+    A.lbl = P->lbl_raw.p;
+    A.labels = P->pot_labels.p;
+    A.es = P->es_blocks.p;
+    A.hf = P->hf_blocks.p;
+    A.tkT = P->hf_tk_T.p;
+    A.tkK = P->hf_tk_K.p;
+    A.axi = P->axi ? 1 : 0;
+    A.lc = kPpLengthConv[P->pot_length_units];
+    // (epproc.cpp:104, hpproc.cpp:160: a depth of -1 means 1 m)
+    A.depth = P->pot_depth_user == -1 ? 1 : P->pot_depth_user * A.lc;
+    A.ext_ro = P->pot_ext_user[0];
+    A.ext_ri = P->pot_ext_user[1];
+    A.ext_zo = P->pot_ext_user[2];
+    return A;
+}
+
+// The tables that depend on the mesh alone, built at the first
+// post-processing call on the host and uploaded: coordinates in user units,
+// the Q marks, the "same material" class of each block, and the node ->
+// element lists of the mesh's own connectivity in the reference's order (a
+// stable sort by arg(centroid - node) of lists built in element order: what
+// the bubble sort of epproc.cpp:165-182 leaves).
+static int pp_mesh(xfk_problem *P)
+{
+    if (P->pp_mesh_ready) return XFK_OK;
+    hipStream_t s = P->stream;
+    const int N = P->N, NE = P->NE;
+    std::vector<double> x(N), y(N);
+    std::vector<int> p(3 * (size_t)NE), lbl(NE);
+    XFK_CHECK(d2h(x.data(), P->x.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(y.data(), P->y.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(p.data(), P->pot_p.p, sizeof(int) * 3 * (size_t)NE, s));
+    XFK_CHECK(d2h(lbl.data(), P->lbl_raw.p, sizeof(int) * NE, s));
+    const double u = P->pot_unit;
+    for (int i = 0; i < N; ++i) {
+        x[i] = x[i] / u;
+        y[i] = y[i] / u;
+    }
+    std::vector<int> ptr(N + 1, 0);
+    for (size_t k = 0; k < 3 * (size_t)NE; ++k) ptr[p[k] + 1]++;
+    for (int i = 0; i < N; ++i) ptr[i + 1] += ptr[i];
+    std::vector<int> lst(3 * (size_t)NE), fill(ptr.begin(), ptr.end() - 1);
+    for (int e = 0; e < NE; ++e)
+        for (int j = 0; j < 3; ++j) lst[fill[p[3 * (size_t)e + j]]++] = e;
+    std::atomic<bool> failed{false};   // (an exception must not leave a worker thread)
+    host_par_for(N, 1 << 14, [&](long long a, long long b) {
+      try {
+        std::vector<std::pair<double, int>> tmp;
+        for (long long i = a; i < b; ++i) {
+            const int l0 = ptr[i], num = ptr[i + 1] - l0;
+            tmp.resize(num);
+            for (int k = 0; k < num; ++k) {
+                const int e = lst[l0 + k];
+                double cx = 0., cy = 0.;
+                for (int j = 0; j < 3; ++j) {
+                    cx += x[p[3 * (size_t)e + j]] / 3.;
+                    cy += y[p[3 * (size_t)e + j]] / 3.;
+                }
+                const double ur = cx - x[i], ui = cy - y[i];
+                tmp[k] = {((ur == 0) && (ui == 0)) ? 0. : std::atan2(ui, ur), e};
+            }
+            std::stable_sort(tmp.begin(), tmp.end(),
+                             [](const std::pair<double, int> &l, const std::pair<double, int> &r) { return l.first < r.first; });
+            for (int k = 0; k < num; ++k) lst[l0 + k] = tmp[k].second;
+        }
+      } catch (...) {
+        failed = true;
+      }
+    });
+    XFK_REQUIRE(!failed, XFK_ERR_ARG, "post-processing failed: out of host memory while sorting the node lists");
+    // isSameMaterialAs (CMaterialProp.cpp:1490-1520, 1611-1618) is an
+    // equivalence: a block's class is the first block it equals
+    std::vector<int> cls;
+    if (P->electro) {
+        std::vector<EsBlock> blk(P->es_blocks.n);
+        XFK_CHECK(d2h(blk.data(), P->es_blocks.p, sizeof(EsBlock) * blk.size(), s));
+        cls.resize(blk.size());
+        for (size_t a = 0; a < blk.size(); ++a) {
+            cls[a] = (int)a;
+            for (size_t b = 0; b < a; ++b)
+                if (blk[a].ex == blk[b].ex && blk[a].ey == blk[b].ey) {
+                    cls[a] = cls[b];
+                    break;
+                }
+        }
+    } else {
+        std::vector<HfBlock> blk(P->hf_blocks.n);
+        std::vector<double> tT(P->hf_tk_T.n), tK(P->hf_tk_K.n);
+        XFK_CHECK(d2h(blk.data(), P->hf_blocks.p, sizeof(HfBlock) * blk.size(), s));
+        XFK_CHECK(d2h(tT.data(), P->hf_tk_T.p, sizeof(double) * tT.size(), s));
+        XFK_CHECK(d2h(tK.data(), P->hf_tk_K.p, sizeof(double) * tK.size(), s));
+        auto same = [&](const HfBlock &m1, const HfBlock &m2) {
+            if ((m1.kx == m2.kx) && (m1.ky == m2.ky) && (m1.npts == 0) && (m2.npts == 0)) return true;
+            if (m1.npts > 0 && m1.npts == m2.npts) {
+                for (int k = 0; k < m1.npts; ++k)
+                    if ((tT[m1.off + k] != tT[m2.off + k]) || (tK[m1.off + k] != tK[m2.off + k])) return false;
+                return true;
+            }
+            return false;
+        };
+        cls.resize(blk.size());
+        for (size_t a = 0; a < blk.size(); ++a) {
+            cls[a] = (int)a;
+            for (size_t b = 0; b < a; ++b)
+                if (same(blk[a], blk[b])) {
+                    cls[a] = cls[b];
+                    break;
+                }
+        }
+    }
+    // the grid over the bounding box: cells of twice the mean element area
+    double xa = x[0], xb = x[0], ya = y[0], yb = y[0];
+    for (int i = 1; i < N; ++i) {
+        xa = std::min(xa, x[i]);
+        xb = std::max(xb, x[i]);
+        ya = std::min(ya, y[i]);
+        yb = std::max(yb, y[i]);
+    }
+    const double W = xb - xa, H = yb - ya;
+    int nx = 1, ny = 1;
+    if (W > 0 && H > 0) {
+        const double h = std::sqrt(W * H / std::max(1., NE / 2.));
+        nx = (int)std::min<double>(kPpMaxCellsPerAxis, std::max(1., std::ceil(W / h)));
+        ny = (int)std::min<double>(kPpMaxCellsPerAxis, std::max(1., std::ceil(H / h)));
+    } else if (W > 0) {
+        nx = std::min(kPpMaxCellsPerAxis, std::max(1, NE));
+    } else if (H > 0) {
+        ny = std::min(kPpMaxCellsPerAxis, std::max(1, NE));
+    }
+    P->pp_nx = nx;
+    P->pp_ny = ny;
+    P->pp_x0 = xa;
+    P->pp_y0 = ya;
+    P->pp_ihx = W > 0 ? nx / W : 0.;
+    P->pp_ihy = H > 0 ? ny / H : 0.;
+    hipError_t e = upload(P->pp_x, x.data(), x.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_y, y.data(), y.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_q, P->pot_qmark.data(), P->pot_qmark.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_n2e_ptr, ptr.data(), ptr.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_n2e, lst.data(), lst.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_class, cls.data(), cls.size(), s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the host vectors go out of scope)
+    XFK_CHECK(e);
+    P->pp_mesh_ready = true;
+    return XFK_OK;
+}
+
+static PpGrid pp_grid_args(const xfk_problem *P)
+{
+    return PpGrid{P->pp_x0, P->pp_y0, P->pp_ihx, P->pp_ihy, P->pp_nx, P->pp_ny};
+}
+
+// count, exclusive scan, fill -- once per problem
+static int pp_grid(xfk_problem *P)
+{
+    if (P->pp_grid_ready) return XFK_OK;
+    hipStream_t s = P->stream;
+    const int NE = P->NE, nc = P->pp_nx * P->pp_ny;
+    const PpGrid G = pp_grid_args(P);
+    DBuf<int> cnt;   // nc counts, then the oversize count
+    XFK_CHECK(cnt.alloc((size_t)nc + 1));
+    XFK_CHECK(P->pp_cell_ptr.alloc((size_t)nc + 1));
+    XFK_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)nc + 1), s));
+    const int g = (NE + kBlock - 1) / kBlock;
+    k_pp_grid<0><<<g, kBlock, 0, s>>>(NE, G, P->pp_x.p, P->pp_y.p, P->pot_p.p, cnt.p, nullptr, nullptr, cnt.p + nc,
+                                      nullptr);
+    k_pp_scan<<<1, kPpScanBlock, 0, s>>>(nc, cnt.p, P->pp_cell_ptr.p);
+    XFK_CHECK(hipGetLastError());
+    int total = 0, nbig = 0;
+    XFK_CHECK(d2h(&total, P->pp_cell_ptr.p + nc, sizeof(int), s));
+    XFK_CHECK(d2h(&nbig, cnt.p + nc, sizeof(int), s));
+    XFK_CHECK(P->pp_cell_el.alloc((size_t)std::max(1, total)));
+    XFK_CHECK(P->pp_big.alloc((size_t)std::max(1, nbig)));
+    XFK_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)nc + 1), s));
+    k_pp_grid<1><<<g, kBlock, 0, s>>>(NE, G, P->pp_x.p, P->pp_y.p, P->pot_p.p, cnt.p, P->pp_cell_ptr.p,
+                                      P->pp_cell_el.p, cnt.p + nc, P->pp_big.p);
+    XFK_CHECK(hipGetLastError());
+    XFK_CHECK(hipStreamSynchronize(s));
+    P->pp_nbig = nbig;
+    P->pp_grid_ready = true;
+    return XFK_OK;
+}
+
+static int pp_fields(xfk_problem *P)
+{
+    int rc = pp_mesh(P);
+    if (rc != XFK_OK || P->pp_fields_ready) return rc;
+    const int NE = P->NE;
+    XFK_CHECK(P->pp_D.alloc(2 * (size_t)NE));
+    XFK_CHECK(P->pp_E.alloc(2 * (size_t)NE));
+    const PpArgs A = pp_args(P);
+    const int g = (NE + kBlock - 1) / kBlock;
+    if (P->heat) k_pp_element<true><<<g, kBlock, 0, P->stream>>>(NE, A, P->pp_D.p, P->pp_E.p);
+    else k_pp_element<false><<<g, kBlock, 0, P->stream>>>(NE, A, P->pp_D.p, P->pp_E.p);
+    XFK_CHECK(hipGetLastError());
+    P->pp_fields_ready = true;
+    return XFK_OK;
+}
+
+static int pp_corners(xfk_problem *P, unsigned char *branch_dev)
+{
+    int rc = pp_fields(P);
+    if (rc != XFK_OK || (P->pp_corner_ready && !branch_dev)) return rc;
+    const int NE = P->NE;
+    XFK_CHECK(P->pp_d.alloc(6 * (size_t)NE));
+    const PpArgs A = pp_args(P);
+    const int g = (3 * NE + kBlock - 1) / kBlock;
+    if (P->heat)
+        k_pp_corner<true><<<g, kBlock, 0, P->stream>>>(NE, A, P->pp_q.p, P->pp_n2e_ptr.p, P->pp_n2e.p, P->pp_class.p,
+                                                       P->pp_D.p, P->pp_d.p, branch_dev);
+    else
+        k_pp_corner<false><<<g, kBlock, 0, P->stream>>>(NE, A, P->pp_q.p, P->pp_n2e_ptr.p, P->pp_n2e.p, P->pp_class.p,
+                                                        P->pp_D.p, P->pp_d.p, branch_dev);
+    XFK_CHECK(hipGetLastError());
+    P->pp_corner_ready = true;
+    return XFK_OK;
+}
+
+// result /= CComplex(vol, 0) (femmcomplex.cpp:393, 456-474)
+static void pp_div_volume(double &re, double &im, double vol)
+{
+    const double zr = vol, zi = 0.;
+    double c, yr, yi;
+    if (std::fabs(zr) > std::fabs(zi)) {
+        c = zi / zr;
+        yr = 1. / (zr * (1. + c * c));
+        yi = (-c) * yr;
+    } else {
+        c = zr / zi;
+        yi = (-1.) / (zi * (1. + c * c));
+        yr = (-c) * yi;
+    }
+    const double r = re * yr - im * yi, i = re * yi + im * yr;
+    re = r;
+    im = i;
+}
+
+static int pp_block_integrals(xfk_problem *P, const unsigned char *sel, double *out)
+{
+    XFK_REQUIRE(sel, XFK_ERR_ARG, "null selection mask (one byte per block label)");
+    XFK_REQUIRE(out, XFK_ERR_ARG, "null output");
+    int rc = pp_fields(P);
+    if (rc != XFK_OK) return rc;
+    hipStream_t s = P->stream;
+    const int NE = P->NE, G = (NE + kPotQBlock - 1) / kPotQBlock;
+    const size_t nlab = P->pot_labels.n;
+    XFK_CHECK(P->pp_sel.alloc(nlab));
+    XFK_CHECK(hipMemcpyAsync(P->pp_sel.p, sel, nlab, hipMemcpyHostToDevice, s));
+    XFK_CHECK(P->pp_part.alloc(7 * ((size_t)G + 1)));
+    const PpArgs A = pp_args(P);
+    // (epproc squares LengthConv, hpproc takes pow(., 2.))
+    const double lc2 = P->heat ? std::pow(A.lc, 2.) : A.lc * A.lc;
+    double *sums = P->pp_part.p + 7 * (size_t)G;
+    if (P->heat) k_pp_integrals<true><<<G, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, P->pp_part.p);
+    else k_pp_integrals<false><<<G, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, P->pp_part.p);
+    k_pot_sum<7><<<1, kPotQBlock, 0, s>>>(G, P->pp_part.p, sums);
+    XFK_CHECK(hipGetLastError());
+    XFK_CHECK(d2h(out, sums, 7 * sizeof(double), s));
+    // the averaged types, divided after the loop as the reference does
+    const double vol = out[2];
+    double zero = 0.;
+    if (P->heat) pp_div_volume(out[0], zero, vol);
+    pp_div_volume(out[3], out[4], vol);
+    pp_div_volume(out[5], out[6], vol);
+    return XFK_OK;
+}
+
+}  // namespace xfk
+
+using namespace xfk;
+
+hipError_t xfk::warm_module_postproc()
+{
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_pp_scan));
+}
+
+// One post-processing entry point: no C++ exception crosses the C boundary
+// (the host tables allocate; the sorting workers catch their own), the
+// problem's device and arena are active while body runs, and blocks retired
+// meanwhile (scratch, the old block of a grown buffer) become reusable once
+// the stream is idle, as at the end of a solve.
+template <class F>
+static int pp_entry(xfk_problem *P, bool need_solution, F &&body)
+{
+    try {
+        XFK_REQUIRE(P, XFK_ERR_ARG, "null problem");
+        XFK_REQUIRE(P->electro || P->heat, XFK_ERR_ARG,
+                    "not a scalar-potential problem: post-processing is for electrostatic and heat-flow problems");
+        XFK_REQUIRE(!need_solution || P->pot_solved, XFK_ERR_ARG,
+                    "no solution yet (solve the problem or xfk_pot_set_solution)");
+        XFK_CHECK(hipSetDevice(P->device));
+        int rc;
+        {
+            ArenaScope arena_scope(&P->arena);
+            rc = body();
+        }
+        problem_recycle(P);
+        return rc;
+    } catch (const std::exception &e) {
+        set_error(std::string("post-processing failed: ") + e.what());
+        return XFK_ERR_ARG;
+    } catch (...) {
+        set_error("post-processing failed: unknown exception");
+        return XFK_ERR_ARG;
+    }
+}
+
+static int pp_launch_points(xfk_problem *P, int n, const double *px, const double *py, int smooth, double *o,
+                            int *ntests)
+{
+    const PpArgs A = pp_args(P);
+    const PpGrid G = pp_grid_args(P);
+    const int g = (n + kBlock - 1) / kBlock;
+    hipStream_t s = P->stream;
+    if (P->heat)
+        k_pp_points<true><<<g, kBlock, 0, s>>>(n, A, G, P->pp_cell_ptr.p, P->pp_cell_el.p, P->pp_nbig, P->pp_big.p, px,
+                                               py, smooth ? 1 : 0, P->pp_D.p, P->pp_d.p, P->pp_pel.p, o, ntests);
+    else
+        k_pp_points<false><<<g, kBlock, 0, s>>>(n, A, G, P->pp_cell_ptr.p, P->pp_cell_el.p, P->pp_nbig, P->pp_big.p, px,
+                                                py, smooth ? 1 : 0, P->pp_D.p, P->pp_d.p, P->pp_pel.p, o, ntests);
+    XFK_CHECK(hipGetLastError());
+    return XFK_OK;
+}
+
+// the points on the device: x, y, then 8 values each
+static int pp_upload_points(xfk_problem *P, int n, const double *x, const double *y)
+{
+    XFK_CHECK(P->pp_pts.alloc(10 * (size_t)n));
+    XFK_CHECK(P->pp_pel.alloc((size_t)n));
+    XFK_CHECK(hipMemcpyAsync(P->pp_pts.p, x, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
+    XFK_CHECK(hipMemcpyAsync(P->pp_pts.p + n, y, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
+    return XFK_OK;
+}
+
+extern "C" {
+
+int xfk_pot_set_solution(xfk_problem *P, const double *V)
+{
+    return pp_entry(P, false, [&]() -> int {
+        XFK_REQUIRE(V, XFK_ERR_ARG, "null solution");
+        P->pot_solved = false;
+        pp_invalidate(P);
+        XFK_CHECK(P->V.alloc((size_t)std::max(P->N, P->NL)));
+        XFK_CHECK(hipMemcpyAsync(P->V.p, V, sizeof(double) * P->N, hipMemcpyHostToDevice, P->stream));
+        XFK_CHECK(hipStreamSynchronize(P->stream));
+        // the integrals of the prescribed-value conductors belong to the solution
+        int rc = P->heat ? heat_conductor_integrals(P) : electro_conductor_integrals(P);
+        if (rc != XFK_OK) return rc;
+        XFK_CHECK(hipStreamSynchronize(P->stream));
+        P->pot_solved = true;
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_element_fields(xfk_problem *P, double *D, double *E)
+{
+    return pp_entry(P, true, [&]() -> int {
+        int rc = pp_fields(P);
+        if (rc != XFK_OK) return rc;
+        const size_t bytes = sizeof(double) * 2 * (size_t)P->NE;
+        if (D) XFK_CHECK(d2h(D, P->pp_D.p, bytes, P->stream));
+        if (E) XFK_CHECK(d2h(E, P->pp_E.p, bytes, P->stream));
+        XFK_CHECK(hipStreamSynchronize(P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_corner_fields(xfk_problem *P, double *d)
+{
+    return pp_entry(P, true, [&]() -> int {
+        int rc = pp_corners(P, nullptr);
+        if (rc != XFK_OK) return rc;
+        if (d) XFK_CHECK(d2h(d, P->pp_d.p, sizeof(double) * 6 * (size_t)P->NE, P->stream));
+        XFK_CHECK(hipStreamSynchronize(P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_corner_branches(xfk_problem *P, unsigned char *branch)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(branch, XFK_ERR_ARG, "null output");
+        DBuf<unsigned char> br;
+        XFK_CHECK(br.alloc(3 * (size_t)P->NE));
+        int rc = pp_corners(P, br.p);
+        if (rc != XFK_OK) return rc;
+        XFK_CHECK(d2h(branch, br.p, 3 * (size_t)P->NE, P->stream));
+        XFK_CHECK(hipStreamSynchronize(P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_block_integrals(xfk_problem *P, const unsigned char *label_selected, double *out7)
+{
+    return pp_entry(P, true, [&]() -> int { return pp_block_integrals(P, label_selected, out7); });
+}
+
+int xfk_pot_block_integral(xfk_problem *P, const unsigned char *label_selected, int type, double *out2)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(type >= 0 && type <= 6, XFK_ERR_ARG, "block integral type out of range (0-4)");
+        XFK_REQUIRE(type <= 4, XFK_ERR_ARG,
+                    "block integral types 5 and 6 (weighted stress tensor force and torque) are not supported: "
+                    "they need the mask of a Laplace solve of their own");
+        XFK_REQUIRE(out2, XFK_ERR_ARG, "null output");
+        double o[7];
+        const int rc = pp_block_integrals(P, label_selected, o);
+        if (rc != XFK_OK) return rc;
+        out2[1] = 0.;
+        if (type <= 2) out2[0] = o[type];
+        else {
+            out2[0] = o[type == 3 ? 3 : 5];
+            out2[1] = o[type == 3 ? 4 : 6];
+        }
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_point_values(xfk_problem *P, int n, const double *x, const double *y, int smooth, int *elem, double *out)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of points");
+        if (n == 0) return XFK_OK;
+        XFK_REQUIRE(x && y && elem && out, XFK_ERR_ARG, "null point arrays");
+        int rc = smooth ? pp_corners(P, nullptr) : pp_fields(P);
+        if (rc == XFK_OK) rc = pp_grid(P);
+        if (rc == XFK_OK) rc = pp_upload_points(P, n, x, y);
+        if (rc != XFK_OK) return rc;
+        double *px = P->pp_pts.p, *o = px + 2 * (size_t)n;
+        rc = pp_launch_points(P, n, px, px + n, smooth, o, nullptr);
+        if (rc != XFK_OK) return rc;
+        XFK_CHECK(d2h(elem, P->pp_pel.p, sizeof(int) * (size_t)n, P->stream));
+        XFK_CHECK(d2h(out, o, sizeof(double) * 8 * (size_t)n, P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_grid_info(xfk_problem *P, double *out8)
+{
+    return pp_entry(P, false, [&]() -> int {
+        XFK_REQUIRE(out8, XFK_ERR_ARG, "null output");
+        int rc = pp_mesh(P);
+        if (rc == XFK_OK) rc = pp_grid(P);
+        if (rc != XFK_OK) return rc;
+        int total = 0;
+        XFK_CHECK(d2h(&total, P->pp_cell_ptr.p + (size_t)P->pp_nx * P->pp_ny, sizeof(int), P->stream));
+        out8[0] = P->pp_x0;
+        out8[1] = P->pp_y0;
+        out8[2] = P->pp_ihx;
+        out8[3] = P->pp_ihy;
+        out8[4] = P->pp_nx;
+        out8[5] = P->pp_ny;
+        out8[6] = P->pp_nbig;
+        out8[7] = total;
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_time(xfk_problem *P, int n, const double *x, const double *y, int repeats, double *ms7,
+                 double *tests_per_point)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(n > 0 && x && y && repeats > 0 && ms7 && tests_per_point, XFK_ERR_ARG,
+                    "xfk_pot_time needs points, repeats > 0 and its outputs");
+        hipStream_t s = P->stream;
+        ScopedEvents<2> ev;
+        XFK_CHECK(ev.create());
+        std::vector<double> t;
+        auto median = [&]() {
+            std::sort(t.begin(), t.end());
+            const double m = t[t.size() / 2];
+            t.clear();
+            return m;
+        };
+        // f() between two events on the stream, repeats + 1 times (the first a warm-up)
+        auto timed = [&](auto f, double &out) -> int {
+            for (int k = 0; k <= repeats; ++k) {
+                XFK_CHECK(hipEventRecord(ev[0], s));
+                const int rc = f();
+                if (rc != XFK_OK) return rc;
+                XFK_CHECK(hipEventRecord(ev[1], s));
+                XFK_CHECK(hipEventSynchronize(ev[1]));
+                float ms = 0;
+                XFK_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+                if (k) t.push_back(ms);
+            }
+            out = median();
+            return XFK_OK;
+        };
+        int rc;
+        // the host build of the mesh tables (wall clock: downloads, the sort, uploads)
+        for (int k = 0; k <= repeats; ++k) {
+            P->pp_mesh_ready = false;
+            const auto t0 = std::chrono::steady_clock::now();
+            if ((rc = pp_mesh(P)) != XFK_OK) return rc;
+            if (k) t.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        }
+        ms7[0] = median();
+        if ((rc = timed([&] { P->pp_grid_ready = false; return pp_grid(P); }, ms7[1])) != XFK_OK) return rc;
+        if ((rc = timed([&] { P->pp_fields_ready = false; return pp_fields(P); }, ms7[2])) != XFK_OK) return rc;
+        if ((rc = timed([&] { P->pp_corner_ready = false; return pp_corners(P, nullptr); }, ms7[3])) != XFK_OK) return rc;
+        // the integral launch and its sum, every label selected
+        const int NE = P->NE, G = (NE + kPotQBlock - 1) / kPotQBlock;
+        const size_t nlab = P->pot_labels.n;
+        std::vector<unsigned char> sel(nlab, 1);
+        XFK_CHECK(P->pp_sel.alloc(nlab));
+        XFK_CHECK(hipMemcpyAsync(P->pp_sel.p, sel.data(), nlab, hipMemcpyHostToDevice, s));
+        XFK_CHECK(hipStreamSynchronize(s));
+        XFK_CHECK(P->pp_part.alloc(7 * ((size_t)G + 1)));
+        const PpArgs A = pp_args(P);
+        const double lc2 = P->heat ? std::pow(A.lc, 2.) : A.lc * A.lc;
+        rc = timed([&] {
+            if (P->heat) k_pp_integrals<true><<<G, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, P->pp_part.p);
+            else k_pp_integrals<false><<<G, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, P->pp_part.p);
+            k_pot_sum<7><<<1, kPotQBlock, 0, s>>>(G, P->pp_part.p, P->pp_part.p + 7 * (size_t)G);
+            return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
+        }, ms7[4]);
+        if (rc != XFK_OK) return rc;
+        if ((rc = pp_upload_points(P, n, x, y)) != XFK_OK) return rc;
+        double *px = P->pp_pts.p, *o = px + 2 * (size_t)n;
+        for (int smooth = 0; smooth < 2; ++smooth)
+            if ((rc = timed([&] { return pp_launch_points(P, n, px, px + n, smooth, o, nullptr); }, ms7[5 + smooth])) != XFK_OK)
+                return rc;
+        // the counted run: the elements each point was tested against
+        DBuf<int> cnt;
+        XFK_CHECK(cnt.alloc((size_t)n));
+        if ((rc = pp_launch_points(P, n, px, px + n, 0, o, cnt.p)) != XFK_OK) return rc;
+        std::vector<int> h(n);
+        XFK_CHECK(d2h(h.data(), cnt.p, sizeof(int) * (size_t)n, s));
+        double sum = 0;
+        for (int v : h) sum += v;
+        *tests_per_point = sum / n;
+        return XFK_OK;
+    });
+}
+
+}  // extern "C"

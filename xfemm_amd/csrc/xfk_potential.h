@@ -83,6 +83,36 @@ __device__ __forceinline__ void pot_geometry(const RowArgs &A, const double (&X)
     }
 }
 
+// (heat flow: the element of xfk_heat.hip and the post-processor of
+// xfk_postproc.hip read the conductivities through this)
+// CHMaterialProp::GetK (CMaterialProp.cpp:1388-1409): Kx in kx, Ky in ky.  A
+// table gives both directions the same value: the first K at or below the
+// first knot, the last at or above the last, else the FIRST interval with
+// T[i] <= t <= T[i+1]; a t no rule catches (NaN, a table that is not
+// ascending) falls through to Kx, Ky as the reference does.
+__device__ __forceinline__ void hf_getk(const HfBlock &bp, const double *__restrict__ tkT,
+                                        const double *__restrict__ tkK, double t, double &kx, double &ky)
+{
+    kx = bp.kx;
+    ky = bp.ky;
+    const int npts = bp.npts;
+    if (npts == 0) return;
+    const double *T = tkT + bp.off, *K = tkK + bp.off;
+    if (npts == 1 || t <= T[0]) {
+        kx = ky = K[0];
+        return;
+    }
+    if (t >= T[npts - 1]) {
+        kx = ky = K[npts - 1];
+        return;
+    }
+    for (int i = 0, j = 1; j < npts; ++i, ++j)
+        if (t >= T[i] && t <= T[j]) {
+            kx = ky = K[i] + (K[j] - K[i]) * (t - T[i]) / (T[j] - T[i]);
+            return;
+        }
+}
+
 // Row gather: one thread per CSR row i sums the contributions of the elements
 // incident on node i of the merged connectivity, in ascending element order --
 // the order the reference's Put(Get() - Me) accumulates each entry in.  Rows
@@ -383,6 +413,7 @@ struct PotentialPrep {
     GlobalPrep G;                         // what the shared build (build_local) reads: boundary data in its form
     xfk_problem_desc md = {};             // ... and the mesh under the merged connectivity
     double depth = 0;                     // [Depth] in the solver's length unit
+    double unit = 1;                      // user length units -> the solver's
     std::vector<int> rep;                 // conductor -> representative node (CircType 0 with nodes), else -1
     std::vector<int> pm;                  // merged connectivity
     std::vector<unsigned char> slave;     // per node: merged away
@@ -390,6 +421,7 @@ struct PotentialPrep {
     std::vector<int> lin_used;            // boundary properties used on edges, ascending: the compact line table
     std::vector<int> cel_ptr, cel;        // conductor -> the elements touching one of its nodes, ascending
     std::vector<int> ncond;               // per node: conductor or -1
+    std::vector<int> qmark;               // per node: L.Q as the reference writes it (the post-processor's smoothing)
     int qmax = 0;                         // the longest of those lists
 };
 
@@ -403,6 +435,7 @@ void prepare_potential(const Desc *d, double u, PotentialPrep &R)
     const int N = d->n_nodes, NE = d->n_elems, NC = d->n_conductors;
     const bool axi = d->problem_type == XFK_AXISYMMETRIC;
     R.depth = d->depth * u;
+    R.unit = u;
     auto marker = [&](int i) { return d->marker ? d->marker[i] : -1; };
     auto cond = [&](int i) { return d->conductor ? d->conductor[i] : -1; };
     auto floating = [&](int c) { return c >= 0 && d->conductors[c].type == 0; };
@@ -491,6 +524,12 @@ void prepare_potential(const Desc *d, double u, PotentialPrep &R)
                 }
             }
     G.last = G.first;
+    // L.Q as the solution file carries it (esolver.cpp:412-440, 592-600;
+    // hsolver.cpp:501-529, 766-774): a conductor's index on its nodes whatever
+    // its type, else -1 on a node with a point property (fixed by it, or marked
+    // when its point source is added) or on a BdryFormat 0 edge, else -2
+    R.qmark.resize(N);
+    for (int i = 0; i < N; ++i) R.qmark[i] = cond(i) >= 0 ? cond(i) : (marker(i) >= 0 || G.fixed[i]) ? -1 : -2;
 
     // point sources on free nodes (esolver.cpp:590-597, hsolver.cpp:764-771),
     // and the source of a floating conductor on its row (esolver.cpp:628,
@@ -564,6 +603,13 @@ hipError_t upload_potential_common(xfk_problem *P, const PotentialPrep &R, const
     P->pot_cond_rep.assign(R.rep.begin(), R.rep.begin() + NC);
     P->pot_cel_ptr = R.cel_ptr;
     P->pot_nslave = (int)R.slave_node.size();
+    P->pot_qmark = R.qmark;
+    P->pot_length_units = d->length_units;
+    P->pot_unit = R.unit;
+    P->pot_depth_user = d->depth;
+    P->pot_ext_user[0] = d->ext_ro;
+    P->pot_ext_user[1] = d->ext_ri;
+    P->pot_ext_user[2] = d->ext_zo;
     std::vector<PotLabel> lab(d->n_labels);
     for (int k = 0; k < d->n_labels; ++k) lab[k] = PotLabel{d->labels[k].block, d->labels[k].is_external ? 1 : 0};
     hipStream_t s = P->stream;

@@ -59,6 +59,8 @@ EXPORTED = (
     "xfk_problem_create_electrostatic", "xfk_electrostatic", "xfk_get_conductors", "xfk_conductor_charge",
     "xfk_problem_create_heatflow", "xfk_heatflow", "xfk_heatflow_assemble", "xfk_heatflow_set_step",
     "xfk_heatflow_advance", "xfk_hf_get_conductors", "xfk_hf_conductor_flow",
+    "xfk_pot_set_solution", "xfk_pot_element_fields", "xfk_pot_corner_fields", "xfk_pot_corner_branches",
+    "xfk_pot_block_integrals", "xfk_pot_block_integral", "xfk_pot_point_values", "xfk_pot_grid_info", "xfk_pot_time",
 )
 
 
@@ -282,6 +284,16 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_heatflow_advance.argtypes = [C.c_void_p, C.c_double]
     L.xfk_hf_get_conductors.argtypes = [C.c_void_p, dptr, dptr]
     L.xfk_hf_conductor_flow.argtypes = [C.c_void_p, C.c_int, dptr]
+    ubptr = C.POINTER(C.c_ubyte)
+    L.xfk_pot_set_solution.argtypes = [C.c_void_p, dptr]
+    L.xfk_pot_element_fields.argtypes = [C.c_void_p, dptr, dptr]
+    L.xfk_pot_corner_fields.argtypes = [C.c_void_p, dptr]
+    L.xfk_pot_corner_branches.argtypes = [C.c_void_p, ubptr]
+    L.xfk_pot_block_integrals.argtypes = [C.c_void_p, ubptr, dptr]
+    L.xfk_pot_block_integral.argtypes = [C.c_void_p, ubptr, C.c_int, dptr]
+    L.xfk_pot_grid_info.argtypes = [C.c_void_p, dptr]
+    L.xfk_pot_time.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, dptr, dptr]
+    L.xfk_pot_point_values.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, iptr, dptr]
     L.xfk_sort_elements.argtypes = [C.c_int, C.POINTER(C.c_uint), C.c_int, iptr]
     L.xfk_magdir_eval.argtypes = [C.c_char_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_double, dptr]
     L.xfk_lua_run.argtypes = [C.c_char_p, C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong)]
@@ -649,7 +661,111 @@ class Static2DProblem:
         return out
 
 
-class ElectrostaticProblem:
+class _PotentialPostProc:
+    """Post-processing shared by ElectrostaticProblem and HeatFlowProblem (the
+    reference's epproc / hpproc on the device, xfk_pot_*).  _POINT_NAMES: the
+    names of the reference's point-value struct over the 8 values per point."""
+
+    _FIELD_NAMES = ("D", "E")
+    _INTEGRAL_NAMES = ("energy", "area", "volume", "D", "E")
+
+    def set_solution(self, V):
+        """Load a nodal solution (one value per node) and mark the problem solved."""
+        v = np.ascontiguousarray(V, dtype=np.float64)
+        if v.shape != (self.n_nodes,):
+            raise ValueError("expected one value per node (%d), got shape %s" % (self.n_nodes, v.shape))
+        _check(_lib.xfk_pot_set_solution(self._h, v.ctypes.data_as(dptr)))
+
+    def element_fields(self) -> dict:
+        """Per element D and E (F and G for heat flow), (n_elems, 2) each."""
+        D = np.zeros((self.n_elems, 2))
+        E = np.zeros((self.n_elems, 2))
+        _check(_lib.xfk_pot_element_fields(self._h, D.ctypes.data_as(dptr), E.ctypes.data_as(dptr)))
+        return {self._FIELD_NAMES[0]: D, self._FIELD_NAMES[1]: E}
+
+    def corner_fields(self) -> np.ndarray:
+        """The smoothed D (F) at the corners of every element, (n_elems, 3, 2)."""
+        d = np.zeros((self.n_elems, 3, 2))
+        _check(_lib.xfk_pot_corner_fields(self._h, d.ctypes.data_as(dptr)))
+        return d
+
+    def corner_branches(self) -> np.ndarray:
+        """Diagnostic: which case of the smoothing each corner took, (n_elems,
+        3): 0 the fit, 1-5 the reference's punts in its order, 6 a singular fit."""
+        b = np.zeros((self.n_elems, 3), np.uint8)
+        _check(_lib.xfk_pot_corner_branches(self._h, b.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return b
+
+    def grid_info(self) -> dict:
+        """Diagnostic: the cell grid of the point search (xfk_pot_grid_info)."""
+        o = np.zeros(8)
+        _check(_lib.xfk_pot_grid_info(self._h, o.ctypes.data_as(dptr)))
+        return dict(x0=o[0], y0=o[1], cells_per_x=o[2], cells_per_y=o[3], nx=int(o[4]), ny=int(o[5]),
+                    oversize=int(o[6]), entries=int(o[7]))
+
+    def time_postproc(self, x, y, repeats: int = 5) -> dict:
+        """Diagnostic: HIP-event times (ms, medians) of the post-processing
+        launches and the mean triangle tests per point (xfk_pot_time)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        ms = np.zeros(7)
+        tests = C.c_double()
+        _check(_lib.xfk_pot_time(self._h, len(x), x.ctypes.data_as(dptr), y.ctypes.data_as(dptr), int(repeats),
+                                 ms.ctypes.data_as(dptr), C.byref(tests)))
+        names = ("mesh_tables_host", "cell_grid", "element_fields", "corner_fields", "block_integrals",
+                 "points", "points_smooth")
+        r = dict(zip(names, ms.tolist()))
+        r["tests_per_point"] = tests.value
+        return r
+
+    def _mask(self, selected_labels):
+        if selected_labels is None:
+            return None, None
+        m = np.zeros(max(1, self.n_labels), np.uint8)
+        s = np.asarray(selected_labels)
+        if s.dtype == np.bool_:
+            m[:len(s)] = s
+        else:
+            m[s.astype(np.int64)] = 1
+        return m, m.ctypes.data_as(C.POINTER(C.c_ubyte))
+
+    def block_integrals(self, selected_labels) -> dict:
+        """The reference's block integrals 0-4 over the elements of the selected
+        labels (indices, or a boolean mask per label)."""
+        keep, mp = self._mask(selected_labels)
+        o = np.zeros(7)
+        _check(_lib.xfk_pot_block_integrals(self._h, mp, o.ctypes.data_as(dptr)))
+        n = self._INTEGRAL_NAMES
+        return {n[0]: o[0], n[1]: o[1], n[2]: o[2], n[3]: o[3:5].copy(), n[4]: o[5:7].copy(), "raw": o}
+
+    def block_integral(self, selected_labels, kind: int) -> complex:
+        """One block integral in the reference's numbering (0-4)."""
+        keep, mp = self._mask(selected_labels)
+        o = np.zeros(2)
+        _check(_lib.xfk_pot_block_integral(self._h, mp, int(kind), o.ctypes.data_as(dptr)))
+        return complex(o[0], o[1])
+
+    def point_values(self, x, y, smooth: bool = False) -> dict:
+        """getPointValues at the points (x, y), in the problem's length units:
+        elem (the lowest-numbered containing element, -1 outside the mesh:
+        its values are NaN) and the reference's point-value fields."""
+        x = np.ascontiguousarray(np.atleast_1d(x), dtype=np.float64)
+        y = np.ascontiguousarray(np.atleast_1d(y), dtype=np.float64)
+        if x.shape != y.shape or x.ndim != 1:
+            raise ValueError("x and y must be one-dimensional and of one length")
+        n = len(x)
+        el = np.zeros(max(1, n), np.int32)
+        o = np.zeros((max(1, n), 8))
+        _check(_lib.xfk_pot_point_values(self._h, n, x.ctypes.data_as(dptr), y.ctypes.data_as(dptr), int(bool(smooth)),
+                                         el.ctypes.data_as(iptr), o.ctypes.data_as(dptr)))
+        o = o[:n]
+        r = {"elem": el[:n], "raw": o}
+        for name, cols in self._POINT_NAMES:
+            r[name] = o[:, cols].copy()
+        return r
+
+
+class ElectrostaticProblem(_PotentialPostProc):
     """One device-resident electrostatic problem (ESolver::AnalyzeProblem).
 
     Arrays follow the reference's in-memory state after ESolver::LoadMesh and
@@ -659,6 +775,8 @@ class ElectrostaticProblem:
     type (1 prescribed V, 0 prescribed total charge q), V, q.  marker /
     conductor: per node, the point property / conductor index.  depth and
     ext_* in the problem's length units."""
+
+    _POINT_NAMES = (("V", 0), ("D", [1, 2]), ("E", [3, 4]), ("e", [5, 6]), ("nrg", 7))
 
     def __init__(self, *, x, y, p, lbl, blocks: Sequence[dict], labels: Sequence[dict],
                  lines: Sequence[dict] = (), points: Sequence[dict] = (), conductors: Sequence[dict] = (),
@@ -711,6 +829,7 @@ class ElectrostaticProblem:
         self.n_nodes = self.n_rows = D.n_nodes
         self.n_elems = D.n_elems
         self.n_conductors = len(conductors)
+        self.n_labels = len(labels)
         h = C.c_void_p()
         _check(L.xfk_problem_create_electrostatic(C.byref(D), device, C.byref(h)))
         self._h = h
@@ -751,7 +870,7 @@ class ElectrostaticProblem:
         return q.value
 
 
-class HeatFlowProblem:
+class HeatFlowProblem(_PotentialPostProc):
     """One device-resident heat-flow problem (HSolver::AnalyzeProblem).
 
     Arrays follow the reference's in-memory state after HSolver::LoadMesh and
@@ -762,6 +881,10 @@ class HeatFlowProblem:
     0 prescribed total heat flow q), T, q.  marker / conductor: per node, the
     point property / conductor index.  depth and ext_* in the problem's length
     units.  dt, t_prev: the time step and the previous solution (0: steady)."""
+
+    _FIELD_NAMES = ("F", "G")
+    _INTEGRAL_NAMES = ("T", "area", "volume", "F", "G")
+    _POINT_NAMES = (("T", 0), ("F", [1, 2]), ("K", [3, 4]), ("G", [5, 6]))
 
     def __init__(self, *, x, y, p, lbl, blocks: Sequence[dict], labels: Sequence[dict],
                  lines: Sequence[dict] = (), points: Sequence[dict] = (), conductors: Sequence[dict] = (),
@@ -820,6 +943,7 @@ class HeatFlowProblem:
         self.n_nodes = self.n_rows = D.n_nodes
         self.n_elems = D.n_elems
         self.n_conductors = len(conductors)
+        self.n_labels = len(labels)
         h = C.c_void_p()
         _check(L.xfk_problem_create_heatflow(C.byref(D), device, C.byref(h)))
         self._h = h
