@@ -717,6 +717,59 @@ int xfk_pot_grid_info(xfk_problem *prob, double *out8);
 int xfk_pot_time(xfk_problem *prob, int n, const double *x, const double *y, int repeats, double *ms7,
                  double *tests_per_point);
 
+/* Diagnostics of the AMG hierarchy (single device), for tests; not part of the
+ * interface a caller should build on.  A probe holds one hierarchy built from
+ * a host CSR (full symmetric, a diagonal in every row) with the options the
+ * solver copies into it; XFK_ERR_UNSUPPORTED of the setup is passed on.
+ * trace != 0 also keeps host copies of the setup's per-level scratch.
+ * xfk_amg_probe_level_size / _level_csr: one operator of a level as the cycle
+ * reads it -- sel XFK_AMG_A / _P / _R / _PF (P~) / _RF (R~); level 0 with
+ * 16-bit tile columns returns the decoded columns unless XFK_AMG_PLAIN_COLS
+ * is or'ed in, with f32 transfers R and P~ return the widened f32 values
+ * unless XFK_AMG_F64_VALS is or'ed in.  (Not covered: with the lab switch
+ * XFK_AMG_F32_SWEEP=1 the level-0 sweeps read an f32 copy of A; XFK_AMG_A
+ * returns the f64 values.)
+ * xfk_amg_probe_tiles: tiles and int-fallback tiles of level 0's 16-bit form.
+ * xfk_amg_probe_vector: XFK_AMG_DINV (n doubles), or XFK_AMG_DENSE, the n x n
+ * operator the coarsest level applies, S M S as k_dense_mv composes it.
+ * xfk_amg_probe_trace: XFK_AMG_TR_SFLAG (nnz bytes), _SDEG, _AGG, _AGG_PRE
+ * (before the weak join), _ROOT (n ints each), _DFINV, _WF (n doubles), of a
+ * level that was coarsened.
+ * xfk_amg_probe_apply: U[:, k] = V-cycle(R[:, k]), nvec columns of n doubles
+ * each stored one after the other.
+ * xfk_amg_probe_refresh: new level-0 values (same pattern), Amg::refresh. */
+typedef struct xfk_amg_probe xfk_amg_probe;
+typedef struct {
+    int sweeps;
+    double theta, omega;
+    int dense_max, fold, col16, f32, wlevel;
+} xfk_amg_probe_opts;
+typedef struct {
+    int n, nc, fold, has16, has32, w_at;
+    long long nnz, pnnz, fnnz;
+    double weight, rho_f;       /* 1 / rho[0] (the smoother's weight) and rho[1] */
+} xfk_amg_level_info;
+typedef struct {
+    int levels, dense_coarse, cinv_f64, traced;
+    xfk_amg_level_info level[16];
+} xfk_amg_info;
+enum { XFK_AMG_A = 0, XFK_AMG_P = 1, XFK_AMG_R = 2, XFK_AMG_PF = 3, XFK_AMG_RF = 4,
+       XFK_AMG_PLAIN_COLS = 16, XFK_AMG_F64_VALS = 32 };
+enum { XFK_AMG_DINV = 0, XFK_AMG_DENSE = 1 };
+enum { XFK_AMG_TR_SFLAG = 0, XFK_AMG_TR_SDEG = 1, XFK_AMG_TR_AGG = 2, XFK_AMG_TR_AGG_PRE = 3,
+       XFK_AMG_TR_ROOT = 4, XFK_AMG_TR_DFINV = 5, XFK_AMG_TR_WF = 6 };
+int xfk_amg_probe_create(int n, const int *rowptr, const int *col, const double *val, int device,
+                         const xfk_amg_probe_opts *opts, int trace, xfk_amg_probe **out);
+int xfk_amg_probe_info(xfk_amg_probe *probe, xfk_amg_info *info);
+int xfk_amg_probe_level_size(xfk_amg_probe *probe, int level, int sel, int *rows, int *cols, long long *nnz);
+int xfk_amg_probe_level_csr(xfk_amg_probe *probe, int level, int sel, int *rowptr, int *col, double *val);
+int xfk_amg_probe_tiles(xfk_amg_probe *probe, int sel, int *tiles, int *wide);
+int xfk_amg_probe_vector(xfk_amg_probe *probe, int level, int what, double *out);
+int xfk_amg_probe_trace(xfk_amg_probe *probe, int level, int what, void *out);
+int xfk_amg_probe_apply(xfk_amg_probe *probe, int nvec, const double *R, double *U);
+int xfk_amg_probe_refresh(xfk_amg_probe *probe, const double *val, int fold);
+void xfk_amg_probe_destroy(xfk_amg_probe *probe);
+
 /* Device views for the bench / tests (stream-ordered on the problem's stream). */
 int xfk_get_csr(xfk_problem *prob, int *rowptr, int *col, double *val, double *b);
 long long xfk_get_nnz(xfk_problem *prob);

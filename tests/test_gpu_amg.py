@@ -11,7 +11,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as sla
 
 from oracle import oracle
-from util import C_ANS, assert_parity, converged, rel_err, synth_to_oracle
+from util import C_ANS, _laplace_random, assert_parity, converged, rel_err, synth_to_oracle
 from xfemm_amd import kernels, synth
 
 pytestmark = pytest.mark.gpu
@@ -104,33 +104,6 @@ def test_spgemm_capacity_overflow_rebuilds(monkeypatch):
         assert np.array_equal(P.solution(), A1)
     P.close()
     assert r["precond"] == kernels.XFK_PRECOND_AMG
-
-
-def _laplace_random(n, seed, shift=1.0):
-    """5-point operator with random positive conductances and a Dirichlet-like
-    diagonal shift on the first row of nodes (SPD; shift = 0: pure Neumann,
-    constants are the null space)."""
-    rng = np.random.default_rng(seed)
-    N = n * n
-    idx = np.arange(N).reshape(n, n)
-    rows, cols, vals = [], [], []
-    diag = np.zeros(N)
-    for a, b in [(idx[:, :-1], idx[:, 1:]), (idx[:-1, :], idx[1:, :])]:
-        a = a.ravel()
-        b = b.ravel()
-        c = np.exp(rng.uniform(-3, 3, len(a)))
-        rows += [a, b]
-        cols += [b, a]
-        vals += [-c, -c]
-        np.add.at(diag, a, c)
-        np.add.at(diag, b, c)
-    diag[idx[0]] += shift
-    rows.append(np.arange(N))
-    cols.append(np.arange(N))
-    vals.append(diag)
-    M = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(N, N))
-    M.sort_indices()
-    return M
 
 
 def test_amg_is_closer_to_the_exact_solution_than_the_reference():

@@ -4,6 +4,7 @@ from __future__ import annotations
 import os
 
 import numpy as np
+import scipy.sparse as sp
 
 from oracle import femfile
 
@@ -156,3 +157,30 @@ def assert_parity(A, Ao, Ac, tol, extra=""):
     msg = parity_message(A, Ao, Ac, tol) + extra
     assert rel_err(A, Ac) <= tol, msg
     assert rel_err(A, Ao) <= precision_bound(Ao, Ac, tol), msg
+
+
+def _laplace_random(n, seed, shift=1.0):
+    """5-point operator with random positive conductances and a Dirichlet-like
+    diagonal shift on the first row of nodes (SPD; shift = 0: pure Neumann,
+    constants are the null space)."""
+    rng = np.random.default_rng(seed)
+    N = n * n
+    idx = np.arange(N).reshape(n, n)
+    rows, cols, vals = [], [], []
+    diag = np.zeros(N)
+    for a, b in [(idx[:, :-1], idx[:, 1:]), (idx[:-1, :], idx[1:, :])]:
+        a = a.ravel()
+        b = b.ravel()
+        c = np.exp(rng.uniform(-3, 3, len(a)))
+        rows += [a, b]
+        cols += [b, a]
+        vals += [-c, -c]
+        np.add.at(diag, a, c)
+        np.add.at(diag, b, c)
+    diag[idx[0]] += shift
+    rows.append(np.arange(N))
+    cols.append(np.arange(N))
+    vals.append(diag)
+    M = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(N, N))
+    M.sort_indices()
+    return M

@@ -99,7 +99,24 @@ struct AmgStats {
     double op_complexity = 0;         // sum nnz / nnz(level 0)
 };
 
+// Host copies of the setup's per-level scratch (xfk_amg_probe_*, tests): the
+// strength flags, strong degrees, lumped diagonal inverse and smoothing weight
+// as k_amg_strength wrote them, the aggregate map after the joins, the map
+// before the weak join (k_agg_join3) and the MIS-2 roots
+struct AmgTrace {
+    struct Level {
+        int n = 0;
+        bool joined = false;          // the level was coarsened: agg, agg_pre, root are set
+        std::vector<unsigned char> sflag;
+        std::vector<int> sdeg, agg, agg_pre, root;
+        std::vector<double> dfinv, wF;
+    };
+    std::vector<Level> lev;
+};
+
 struct Amg {
+    // setup trace: null in every solve (no copy, no synchronisation then)
+    AmgTrace *trace = nullptr;
     // parameters
     double theta = 0.08;              // strength threshold
     double theta_coarse = -1.0;       // levels >= 1 (< 0: theta; XFK_AMG_THETA_COARSE overrides)
@@ -270,7 +287,18 @@ struct Amg {
     int wait_deferred(hipStream_t s, bool &overflow);
     int dense_inverse(hipStream_t s, const AmgLevel &C, int ld);
     int alloc_vectors();
+    int trace_strength(hipStream_t s, int l);
+    int trace_aggregates(hipStream_t s, int l);
     long long ap_nnz = 0;
 };
+
+// the hierarchy's diagnostics behind xfk_amg_probe_* (include/xfemm_kernels.h);
+// each synchronises `s`
+int amg_probe_info(Amg &M, hipStream_t s, xfk_amg_info *info);
+int amg_probe_level_size(Amg &M, hipStream_t s, int level, int sel, int *rows, int *cols, long long *nnz);
+int amg_probe_level_csr(Amg &M, hipStream_t s, int level, int sel, int *rowptr, int *col, double *val);
+int amg_probe_tiles(Amg &M, hipStream_t s, int sel, int *tiles, int *wide);
+int amg_probe_vector(Amg &M, hipStream_t s, int level, int what, double *out);
+int amg_probe_trace(Amg &M, int level, int what, void *out);
 
 }  // namespace xfk

@@ -2700,6 +2700,7 @@ Amg::~Amg()
     pinned_free(host_big);
     if (ev_host) (void)hipEventDestroy(ev_host);
     for (hipEvent_t e : tail_ev) (void)hipEventDestroy(e);
+    delete trace;
 }
 
 #define AMG_CHECK(call)                                                          \
@@ -4265,11 +4266,16 @@ int Amg::build(hipStream_t s, int l0)
                                                 dfinv.p, wF.p, rho_part.p, signed_strength());
         k_max_reduce<<<1, kMaxReduceT, 0, s>>>(nb_str(n), rho_part.p, omega, rho.p + 2 * l);
         if (g_prof) g_prof->end();
+        if (trace) {   // (the P SpGEMM below reuses cnt)
+            int rct = trace_strength(s, l);
+            if (rct != XFK_OK) return rct;
+        }
         if (l == kAmgMaxLevels - 1) break;   // smoother-only coarsest level
         long long nc = 0;
         int rc = aggregate(s, l, nc, true);
         if (rc != XFK_OK) return rc;
         if (nc == 0) break;
+        if (trace && (rc = trace_aggregates(s, l)) != XFK_OK) return rc;
         // AP = A P, then A_c = R (A P)
         SgX XA{A.rowptr, A.col, A.val, A.ncol_lim, nullptr, nullptr, nullptr, A.has16 ? A.a16.p : nullptr,
                A.has16 ? A.a16b.p : nullptr};
@@ -5382,6 +5388,259 @@ int Amg::vcycle(hipStream_t s, const double *r, double *u, const int *done, doub
     if (rc != XFK_OK) return rc;
     AMG_CHECK(hipGetLastError());
     return XFK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// diagnostics (xfk_amg_probe_*): the setup trace and copies of the hierarchy
+// ---------------------------------------------------------------------------
+
+namespace {
+
+template <class T>
+int fetch(hipStream_t s, std::vector<T> &h, const T *d, size_t n)
+{
+    h.resize(n);
+    if (n > 0) AMG_CHECK(hipMemcpyAsync(h.data(), d, sizeof(T) * n, hipMemcpyDeviceToHost, s));
+    AMG_CHECK(hipStreamSynchronize(s));
+    return XFK_OK;
+}
+
+}  // namespace
+
+// after k_amg_strength of level l (before the P SpGEMM reuses cnt)
+int Amg::trace_strength(hipStream_t s, int l)
+{
+    const AmgLevel &A = *L[l];
+    if ((int)trace->lev.size() <= l) trace->lev.resize((size_t)l + 1);
+    AmgTrace::Level &T = trace->lev[l];
+    T = AmgTrace::Level();
+    T.n = A.n;
+    std::vector<int> end;   // (a coarse level's nnz may still be a deferred bound)
+    int rc = fetch(s, end, A.rowptr + A.n, 1);
+    if (rc == XFK_OK) rc = fetch(s, T.sflag, (const unsigned char *)sflag.p, (size_t)end[0]);
+    if (rc == XFK_OK) rc = fetch(s, T.sdeg, (const int *)cnt.p, (size_t)A.n);
+    if (rc == XFK_OK) rc = fetch(s, T.dfinv, (const double *)dfinv.p, (size_t)A.n);
+    if (rc == XFK_OK) rc = fetch(s, T.wF, (const double *)wF.p, (size_t)A.n);
+    return rc;
+}
+
+// after the joins of level l: agg holds the joined map, agg1 the map before
+// the weak join (k_agg_join3 read it), key the MIS-2 states
+int Amg::trace_aggregates(hipStream_t s, int l)
+{
+    AmgTrace::Level &T = trace->lev[l];
+    const size_t n = (size_t)L[l]->n;
+    std::vector<MisKey> k;
+    int rc = fetch(s, T.agg, (const int *)agg.p, n);
+    if (rc == XFK_OK) rc = fetch(s, T.agg_pre, (const int *)agg1.p, n);
+    if (rc == XFK_OK) rc = fetch(s, k, (const MisKey *)key.p, n);
+    if (rc != XFK_OK) return rc;
+    T.root.resize(n);
+    for (size_t i = 0; i < n; ++i) T.root[i] = (k[i] >> 30) == kStIn;
+    T.joined = true;
+    return XFK_OK;
+}
+
+namespace {
+
+struct ProbeView {
+    int rows = 0, cols = 0;
+    const int *rp = nullptr, *cl = nullptr;
+    const double *v = nullptr;
+    const unsigned short *c16 = nullptr;
+    const int *cb = nullptr;
+    int B = 0;                      // rows per 16-bit tile
+    const float *v32 = nullptr;
+};
+
+int probe_view(Amg &M, int level, int sel, ProbeView &V)
+{
+    XFK_REQUIRE(!M.dist && level >= 0 && level < M.nlev, XFK_ERR_ARG, "AMG probe: no such level");
+    const AmgLevel &A = *M.L[level];
+    const int what = sel & 15;
+    XFK_REQUIRE(what == XFK_AMG_A || (level < M.nlev - 1 && A.nc > 0), XFK_ERR_ARG,
+                "AMG probe: the coarsest level has no transfer");
+    V = ProbeView();
+    switch (what) {
+    case XFK_AMG_A:
+        V.rows = V.cols = A.n;
+        V.rp = A.rowptr, V.cl = A.col, V.v = A.val;
+        if (A.has16) V.c16 = A.a16.p, V.cb = A.a16b.p, V.B = kCgBlock;
+        break;
+    case XFK_AMG_P:
+        V.rows = A.n, V.cols = A.nc;
+        V.rp = A.prow.p, V.cl = A.pcol.p, V.v = A.pval.p;
+        break;
+    case XFK_AMG_R:
+        V.rows = A.nc, V.cols = A.n;
+        V.rp = A.rrow.p, V.cl = A.rcol.p, V.v = A.rval.p;
+        if (A.has16) V.c16 = A.r16.p, V.cb = A.r16b.p, V.B = 256;
+        if (A.has32) V.v32 = A.r32.p;
+        break;
+    case XFK_AMG_PF:
+        XFK_REQUIRE(A.fold_formed, XFK_ERR_ARG, "AMG probe: the level has no folded transfer");
+        V.rows = A.n, V.cols = A.nc;
+        V.rp = A.ftrow.p, V.cl = A.ftcol.p, V.v = A.ftval.p;
+        if (A.has16) V.c16 = A.f16.p, V.cb = A.f16b.p, V.B = kCgBlock;
+        if (A.has32) V.v32 = A.f32v.p;
+        break;
+    case XFK_AMG_RF:
+        XFK_REQUIRE(A.fold_formed && level > 0, XFK_ERR_ARG, "AMG probe: the level has no folded restriction");
+        V.rows = A.nc, V.cols = A.n;
+        V.rp = A.frrow.p, V.cl = A.frcol.p, V.v = A.frval.p;
+        break;
+    default:
+        set_error("AMG probe: unknown operator");
+        return XFK_ERR_ARG;
+    }
+    return XFK_OK;
+}
+
+}  // namespace
+
+int amg_probe_info(Amg &M, hipStream_t s, xfk_amg_info *info)
+{
+    *info = xfk_amg_info{};
+    info->levels = M.nlev;
+    info->dense_coarse = M.dense_coarse;
+    info->cinv_f64 = M.cinv_f64;
+    info->traced = M.trace != nullptr;
+    std::vector<unsigned long long> r;
+    int rc = fetch(s, r, (const unsigned long long *)M.rho.p, (size_t)2 * kAmgMaxLevels);
+    if (rc != XFK_OK) return rc;
+    for (int l = 0; l < M.nlev && l < 16; ++l) {
+        const AmgLevel &A = *M.L[l];
+        xfk_amg_level_info &I = info->level[l];
+        const bool last = l == M.nlev - 1;
+        I.n = A.n;
+        I.nnz = A.nnz;
+        I.nc = last ? 0 : A.nc;
+        I.pnnz = last ? 0 : A.pnnz;
+        I.fnnz = (last || !A.fold_formed) ? 0 : A.fnnz;
+        I.fold = !last && A.fold;
+        I.has16 = A.has16;
+        I.has32 = A.has32;
+        I.w_at = !last && M.w_at(l);
+        double ra, rf;
+        std::memcpy(&ra, &r[2 * l], 8);
+        std::memcpy(&rf, &r[2 * l + 1], 8);
+        I.weight = ra > 0.0 ? 1.0 / ra : 0.0;
+        I.rho_f = rf;
+    }
+    return XFK_OK;
+}
+
+int amg_probe_level_size(Amg &M, hipStream_t s, int level, int sel, int *rows, int *cols, long long *nnz)
+{
+    ProbeView V;
+    int rc = probe_view(M, level, sel, V);
+    if (rc != XFK_OK) return rc;
+    std::vector<int> end;
+    if ((rc = fetch(s, end, V.rp + V.rows, 1)) != XFK_OK) return rc;
+    *rows = V.rows;
+    *cols = V.cols;
+    *nnz = end[0];
+    return XFK_OK;
+}
+
+int amg_probe_level_csr(Amg &M, hipStream_t s, int level, int sel, int *rowptr, int *col, double *val)
+{
+    ProbeView V;
+    int rc = probe_view(M, level, sel, V);
+    if (rc != XFK_OK) return rc;
+    std::vector<int> rp, cl, cb;
+    std::vector<double> v;
+    if ((rc = fetch(s, rp, V.rp, (size_t)V.rows + 1)) != XFK_OK) return rc;
+    const size_t nz = (size_t)rp[V.rows];
+    if ((rc = fetch(s, cl, V.cl, nz)) != XFK_OK) return rc;
+    if (V.c16 && !(sel & XFK_AMG_PLAIN_COLS)) {
+        // the tile logic of ColView / cg_tile_spmv16: a tile with a base reads base + offset
+        std::vector<unsigned short> c16;
+        const int nt = (V.rows + V.B - 1) / V.B;
+        if ((rc = fetch(s, c16, V.c16, nz)) != XFK_OK || (rc = fetch(s, cb, V.cb, (size_t)nt)) != XFK_OK) return rc;
+        for (int t = 0; t < nt; ++t) {
+            if (cb[t] == kNoColBase) continue;
+            for (int k = rp[t * V.B]; k < rp[std::min(V.rows, (t + 1) * V.B)]; ++k) cl[k] = cb[t] + (int)c16[k];
+        }
+    }
+    if (V.v32 && !(sel & XFK_AMG_F64_VALS)) {
+        std::vector<float> f;
+        if ((rc = fetch(s, f, V.v32, nz)) != XFK_OK) return rc;
+        v.assign(f.begin(), f.end());
+    } else if ((rc = fetch(s, v, V.v, nz)) != XFK_OK) {
+        return rc;
+    }
+    std::copy(rp.begin(), rp.end(), rowptr);
+    std::copy(cl.begin(), cl.end(), col);
+    std::copy(v.begin(), v.end(), val);
+    return XFK_OK;
+}
+
+int amg_probe_tiles(Amg &M, hipStream_t s, int sel, int *tiles, int *wide)
+{
+    ProbeView V;
+    int rc = probe_view(M, 0, sel, V);
+    if (rc != XFK_OK) return rc;
+    *tiles = *wide = 0;
+    if (!V.c16) return XFK_OK;
+    std::vector<int> cb;
+    const int nt = (V.rows + V.B - 1) / V.B;
+    if ((rc = fetch(s, cb, V.cb, (size_t)nt)) != XFK_OK) return rc;
+    *tiles = nt;
+    for (int t = 0; t < nt; ++t) *wide += cb[t] == kNoColBase;
+    return XFK_OK;
+}
+
+int amg_probe_vector(Amg &M, hipStream_t s, int level, int what, double *out)
+{
+    XFK_REQUIRE(!M.dist && level >= 0 && level < M.nlev, XFK_ERR_ARG, "AMG probe: no such level");
+    const AmgLevel &A = *M.L[level];
+    std::vector<double> v;
+    int rc;
+    if (what == XFK_AMG_DINV) {
+        if ((rc = fetch(s, v, (const double *)A.dinv.p, (size_t)A.n)) != XFK_OK) return rc;
+        std::copy(v.begin(), v.end(), out);
+        return XFK_OK;
+    }
+    XFK_REQUIRE(what == XFK_AMG_DENSE && level == M.nlev - 1 && M.dense_coarse, XFK_ERR_ARG,
+                "AMG probe: not the dense coarsest level");
+    const size_t ld = (size_t)M.cinv_ld, n = (size_t)A.n;
+    std::vector<double> sc;
+    if ((rc = fetch(s, sc, (const double *)M.cinv_sc.p, ld)) != XFK_OK) return rc;
+    if (M.cinv_f64) {
+        if ((rc = fetch(s, v, (const double *)M.cinv_o64.p, ld * ld)) != XFK_OK) return rc;
+    } else {
+        std::vector<float> f;
+        if ((rc = fetch(s, f, M.cinv_apply, ld * ld)) != XFK_OK) return rc;
+        v.assign(f.begin(), f.end());
+    }
+    // k_dense_mv on a unit vector: x_i = S_i (M_ij (S_j 1))
+    for (size_t i = 0; i < n; ++i)
+        for (size_t j = 0; j < n; ++j) out[i * n + j] = sc[i] * (v[i * ld + j] * sc[j]);
+    return XFK_OK;
+}
+
+int amg_probe_trace(Amg &M, int level, int what, void *out)
+{
+    XFK_REQUIRE(M.trace && level >= 0 && level < (int)M.trace->lev.size(), XFK_ERR_ARG,
+                "AMG probe: the level was not traced");
+    const AmgTrace::Level &T = M.trace->lev[level];
+    auto put = [&](const auto &v) {
+        if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(v[0]));
+        return XFK_OK;
+    };
+    XFK_REQUIRE(T.joined || what == XFK_AMG_TR_SFLAG || what == XFK_AMG_TR_SDEG || what >= XFK_AMG_TR_DFINV,
+                XFK_ERR_ARG, "AMG probe: the level was not coarsened");
+    switch (what) {
+    case XFK_AMG_TR_SFLAG: return put(T.sflag);
+    case XFK_AMG_TR_SDEG: return put(T.sdeg);
+    case XFK_AMG_TR_AGG: return put(T.agg);
+    case XFK_AMG_TR_AGG_PRE: return put(T.agg_pre);
+    case XFK_AMG_TR_ROOT: return put(T.root);
+    case XFK_AMG_TR_DFINV: return put(T.dfinv);
+    case XFK_AMG_TR_WF: return put(T.wF);
+    default: set_error("AMG probe: unknown trace array"); return XFK_ERR_ARG;
+    }
 }
 
 }  // namespace xfk

@@ -2996,11 +2996,15 @@ int xfk_set_option(xfk_problem *P, int option, double value)
     }
 }
 
-int xfk_pcg_solve_csr_pc(int n, const int *rowptr, const int *col, const double *val, const double *b, double *V,
-                         int flag, double precision, int device, int precond, long long *iters, double *er)
+// A problem that holds only a host CSR (full symmetric, a diagonal in every
+// row) on `device`: its stream, the matrix and the diagonal positions.
+// *out is set even on failure (the caller destroys it).  `diag` is the
+// caller's: the copy of it is only queued here, so it has to outlive the
+// caller's next synchronisation of the stream (no synchronisation here).
+static int csr_problem_upload(int n, const int *rowptr, const int *col, const double *val, int device,
+                              std::vector<int> &diag, xfk_problem **out)
 {
-    XFK_REQUIRE(precond == XFK_PRECOND_JACOBI || precond == XFK_PRECOND_AMG, XFK_ERR_ARG, "unknown preconditioner");
-    XFK_REQUIRE(n > 0 && rowptr && col && val && b && V, XFK_ERR_ARG, "null argument");
+    *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device available (the fsolver hot path has no CPU fallback)");
@@ -3008,18 +3012,17 @@ int xfk_pcg_solve_csr_pc(int n, const int *rowptr, const int *col, const double 
     }
     XFK_CHECK(hipSetDevice(device));
     xfk_problem *P = new xfk_problem();
+    *out = P;
     P->device = device;
     P->N = n;
     P->NL = n;
     P->nnz = rowptr[n];
     P->nnz_own = P->nnz;
     P->NR = n;
-    P->precision = precision;
-    P->precond = precond;
     int rc = XFK_OK;
     hipError_t e = stream_acquire(&P->stream);
     // diagonal positions
-    std::vector<int> diag(n, -1);
+    diag.assign(n, -1);
     for (int i = 0; i < n; ++i)
         for (int k = rowptr[i]; k < rowptr[i + 1]; ++k)
             if (col[k] == i) diag[i] = k;
@@ -3032,20 +3035,42 @@ int xfk_pcg_solve_csr_pc(int n, const int *rowptr, const int *col, const double 
     if (e == hipSuccess) e = upload(P->rowptr, rowptr, (size_t)n + 1, s);
     if (e == hipSuccess) e = upload(P->col, col, (size_t)P->nnz, s);
     if (e == hipSuccess) e = upload(P->val, val, (size_t)P->nnz, s);
-    if (e == hipSuccess) e = upload(P->b, b, (size_t)n, s);
-    if (e == hipSuccess) e = upload(P->V, V, (size_t)n, s);
     if (e == hipSuccess) e = upload(P->diag, diag.data(), (size_t)n, s);
-    for (DBuf<double> *v : {&P->P, &P->dinv})
-        if (e == hipSuccess) e = v->alloc(n);
-    if (e == hipSuccess) e = P->partials.alloc(2 * kRedGrid);
-    if (e == hipSuccess) e = P->counters.alloc(8);
-    if (e == hipSuccess) e = hipMemsetAsync(P->counters.p, 0, sizeof(unsigned) * 8, s);
-    if (e == hipSuccess) e = P->pcg.alloc(1);
-    if (e == hipSuccess) e = pinned_malloc((void **)&P->pcg_host, sizeof(CgState));
-    if (e == hipSuccess) e = pinned_malloc((void **)&P->hpin, 16 * sizeof(int));
     if (e != hipSuccess) {
         set_error(std::string("pcg setup failed: ") + hipGetErrorString(e));
         rc = XFK_ERR_HIP;
+    }
+    return rc;
+}
+
+int xfk_pcg_solve_csr_pc(int n, const int *rowptr, const int *col, const double *val, const double *b, double *V,
+                         int flag, double precision, int device, int precond, long long *iters, double *er)
+{
+    XFK_REQUIRE(precond == XFK_PRECOND_JACOBI || precond == XFK_PRECOND_AMG, XFK_ERR_ARG, "unknown preconditioner");
+    XFK_REQUIRE(n > 0 && rowptr && col && val && b && V, XFK_ERR_ARG, "null argument");
+    xfk_problem *P = nullptr;
+    std::vector<int> diag;   // (alive until the solve below has synchronised)
+    int rc = csr_problem_upload(n, rowptr, col, val, device, diag, &P);
+    if (!P) return rc;
+    P->precision = precision;
+    P->precond = precond;
+    hipStream_t s = P->stream;
+    hipError_t e = hipSuccess;
+    if (rc == XFK_OK) {
+        e = upload(P->b, b, (size_t)n, s);
+        if (e == hipSuccess) e = upload(P->V, V, (size_t)n, s);
+        for (DBuf<double> *v : {&P->P, &P->dinv})
+            if (e == hipSuccess) e = v->alloc(n);
+        if (e == hipSuccess) e = P->partials.alloc(2 * kRedGrid);
+        if (e == hipSuccess) e = P->counters.alloc(8);
+        if (e == hipSuccess) e = hipMemsetAsync(P->counters.p, 0, sizeof(unsigned) * 8, s);
+        if (e == hipSuccess) e = P->pcg.alloc(1);
+        if (e == hipSuccess) e = pinned_malloc((void **)&P->pcg_host, sizeof(CgState));
+        if (e == hipSuccess) e = pinned_malloc((void **)&P->hpin, 16 * sizeof(int));
+        if (e != hipSuccess) {
+            set_error(std::string("pcg setup failed: ") + hipGetErrorString(e));
+            rc = XFK_ERR_HIP;
+        }
     }
     if (rc == XFK_OK) rc = pcg_solve(P, flag, std::max<long long>(100000, 20LL * n));
     if (rc == XFK_OK || rc == XFK_ERR_NOCONV) {
@@ -3054,6 +3079,143 @@ int xfk_pcg_solve_csr_pc(int n, const int *rowptr, const int *col, const double 
         if (er) *er = P->pcg_host->er;
     }
     xfk_problem_destroy(P);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// diagnostics of the AMG hierarchy (tests): see include/xfemm_kernels.h
+// ---------------------------------------------------------------------------
+
+struct xfk_amg_probe {
+    xfk_problem *P = nullptr;
+    DBuf<double> in, out;   // apply: the uploaded and the computed vectors
+};
+
+void xfk_amg_probe_destroy(xfk_amg_probe *H)
+{
+    if (!H) return;
+    if (H->P) {
+        (void)hipSetDevice(H->P->device);
+        (void)hipStreamSynchronize(H->P->stream);
+        H->in.free();
+        H->out.free();
+        xfk_problem_destroy(H->P);
+    }
+    delete H;
+}
+
+int xfk_amg_probe_create(int n, const int *rowptr, const int *col, const double *val, int device,
+                         const xfk_amg_probe_opts *o, int trace, xfk_amg_probe **out)
+{
+    XFK_REQUIRE(n > 0 && rowptr && col && val && o && out, XFK_ERR_ARG, "null argument");
+    XFK_REQUIRE(o->sweeps >= 1 && o->sweeps <= 8 && o->theta >= 0.0 && o->theta < 1.0 && o->omega > 0.0 &&
+                    o->omega < 2.0 && o->dense_max >= 16 && o->dense_max <= kAmgDenseMax && o->wlevel >= -2 &&
+                    o->wlevel < kAmgMaxLevels,
+                XFK_ERR_ARG, "AMG probe: option out of range (xfk_set_option's ranges)");
+    *out = nullptr;
+    xfk_amg_probe *H = new xfk_amg_probe();
+    std::vector<int> diag;   // (alive until the setup below has synchronised)
+    int rc = csr_problem_upload(n, rowptr, col, val, device, diag, &H->P);
+    if (rc == XFK_OK) {
+        xfk_problem *P = H->P;
+        P->precond = XFK_PRECOND_AMG;
+        Amg *M = P->amg = new Amg();
+        M->theta = o->theta;
+        M->sweeps = o->sweeps;
+        M->omega = o->omega;
+        M->dense_max = o->dense_max;
+        M->fold_on = o->fold;
+        M->col16 = o->col16;
+        M->prec32 = o->f32;
+        M->wlevel = o->wlevel;
+        if (trace) M->trace = new AmgTrace();
+        rc = M->setup(P->stream, P->N, P->N, P->rowptr.p, P->col.p, P->val.p, P->nnz_own);
+        if (rc == XFK_OK && hipStreamSynchronize(P->stream) != hipSuccess) {
+            set_error("AMG probe: the setup failed on the device");
+            rc = XFK_ERR_HIP;
+        }
+    }
+    if (rc != XFK_OK) {
+        xfk_amg_probe_destroy(H);
+        return rc;
+    }
+    *out = H;
+    return XFK_OK;
+}
+
+#define PROBE_ENTER(H)                                                                        \
+    XFK_REQUIRE((H) && (H)->P && (H)->P->amg, XFK_ERR_ARG, "null AMG probe");                 \
+    XFK_CHECK(hipSetDevice((H)->P->device))
+
+int xfk_amg_probe_info(xfk_amg_probe *H, xfk_amg_info *info)
+{
+    PROBE_ENTER(H);
+    XFK_REQUIRE(info, XFK_ERR_ARG, "null argument");
+    return amg_probe_info(*H->P->amg, H->P->stream, info);
+}
+
+int xfk_amg_probe_level_size(xfk_amg_probe *H, int level, int sel, int *rows, int *cols, long long *nnz)
+{
+    PROBE_ENTER(H);
+    XFK_REQUIRE(rows && cols && nnz, XFK_ERR_ARG, "null argument");
+    return amg_probe_level_size(*H->P->amg, H->P->stream, level, sel, rows, cols, nnz);
+}
+
+int xfk_amg_probe_level_csr(xfk_amg_probe *H, int level, int sel, int *rowptr, int *col, double *val)
+{
+    PROBE_ENTER(H);
+    XFK_REQUIRE(rowptr && col && val, XFK_ERR_ARG, "null argument");
+    return amg_probe_level_csr(*H->P->amg, H->P->stream, level, sel, rowptr, col, val);
+}
+
+int xfk_amg_probe_tiles(xfk_amg_probe *H, int sel, int *tiles, int *wide)
+{
+    PROBE_ENTER(H);
+    XFK_REQUIRE(tiles && wide, XFK_ERR_ARG, "null argument");
+    return amg_probe_tiles(*H->P->amg, H->P->stream, sel, tiles, wide);
+}
+
+int xfk_amg_probe_vector(xfk_amg_probe *H, int level, int what, double *out)
+{
+    PROBE_ENTER(H);
+    XFK_REQUIRE(out, XFK_ERR_ARG, "null argument");
+    return amg_probe_vector(*H->P->amg, H->P->stream, level, what, out);
+}
+
+int xfk_amg_probe_trace(xfk_amg_probe *H, int level, int what, void *out)
+{
+    PROBE_ENTER(H);
+    XFK_REQUIRE(out, XFK_ERR_ARG, "null argument");
+    return amg_probe_trace(*H->P->amg, level, what, out);
+}
+
+int xfk_amg_probe_apply(xfk_amg_probe *H, int nvec, const double *R, double *U)
+{
+    PROBE_ENTER(H);
+    XFK_REQUIRE(nvec > 0 && R && U, XFK_ERR_ARG, "null argument");
+    xfk_problem *P = H->P;
+    hipStream_t s = P->stream;
+    const size_t n = (size_t)P->N, tot = n * (size_t)nvec;
+    XFK_CHECK(upload(H->in, R, tot, s));
+    XFK_CHECK(H->out.alloc(tot));
+    for (int k = 0; k < nvec; ++k) {
+        const int rc = P->amg->vcycle(s, H->in.p + k * n, H->out.p + k * n, nullptr);
+        if (rc != XFK_OK) return rc;
+    }
+    XFK_CHECK(hipGetLastError());
+    XFK_CHECK(d2h(U, H->out.p, sizeof(double) * tot, s));
+    return XFK_OK;
+}
+
+int xfk_amg_probe_refresh(xfk_amg_probe *H, const double *val, int fold)
+{
+    PROBE_ENTER(H);
+    XFK_REQUIRE(val, XFK_ERR_ARG, "null argument");
+    xfk_problem *P = H->P;
+    // (in place: the hierarchy's level 0 points at the problem's arrays)
+    XFK_CHECK(hipMemcpyAsync(P->val.p, val, sizeof(double) * (size_t)P->nnz, hipMemcpyHostToDevice, P->stream));
+    const int rc = P->amg->refresh(P->stream, fold != 0);
+    XFK_CHECK(hipStreamSynchronize(P->stream));
     return rc;
 }
 

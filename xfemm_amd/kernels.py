@@ -61,6 +61,9 @@ EXPORTED = (
     "xfk_heatflow_advance", "xfk_hf_get_conductors", "xfk_hf_conductor_flow",
     "xfk_pot_set_solution", "xfk_pot_element_fields", "xfk_pot_corner_fields", "xfk_pot_corner_branches",
     "xfk_pot_block_integrals", "xfk_pot_block_integral", "xfk_pot_point_values", "xfk_pot_grid_info", "xfk_pot_time",
+    "xfk_amg_probe_create", "xfk_amg_probe_info", "xfk_amg_probe_level_size", "xfk_amg_probe_level_csr",
+    "xfk_amg_probe_tiles", "xfk_amg_probe_vector", "xfk_amg_probe_trace", "xfk_amg_probe_apply",
+    "xfk_amg_probe_refresh", "xfk_amg_probe_destroy",
 )
 
 
@@ -209,6 +212,22 @@ class DistInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AmgProbeOpts(C.Structure):
+    _fields_ = [("sweeps", C.c_int), ("theta", C.c_double), ("omega", C.c_double), ("dense_max", C.c_int),
+                ("fold", C.c_int), ("col16", C.c_int), ("f32", C.c_int), ("wlevel", C.c_int)]
+
+
+class AmgLevelInfo(C.Structure):
+    _fields_ = [("n", C.c_int), ("nc", C.c_int), ("fold", C.c_int), ("has16", C.c_int), ("has32", C.c_int),
+                ("w_at", C.c_int), ("nnz", C.c_longlong), ("pnnz", C.c_longlong), ("fnnz", C.c_longlong),
+                ("weight", C.c_double), ("rho_f", C.c_double)]
+
+
+class AmgInfo(C.Structure):
+    _fields_ = [("levels", C.c_int), ("dense_coarse", C.c_int), ("cinv_f64", C.c_int), ("traced", C.c_int),
+                ("level", AmgLevelInfo * 16)]
+
+
 _lib = None
 
 
@@ -242,6 +261,18 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_pcg_solve_csr_pc.argtypes = [C.c_int, iptr, iptr, dptr, dptr, dptr, C.c_int, C.c_double, C.c_int,
                                        C.c_int, C.POINTER(C.c_longlong), dptr]
     L.xfk_pcg_time.argtypes = [C.c_void_p, C.c_int, dptr, dptr]
+    L.xfk_amg_probe_create.argtypes = [C.c_int, iptr, iptr, dptr, C.c_int, C.POINTER(AmgProbeOpts), C.c_int,
+                                       C.POINTER(C.c_void_p)]
+    L.xfk_amg_probe_info.argtypes = [C.c_void_p, C.POINTER(AmgInfo)]
+    L.xfk_amg_probe_level_size.argtypes = [C.c_void_p, C.c_int, C.c_int, iptr, iptr, C.POINTER(C.c_longlong)]
+    L.xfk_amg_probe_level_csr.argtypes = [C.c_void_p, C.c_int, C.c_int, iptr, iptr, dptr]
+    L.xfk_amg_probe_tiles.argtypes = [C.c_void_p, C.c_int, iptr, iptr]
+    L.xfk_amg_probe_vector.argtypes = [C.c_void_p, C.c_int, C.c_int, dptr]
+    L.xfk_amg_probe_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.xfk_amg_probe_apply.argtypes = [C.c_void_p, C.c_int, dptr, dptr]
+    L.xfk_amg_probe_refresh.argtypes = [C.c_void_p, dptr, C.c_int]
+    L.xfk_amg_probe_destroy.argtypes = [C.c_void_p]
+    L.xfk_amg_probe_destroy.restype = None
     L.xfk_phase_profile.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.xfk_alloc_stats.argtypes = [dptr, C.c_int]
     L.xfk_problem_memory.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
@@ -1158,6 +1189,100 @@ def pcg_solve_csr(rowptr, col, val, b, V0=None, flag=0, precision=1e-8, device=0
                                   bb.ctypes.data_as(dptr), V.ctypes.data_as(dptr), flag, precision, device,
                                   PRECONDS[precond], C.byref(it), C.byref(er)))
     return V, it.value, er.value
+
+
+class AmgProbe:
+    """Diagnostics of one AMG hierarchy built from a host CSR (xfk_amg_probe_*):
+    the operators of every level as the cycle reads them, the setup's traced
+    scratch, the cycle applied to given vectors and a values-only refresh.
+    For tests; not an interface to build on."""
+
+    A, P, R, PF, RF = 0, 1, 2, 3, 4
+    PLAIN_COLS, F64_VALS = 16, 32
+    _TRACE = {"sflag": (0, np.uint8), "sdeg": (1, np.int32), "agg": (2, np.int32), "agg_pre": (3, np.int32),
+              "root": (4, np.int32), "dfinv": (5, np.float64), "wF": (6, np.float64)}
+
+    def __init__(self, rowptr, col, val, device=0, sweeps=1, theta=0.08, omega=1.75, dense_max=2048, fold=1,
+                 col16=1, f32=1, wlevel=-1, trace=False):
+        L = load_library()
+        self.n = len(rowptr) - 1
+        rp = np.ascontiguousarray(rowptr, np.int32)
+        cl = np.ascontiguousarray(col, np.int32)
+        vl = np.ascontiguousarray(val, np.float64)
+        self.nnz = int(rp[-1])
+        o = AmgProbeOpts(sweeps, theta, omega, dense_max, int(fold), int(col16), int(f32), wlevel)
+        h = C.c_void_p()
+        self._h = None
+        _check(L.xfk_amg_probe_create(self.n, rp.ctypes.data_as(iptr), cl.ctypes.data_as(iptr),
+                                      vl.ctypes.data_as(dptr), device, C.byref(o), int(trace), C.byref(h)))
+        self._h = h
+
+    def info(self):
+        I = AmgInfo()
+        _check(_lib.xfk_amg_probe_info(self._h, C.byref(I)))
+        lv = [{k: getattr(I.level[l], k) for k, _ in AmgLevelInfo._fields_} for l in range(I.levels)]
+        return {"levels": I.levels, "dense_coarse": bool(I.dense_coarse), "cinv_f64": bool(I.cinv_f64),
+                "level": lv}
+
+    def csr(self, level, sel):
+        """(shape, rowptr, col, val) of one operator of a level."""
+        r, c, z = C.c_int(), C.c_int(), C.c_longlong()
+        _check(_lib.xfk_amg_probe_level_size(self._h, level, sel, C.byref(r), C.byref(c), C.byref(z)))
+        rp = np.zeros(r.value + 1, np.int32)
+        cl = np.zeros(max(1, z.value), np.int32)
+        vl = np.zeros(max(1, z.value))
+        _check(_lib.xfk_amg_probe_level_csr(self._h, level, sel, rp.ctypes.data_as(iptr), cl.ctypes.data_as(iptr),
+                                            vl.ctypes.data_as(dptr)))
+        return (r.value, c.value), rp, cl[:z.value], vl[:z.value]
+
+    def tiles(self, sel):
+        t, w = C.c_int(), C.c_int()
+        _check(_lib.xfk_amg_probe_tiles(self._h, sel, C.byref(t), C.byref(w)))
+        return t.value, w.value
+
+    def dinv(self, level):
+        out = np.zeros(self.info()["level"][level]["n"])
+        _check(_lib.xfk_amg_probe_vector(self._h, level, 0, out.ctypes.data_as(dptr)))
+        return out
+
+    def dense(self):
+        """The n x n operator the dense coarsest level applies."""
+        I = self.info()
+        n = I["level"][-1]["n"]
+        out = np.zeros((n, n))
+        _check(_lib.xfk_amg_probe_vector(self._h, I["levels"] - 1, 1, out.ctypes.data_as(dptr)))
+        return out
+
+    def trace(self, level, name):
+        what, dt = self._TRACE[name]
+        lv = self.info()["level"][level]
+        out = np.zeros(max(1, lv["nnz"] if name == "sflag" else lv["n"]), dt)
+        _check(_lib.xfk_amg_probe_trace(self._h, level, what, out.ctypes.data_as(C.c_void_p)))
+        return out[:lv["nnz"] if name == "sflag" else lv["n"]]
+
+    def apply(self, R):
+        """U[:, k] = V-cycle(R[:, k])."""
+        R = np.asarray(R, np.float64)
+        Rt = np.ascontiguousarray(R.reshape(self.n, -1).T)
+        U = np.zeros_like(Rt)
+        _check(_lib.xfk_amg_probe_apply(self._h, Rt.shape[0], Rt.ctypes.data_as(dptr), U.ctypes.data_as(dptr)))
+        return np.ascontiguousarray(U.T).reshape(R.shape)
+
+    def refresh(self, val, fold=True):
+        vl = np.ascontiguousarray(val, np.float64)
+        assert vl.size == self.nnz
+        _check(_lib.xfk_amg_probe_refresh(self._h, vl.ctypes.data_as(dptr), int(fold)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().xfk_amg_probe_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class CommOp(C.Structure):
