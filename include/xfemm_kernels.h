@@ -190,17 +190,17 @@ enum {
                                    2x the iterations of the last fresh build; 0: rebuild every time */
     XFK_OPT_AMG_DENSE = 7,      /* coarsening stops at a level of at most this many rows, which is
                                    solved by its dense inverse (16..2048, default 2048) */
-    XFK_OPT_AMG_FOLD = 8,       /* 1 (default, or XFK_AMG_FOLD from the environment): V(1,1) levels
+    XFK_OPT_AMG_FOLD = 8,       /* 1 (default): V(1,1) levels
                                    run folded (one pass over P~ = (I - w D^-1 A) P for prolongation +
                                    post-sweep, coarse pre-steps with R~ = P~^T); 0: the plain cycle */
-    XFK_OPT_AMG_COL16 = 9,      /* 1 (default, unless XFK_NO_COL16 is set): single-device level-0
+    XFK_OPT_AMG_COL16 = 9,      /* 1 (default): single-device level-0
                                    operators (the PCG SpMV, the sweeps, P~, R) read 16-bit column
                                    offsets per row tile (tiles spanning > 65535 columns read the int
                                    columns); 0: int columns.  The same column indices: the same bits. */
     XFK_OPT_AMG_WLEVEL = 10,    /* the folded coarse level that runs a W-cycle (two coarse
                                    corrections); -2 (default): the level above the last V-cycle
-                                   level (XFK_AMG_W overrides), -1: a plain V-cycle */
-    XFK_OPT_AMG_F32 = 11,       /* 1 (default, unless XFK_AMG_F32=0 is set; needs 16-bit columns):
+                                   level, -1: a plain V-cycle */
+    XFK_OPT_AMG_F32 = 11,       /* 1 (default; needs 16-bit columns):
                                    the V-cycle's level-0 transfers (R, P~) store f32 values,
                                    products and sums in f64; 0: f64 values.  The sweeps and the
                                    PCG's own SpMV keep A in f64. */
@@ -726,9 +726,7 @@ int xfk_pot_time(xfk_problem *prob, int n, const double *x, const double *y, int
  * reads it -- sel XFK_AMG_A / _P / _R / _PF (P~) / _RF (R~); level 0 with
  * 16-bit tile columns returns the decoded columns unless XFK_AMG_PLAIN_COLS
  * is or'ed in, with f32 transfers R and P~ return the widened f32 values
- * unless XFK_AMG_F64_VALS is or'ed in.  (Not covered: with the lab switch
- * XFK_AMG_F32_SWEEP=1 the level-0 sweeps read an f32 copy of A; XFK_AMG_A
- * returns the f64 values.)
+ * unless XFK_AMG_F64_VALS is or'ed in.
  * xfk_amg_probe_tiles: tiles and int-fallback tiles of level 0's 16-bit form.
  * xfk_amg_probe_vector: XFK_AMG_DINV (n doubles), or XFK_AMG_DENSE, the n x n
  * operator the coarsest level applies, S M S as k_dense_mv composes it.

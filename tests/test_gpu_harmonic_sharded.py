@@ -140,7 +140,7 @@ def test_sharded_newton_ac_matches_oracle(nranks, kind, n):
 
     Not periodic 16: there the path decides the answer.  The first Newton
     pass starts from the same V and the same matrices (auxiliary, M, b equal
-    to 1e-9 on 2 ranks: tools/lab/aux_dump_cmp.py), but the row-block AMG is
+    to 1e-9 on 2 ranks, compared entry by entry from a temporary dump), but the row-block AMG is
     another preconditioner, so the inner COCG stops at lprec after other
     iterations (4 vs 1); on 2 ranks pass 10 then finds KludgeSolve's start
     residual below lprec, takes no step, and the loop stops on a zero change

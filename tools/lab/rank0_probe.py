@@ -1,7 +1,7 @@
 """Lab: configs[4] rank r of R, compute only (bench.configs4_rank0_of_8 with
 knobs), under environment variants given as NAME=VALUE[,NAME=VALUE] args.
 Each variant runs in a child process (the library reads its switches once).
-Usage: python tools/lab/rank0_probe.py [--cells 3162] [--ranks 8] '' XFK_NO_OVERLAP=1 ..."""
+Usage: python tools/lab/rank0_probe.py [--cells 3162] [--ranks 8] '' XFK_OVERLAP=1 ..."""
 import argparse
 import json
 import os

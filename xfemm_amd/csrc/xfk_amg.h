@@ -82,11 +82,11 @@ struct AmgLevel {
     DBuf<unsigned short> a16, f16, r16, p16;
     DBuf<int> a16b, f16b, r16b, p16b;
     // level 0 (with has16): the V-cycle's transfers R and P~ with f32 values
-    // (products and sums in f64; A keeps f64 -- a32 only with XFK_AMG_F32_SWEEP=1);
+    // (products and sums in f64; A keeps f64);
     // a sharded level 0 (unfolded) keeps R and P in f32, P with 16-bit
     // columns in 256-row tiles (p16)
     bool has32 = false;
-    DBuf<float> a32, r32, f32v, p32;
+    DBuf<float> r32, f32v, p32;
     // stored bytes per nonzero of the level's V-cycle transfers (column + value)
     double nz_bytes() const { return (has16 ? 2.0 : 4.0) + (has32 ? 4.0 : 8.0); }
 };
@@ -119,10 +119,10 @@ struct Amg {
     AmgTrace *trace = nullptr;
     // parameters
     double theta = 0.08;              // strength threshold
-    double theta_coarse = -1.0;       // levels >= 1 (< 0: theta; XFK_AMG_THETA_COARSE overrides)
+    double theta_coarse = -1.0;       // levels >= 1 (< 0: theta)
     double theta_at(int l) const;
     int sweeps = 1;                   // Jacobi sweeps before and after the coarse correction
-    int wlevel = -2;                  // W-cycle (two coarse corrections) at this folded level (-1: none; -2: XFK_AMG_W)
+    int wlevel = -2;                  // W-cycle (two coarse corrections) at this folded level (-1: none; -2: the default level)
     int wcycle_level() const;
     bool w_at(int l) const;
     double omega = 1.75;              // Jacobi weight = omega / rho_A (rho_A: Gershgorin bound of D^-1 A);
@@ -199,9 +199,9 @@ struct Amg {
     bool dist = false;
     int rep_rows = 250000;
     int dense_max = kAmgDenseMax;     // coarsest level: dense inverse at <= dense_max rows
-    int fold_on = -1;                 // folded V(1,1) levels: 1 / 0, -1 = the XFK_AMG_FOLD default
-    int col16 = -1;                   // 16-bit tile columns on level 0: 1 / 0, -1 = on unless XFK_NO_COL16
-    int prec32 = -1;                  // f32 values of level 0's V-cycle operators: 1 / 0, -1 = on unless XFK_AMG_F32=0
+    int fold_on = 1;                  // folded V(1,1) levels: 1 / 0
+    int col16 = 1;                    // 16-bit tile columns on level 0: 1 / 0
+    int prec32 = 1;                   // f32 values of level 0's V-cycle operators: 1 / 0
     int lrep = 0;
     xfk_comm *comm = nullptr;
     int nranks = 1, rank = 0;
@@ -221,6 +221,7 @@ struct Amg {
     int host_big_n = 0;
     double *part_gam_ = nullptr;      // vcycle's gamma partials, for vc_dist
     SideStream side;                  // sharded: halo exchanges overlapped with interior tiles
+    bool overlap = false;             // ... when XFK_OVERLAP=1 (read per setup_dist)
     // sharded, XFK_TIME_TAIL: event pairs around the replicated tail -- per
     // V-cycle the all-gather of the coarse right-hand side and the replicated
     // cycle (kind 0), in the setup the build of the replicated levels (kind 1)

@@ -193,7 +193,7 @@ __global__ void __launch_bounds__(kB) k_amg_strength(int n, int ncl, double thet
                                                      const double *__restrict__ dinv,
                                                      unsigned char *__restrict__ sflag, int *__restrict__ sdeg,
                                                      double *__restrict__ dfinv, double *__restrict__ wF,
-                                                     double *__restrict__ rho_part, bool sgnd)
+                                                     double *__restrict__ rho_part)
 {
     __shared__ double red[2 * (kB / 64)];
     const int i = (blockIdx.x * blockDim.x + threadIdx.x) / kStrG;
@@ -213,7 +213,6 @@ __global__ void __launch_bounds__(kB) k_amg_strength(int n, int ncl, double thet
         // The test follows the diagonal's sign: the static operators are SPD,
         // the harmonic surrogate (Re A + s Im A of FEMM's sign convention) is
         // negative definite -- the diagonal negative, the couplings positive.
-        // (sgnd == 0: |a_ij|, the former test, XFK_AMG_ABS_STRENGTH=1)
         const double sg = dinv[i] < 0.0 ? -1.0 : 1.0;
         const int s = rowptr[i] + g, e = rowptr[i + 1];
         // a chunk of this lane's entries at a time: columns and values, then
@@ -249,10 +248,10 @@ __global__ void __launch_bounds__(kB) k_amg_strength(int n, int ncl, double thet
                 // peer's diagonal is not known here)
                 sumA += fabs(a);
                 lump += a;
-                hdeg += ((sgnd ? -sg * a : fabs(a)) > theta * ai);
+                hdeg += (-sg * a > theta * ai);
             } else {
                 sumA += fabs(a);
-                if (a != 0.0 && (sgnd ? -sg * a : fabs(a)) > theta * sqrt(ai * dj[q])) {
+                if (a != 0.0 && -sg * a > theta * sqrt(ai * dj[q])) {
                     f = 1;
                     ++deg;
                     sumS += fabs(a);
@@ -369,11 +368,11 @@ template <int G>
 __global__ void k_mis_max(int n, const int *__restrict__ rowptr, ColView cv,
                           const unsigned char *__restrict__ sflag, const MisKey *__restrict__ in,
                           MisKey *__restrict__ out, const int *prev, int *cur, int *run,
-                          unsigned char *__restrict__ act, int xcd)
+                          unsigned char *__restrict__ act)
 {
-    // xcd: consecutive blocks on one XCD (xcd_tile): a block's neighbour rows
+    // consecutive blocks on one XCD (xcd_tile): a block's neighbour rows
     // a mesh row away stay in that XCD's L2
-    const int bx = xcd ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int bx = xcd_tile(blockIdx.x, gridDim.x);
     const int t = bx * blockDim.x + threadIdx.x;
     const int i = t / G, g = t % G;
     if (blockIdx.x == 0 && threadIdx.x == 0) {   // k_mis_update of this round runs after this launch
@@ -409,10 +408,9 @@ __global__ void k_mis_max(int n, const int *__restrict__ rowptr, ColView cv,
 template <int G, bool ROOTS = false>
 __global__ void k_mis_update(int n, const int *__restrict__ rowptr, ColView cv,
                              const unsigned char *__restrict__ sflag, const MisKey *__restrict__ t1,
-                             MisKey *__restrict__ key, const int *prev, int *undecided, int *__restrict__ flag,
-                             int xcd)
+                             MisKey *__restrict__ key, const int *prev, int *undecided, int *__restrict__ flag)
 {
-    const int bx = xcd ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int bx = xcd_tile(blockIdx.x, gridDim.x);
     const int t = bx * blockDim.x + threadIdx.x;
     const int i = t / G, g = t % G;
     if (i >= n) return;
@@ -593,8 +591,7 @@ __global__ void __launch_bounds__(kB) k_agg_join2(int n, const int *__restrict__
 // lanes per row of the aggregation joins for rows of this average length
 static int join_lanes(double per_row)
 {
-    const char *e = std::getenv("XFK_JOIN_LANES");   // (read per level: tests toggle it)
-    const int v = e ? std::atoi(e) : 0;
+    const int v = (int)env_int("XFK_JOIN_LANES", 0);   // (read per level: tests toggle it)
     if (v == 1 || v == 4 || v == 8) return v;
     return per_row <= 8.0 ? 1 : (per_row <= 16.0 ? 4 : 8);
 }
@@ -603,30 +600,10 @@ static int join_lanes(double per_row)
 // setup: R = P^T
 // --------------------------------------------------------------------------
 
-__global__ void k_rt_count(int n, const int *__restrict__ prow, const int *__restrict__ pcol, int *__restrict__ rcnt)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int k = prow[i]; k < prow[i + 1]; ++k) atomicAdd(&rcnt[pcol[k]], 1);
-}
-
-// the counts left by k_rt_count count down to each row's free slot (no
-// zeroed cursor array needed)
-__global__ void k_rt_fill(int n, const int *__restrict__ prow, const int *__restrict__ pcol,
-                          const int *__restrict__ rrow, int *__restrict__ cnt, int *__restrict__ rcol)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int k = prow[i]; k < prow[i + 1]; ++k) {
-        const int J = pcol[k];
-        rcol[rrow[J] + atomicSub(&cnt[J], 1) - 1] = i;
-    }
-}
-
-// Tiled transpose (XFK_RT_TILE, default on): a workgroup of 256 rows holds
-// its entries' columns in a window [lo, hi] (a banded numbering: a few
-// hundred columns), counts them in LDS and touches
-// the global counts once per (workgroup, column) instead of once per entry.
+// Tiled transpose: a workgroup of 256 rows holds its entries' columns in a
+// window [lo, hi] (a banded numbering: a few hundred columns), counts them in
+// LDS and touches the global counts once per (workgroup, column) instead of
+// once per entry.
 // The fill reserves one chunk of each target row per workgroup (returning
 // atomic on the count-down counter), places its entries there through LDS
 // cursors and writes the values with the columns; the row sort restores the
@@ -786,71 +763,6 @@ __global__ void __launch_bounds__(256) k_rt_sort_pairs(int nc, const int *__rest
                 rval[q + 1] = kv;
             }
         }
-    }
-}
-
-// sort each R row (the atomic fill order is arbitrary), then look the values
-// up in P.  One wavefront per row: rows of <= 64 entries are sorted by a
-// register bitonic network, longer ones by lane 0 (insertion sort).
-__global__ void __launch_bounds__(256) k_rt_sort_vals(int nc, const int *__restrict__ rrow, int *__restrict__ rcol,
-                                                      const int *__restrict__ prow, const int *__restrict__ pcol,
-                                                      const double *__restrict__ pval, double *__restrict__ rval)
-{
-    const int J = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (J >= nc) return;
-    const int s = rrow[J], e = rrow[J + 1], len = e - s;
-    if (len <= 64) {
-        int v = (lane < len) ? rcol[s + lane] : INT_MAX;
-#pragma unroll
-        for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                const int o = __shfl_xor(v, j, 64);
-                const bool up = ((lane & k) == 0);
-                const bool lower = ((lane & j) == 0);
-                v = (lower == up) ? min(v, o) : max(v, o);
-            }
-        }
-        if (lane < len) rcol[s + lane] = v;
-    } else if (len <= kRtLdsRow) {
-        // longer rows (the folded R~ of a coarse level: ~150 entries): the row
-        // in LDS, every entry placed at its rank (the row indices are distinct)
-        __shared__ int buf[4][kRtLdsRow];
-        int *b = buf[threadIdx.x >> 6];
-        for (int a = lane; a < len; a += 64) b[a] = rcol[s + a];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int a = lane; a < len; a += 64) {
-            const int v = b[a];
-            int rk = 0;
-            for (int q = 0; q < len; ++q) rk += b[q] < v;
-            rcol[s + rk] = v;
-        }
-    } else if (lane == 0) {
-        for (int a = s + 1; a < e; ++a) {
-            const int key = rcol[a];
-            int b = a - 1;
-            while (b >= s && rcol[b] > key) {
-                rcol[b + 1] = rcol[b];
-                --b;
-            }
-            rcol[b + 1] = key;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int a = s + lane; a < e; a += 64) {
-        const int i = rcol[a];
-        int lo = prow[i], hi = prow[i + 1] - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (pcol[mid] < J) lo = mid + 1;
-            else hi = mid;
-        }
-        rval[a] = pval[lo];
     }
 }
 
@@ -1774,16 +1686,6 @@ __device__ __forceinline__ void bgj_inv_mfma(dbl4 (&c)[2][2], double thr, double
     }
 }
 
-// XFK_BGJ_INV=0: the pivot-block inverse by bgj_diag_inv (FMA updates)
-static int bgj_inv_mode()
-{
-    static const int v = [] {
-        const char *e = std::getenv("XFK_BGJ_INV");
-        return e ? std::atoi(e) : 1;
-    }();
-    return v;
-}
-
 template <int S>
 __device__ __forceinline__ void bgj_load(double *__restrict__ dst, const double *__restrict__ src, size_t ld)
 {
@@ -1835,7 +1737,7 @@ __global__ void __launch_bounds__(256) k_bgj_step(int k, int nbk, int ld, double
                                                   const double *__restrict__ Dk, const double *__restrict__ Rk,
                                                   const double *__restrict__ Ck, double *__restrict__ Dn,
                                                   double *__restrict__ Rn, double *__restrict__ Cn,
-                                                  const double *__restrict__ maxd, int inv_mode)
+                                                  const double *__restrict__ maxd)
 {
     const int nt = nbk * nbk, kn = k + 1 < nbk ? k + 1 : 0;
     const int b = (int)((blockIdx.x + (unsigned)(kn * nbk + kn)) % (unsigned)nt);
@@ -1899,8 +1801,7 @@ __global__ void __launch_bounds__(256) k_bgj_step(int k, int nbk, int ld, double
     }
     double *rn = (i == k + 1) ? Rn + j * T2 : nullptr;
     double *cn = (j == k + 1) ? Cn + i * T2 : nullptr;
-    const bool fast = piv && inv_mode != 0;
-    if (piv) __syncthreads();   // Xs / Ys are reused below
+    if (piv) __syncthreads();   // Ys is reused below
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
@@ -1913,28 +1814,16 @@ __global__ void __launch_bounds__(256) k_bgj_step(int k, int nbk, int ld, double
                 *e = v;
                 if (rn) rn[row * kBj + col] = v;
                 if (cn) cn[row * kBj + col] = v;
-                if (fast) c[ti][tj][r] = v;
-                else if (piv) Xs[row * kBj + col] = v;
+                if (piv) c[ti][tj][r] = v;
             }
     if (!piv) return;
-    if (fast) {
-        bgj_inv_mfma(c, 1e-11 * (*maxd), Ys);
+    bgj_inv_mfma(c, 1e-11 * (*maxd), Ys);
 #pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
+    for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
+        for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) Dn[bgj_row(ti, r) * kBj + bgj_col(tj)] = c[ti][tj][r];
-        return;
-    }
-    __syncthreads();
-    const int jl = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double a[16];
-#pragma unroll
-    for (int m = 0; m < 16; ++m) a[m] = Xs[(16 * w + m) * kBj + jl];
-    bgj_diag_inv(a, 1e-11 * (*maxd), Ys);
-#pragma unroll
-    for (int m = 0; m < 16; ++m) Dn[(16 * w + m) * kBj + jl] = a[m];
+            for (int r = 0; r < 4; ++r) Dn[bgj_row(ti, r) * kBj + bgj_col(tj)] = c[ti][tj][r];
 }
 
 // Nested-dissection steps.  The coarsest operator is reordered by a
@@ -1962,7 +1851,7 @@ struct BgjStep {
 // by-value kernel argument would be placed in scratch memory)
 __global__ void __launch_bounds__(256, 2) k_bgj_multi(int nbk, int ld, double *__restrict__ M, BgjStep st,
                                                       const unsigned char *__restrict__ mask,
-                                                      const int *__restrict__ tiles, const double *maxd, int inv_mode)
+                                                      const int *__restrict__ tiles, const double *maxd)
 {
     const size_t T2 = (size_t)kBj * kBj;
     int i, j;
@@ -2067,8 +1956,7 @@ __global__ void __launch_bounds__(256, 2) k_bgj_multi(int nbk, int ld, double *_
         rs[t] = (t < st.nn && i == st.nx[t]) ? st.Rn[t] + j * T2 : nullptr;
         cs[t] = (t < st.nn && j == st.nx[t]) ? st.Cn[t] + i * T2 : nullptr;
     }
-    const bool fast = Dpiv && inv_mode != 0;
-    if (Dpiv) __syncthreads();   // Xs / Ys are reused below
+    if (Dpiv) __syncthreads();   // Ys is reused below
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
@@ -2084,38 +1972,26 @@ __global__ void __launch_bounds__(256, 2) k_bgj_multi(int nbk, int ld, double *_
                     if (rs[t]) rs[t][row * kBj + col] = v;
                     if (cs[t]) cs[t][row * kBj + col] = v;
                 }
-                if (fast) acc[ti][tj][r] = v;
-                else if (Dpiv) Xs[row * kBj + col] = v;
+                if (Dpiv) acc[ti][tj][r] = v;
             }
     if (!Dpiv) return;
-    if (fast) {
-        bgj_inv_mfma(acc, 1e-11 * (*maxd), Ys);
+    bgj_inv_mfma(acc, 1e-11 * (*maxd), Ys);
 #pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
+    for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
+        for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) Dpiv[bgj_row(ti, r) * kBj + bgj_col(tj)] = acc[ti][tj][r];
-        return;
-    }
-    __syncthreads();
-    const int jl = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double a[16];
-#pragma unroll
-    for (int m = 0; m < 16; ++m) a[m] = Xs[(16 * w + m) * kBj + jl];
-    bgj_diag_inv(a, 1e-11 * (*maxd), Ys);
-#pragma unroll
-    for (int m = 0; m < 16; ++m) Dpiv[(16 * w + m) * kBj + jl] = a[m];
+            for (int r = 0; r < 4; ++r) Dpiv[bgj_row(ti, r) * kBj + bgj_col(tj)] = acc[ti][tj][r];
 }
 
 // first step of the first phase: pivot-block inverses (workgroups 0 .. n-1)
 // and row / column snapshots of the chains' first pivot blocks
 __global__ void __launch_bounds__(256) k_bgj_init(int nbk, int ld, const double *__restrict__ M, BgjStep st,
-                                                  const double *__restrict__ maxd, int inv_mode)
+                                                  const double *__restrict__ maxd)
 {
     const int b = blockIdx.x;
     if (b < st.nn) {
-        __shared__ __attribute__((aligned(16))) double lds[kBjDiagLds];
+        __shared__ __attribute__((aligned(16))) double lds[kBjInvLds];
         int k = 0;
         double *D = nullptr;
 #pragma unroll
@@ -2124,31 +2000,21 @@ __global__ void __launch_bounds__(256) k_bgj_init(int nbk, int ld, const double 
                 k = st.nx[t];
                 D = st.Dn[t];
             }
-        const int jl = threadIdx.x & 63, w = threadIdx.x >> 6;
         const size_t base = (size_t)k * kBj * ld + (size_t)k * kBj;
-        if (inv_mode != 0) {
-            dbl4 c[2][2];
+        dbl4 c[2][2];
 #pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
+        for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-                for (int tj = 0; tj < 2; ++tj)
+            for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) c[ti][tj][r] = M[base + (size_t)bgj_row(ti, r) * ld + bgj_col(tj)];
-            bgj_inv_mfma(c, 1e-11 * (*maxd), lds);
+                for (int r = 0; r < 4; ++r) c[ti][tj][r] = M[base + (size_t)bgj_row(ti, r) * ld + bgj_col(tj)];
+        bgj_inv_mfma(c, 1e-11 * (*maxd), lds);
 #pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
+        for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-                for (int tj = 0; tj < 2; ++tj)
+            for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) D[bgj_row(ti, r) * kBj + bgj_col(tj)] = c[ti][tj][r];
-            return;
-        }
-        double a[16];
-#pragma unroll
-        for (int m = 0; m < 16; ++m) a[m] = M[base + (size_t)(16 * w + m) * ld + jl];
-        bgj_diag_inv(a, 1e-11 * (*maxd), lds);
-#pragma unroll
-        for (int m = 0; m < 16; ++m) D[(16 * w + m) * kBj + jl] = a[m];
+                for (int r = 0; r < 4; ++r) D[bgj_row(ti, r) * kBj + bgj_col(tj)] = c[ti][tj][r];
         return;
     }
     const int e0 = b - st.nn, ch = e0 / (2 * nbk), rem = e0 % (2 * nbk);
@@ -2722,15 +2588,8 @@ namespace {
 // prefixes are stored -- one memory round trip each way.
 constexpr int kScanLds = 16384;
 
-// XFK_NO_SCAN_LDS=1: every scan through hipcub
-bool scan_lds_on(int n)
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_NO_SCAN_LDS");
-        return !(e && std::atoi(e) != 0);
-    }();
-    return v && n <= kScanLds;
-}
+// levels / transfer operators with at least this many rows use the tile kernels
+constexpr int kTileMinRows = 16384;
 
 __global__ void __launch_bounds__(1024) k_scan_lds(int n, const int *__restrict__ in, int *__restrict__ out)
 {
@@ -2776,7 +2635,7 @@ __global__ void __launch_bounds__(1024) k_scan_lds(int n, const int *__restrict_
 
 int scan_total(Amg &A, hipStream_t s, const int *in, int *out, int n, long long &total)
 {
-    if (scan_lds_on(n)) {
+    if (n <= kScanLds) {
         k_scan_lds<<<1, 1024, 0, s>>>(n, in, out);
         AMG_CHECK(hipGetLastError());
     } else {
@@ -2798,7 +2657,7 @@ int scan_total(Amg &A, hipStream_t s, const int *in, int *out, int n, long long 
 // only fills the unused last slot)
 int scan_only(DBuf<char> &tmp, hipStream_t s, const int *in, int *out, int n)
 {
-    if (scan_lds_on(n)) {
+    if (n <= kScanLds) {
         k_scan_lds<<<1, 1024, 0, s>>>(n, in, out);
         AMG_CHECK(hipGetLastError());
         return XFK_OK;
@@ -2824,11 +2683,7 @@ int read_flag(Amg &A, hipStream_t s, int idx, int &v)
 // compaction moves them row by row (the layout before the dense slabs)
 static bool spgemm_slab_on()
 {
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_SPGEMM_SLAB");
-        return !(e && std::atoi(e) == 0);
-    }();
-    return v;
+    return env_int("XFK_SPGEMM_SLAB", 1) != 0;
 }
 
 // rows per k_spgemm_sort wavefront (64 / G of the instance launch_sort takes for `cap`)
@@ -2981,7 +2836,7 @@ int spgemm(Amg &M, hipStream_t s, int nrows, const SgX &X, const SgY &Y, DBuf<in
         if (key >= 0) {
             // XFK_AMG_TEST_SMALL_HINT=1 (tests only): store a too-small capacity so
             // the next setup takes the overflow-and-rebuild path
-            const bool small = std::getenv("XFK_AMG_TEST_SMALL_HINT") != nullptr;
+            const bool small = env_set("XFK_AMG_TEST_SMALL_HINT");
             M.cap_hint[key] = small ? 16 : cap;   // (16: the smallest capacity the kernels have)
         }
         return XFK_OK;
@@ -3018,74 +2873,23 @@ int spgemm(Amg &M, hipStream_t s, int nrows, const SgX &X, const SgY &Y, DBuf<in
     return XFK_OK;
 }
 
-// levels / transfer operators with at least this many rows use the tile kernels
-// (XFK_TILE_MIN_ROWS overrides, for experiments)
-static int tile_min_rows()
-{
-    static const int v = [] {
-        const char *e = std::getenv("XFK_TILE_MIN_ROWS");
-        return e ? std::atoi(e) : 16384;
-    }();
-    return v;
-}
-#define kTileMinRows tile_min_rows()
-
-// folded coarse levels (k_fold_pre); XFK_AMG_FOLD=0 keeps the four-launch form
-static bool fold_levels()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_AMG_FOLD");
-        return !e || std::atoi(e) != 0;
-    }();
-    return v;
-}
-
 // lanes per row for a CSR with this many nonzeros per row on average
 int lanes_for(double per_row)
 {
     return per_row <= 6.0 ? 4 : (per_row <= 20.0 ? 8 : 16);
 }
 
-// lab switch for the long-row transfer operators (R of level 0): 0 = tile of
-// 256 rows with 6 slots (48 KiB LDS), 1 = G lanes per row, 2 = tile of 128
-// rows with 6 slots (24 KiB), 3 = tile of 256 rows with 3 slots (24 KiB)
-static int rmv_mode()
-{
-    static const int v = [] {
-        const char *e = std::getenv("XFK_RMV");
-        return e ? std::atoi(e) : 0;
-    }();
-    return v;
-}
-
 // level 0 with f32 values: the 256-row tile kernels (level 0 always has >= kTileMinRows rows)
 // (128- and 64-row tiles for R's ~25-entry rows were measured slower: 14.4 -> 15.0 / 15.6 us,
 // profiles/r04_experiments/r04h_XFK_R0_TILE_*.json)
-// XFK_R0_SLOTS (lab): staging slots per lane for the long rows (6 = 6144
-// products per pass; R's ~27-entry rows fill 256-row tiles with ~6900);
-// 8 / 7 (one pass, 64 / 56 KiB of LDS) measured 20.3 / 20.2 us vs 14.7 us
-static int r0_slots()
-{
-    static const int v = [] {
-        const char *e = std::getenv("XFK_R0_SLOTS");
-        return e ? std::atoi(e) : 6;
-    }();
-    return v;
-}
-
+// staging slots per lane for the long rows: 6 = 6144 products per pass (R's
+// ~27-entry rows fill 256-row tiles with ~6900); 8 / 7 (one pass, 64 / 56 KiB
+// of LDS) measured 20.3 / 20.2 us vs 14.7 us
 void launch_mv32(hipStream_t s, int n, const int *rowptr, const int *col, const float *val, const double *x,
                  double *y, bool acc, int G, const int *done, const unsigned short *c16, const int *cbase)
 {
     if (n <= 0) return;
     const int g = (n + 255) / 256;
-    if (G > 4 && r0_slots() != 6 && !acc) {
-        const int v = r0_slots();
-        if (v == 8) k_csr_mv_tile<256, false, 8><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-        else if (v == 4) k_csr_mv_tile<256, false, 4><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-        else if (v == 3) k_csr_mv_tile<256, false, 3><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-        else k_csr_mv_tile<256, false, 2><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-        return;
-    }
     if (G <= 4) {
         if (acc) k_csr_mv_tile<256, true, 2><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
         else k_csr_mv_tile<256, false, 2><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
@@ -3100,19 +2904,7 @@ void launch_mv(hipStream_t s, int n, const int *rowptr, const int *col, const do
                bool acc, int G, const int *done, const unsigned short *c16 = nullptr, const int *cbase = nullptr)
 {
     if (n <= 0) return;
-    if (n >= kTileMinRows && G == 8 && rmv_mode() == 2) {
-        const int g = (n + 127) / 128;
-        if (acc) k_csr_mv_tile<128, true, 6><<<g, 128, 0, s>>>(n, rowptr, col, val, x, y, done);
-        else k_csr_mv_tile<128, false, 6><<<g, 128, 0, s>>>(n, rowptr, col, val, x, y, done);
-        return;
-    }
-    if (n >= kTileMinRows && G == 8 && rmv_mode() == 3) {
-        const int g = (n + 255) / 256;
-        if (acc) k_csr_mv_tile<256, true, 3><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done);
-        else k_csr_mv_tile<256, false, 3><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done);
-        return;
-    }
-    if (n >= kTileMinRows && G <= 8 && !(G == 8 && rmv_mode() == 1)) {
+    if (n >= kTileMinRows && G <= 8) {
         // G = 8: 7..20 entries per row -> 6 slots per lane, one staging pass per tile
         const int g = (n + 255) / 256;
         if (G <= 4) {
@@ -3263,77 +3055,18 @@ SideStream::~SideStream()
 // default the level above the last V-cycle level (nlev - 3: on configs[2]
 // level 1, whose coarse level of 14k rows costs a few launches per visit;
 // 21 -> 18 PCG iterations), in single-device and replicated hierarchies
-// alike.  wlevel when set (-1: none), else XFK_AMG_W (-1: none).
+// alike.  wlevel when set (-1: none).
 int Amg::wcycle_level() const
 {
-    static const int v = [] {
-        const char *e = std::getenv("XFK_AMG_W");
-        return e ? std::atoi(e) : -2;
-    }();
-    const int w = wlevel != -2 ? wlevel : v;
-    if (w != -2) return w;
+    if (wlevel != -2) return wlevel;
     return nlev >= 4 ? nlev - 3 : -1;
 }
 
-// W-cycle at level l: l is the W level, or between XFK_AMG_W_LO and it
-// (experiments with W over several levels; default: the W level alone)
+// W-cycle at level l: l is the W level
 bool Amg::w_at(int l) const
 {
-    static const int lo_env = [] {
-        const char *e = std::getenv("XFK_AMG_W_LO");
-        return e ? std::atoi(e) : -1;
-    }();
     const int w = wcycle_level();
-    if (w < 0 || l > w || l + 1 >= nlev - 1) return false;
-    return l == w || (lo_env >= 0 && l >= lo_env);
-}
-
-// XFK_NO_COL16=1: level 0 reads 32-bit column indices
-static bool col16_on()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_NO_COL16");
-        return !(e && std::atoi(e) != 0);
-    }();
-    return v;
-}
-
-// XFK_NO_SIDE_SETUP=1: every setup step on the main stream
-static bool side_setup_on()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_NO_SIDE_SETUP");
-        return !(e && std::atoi(e) != 0);
-    }();
-    return v;
-}
-
-// XFK_AMG_F32=0: level 0's V-cycle operators keep f64 values
-// signed strength (k_amg_strength); XFK_AMG_ABS_STRENGTH=1: |a_ij|
-static bool signed_strength()
-{
-    static const bool v = std::getenv("XFK_AMG_ABS_STRENGTH") == nullptr;
-    return v;
-}
-
-static bool f32_on()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_AMG_F32");
-        return !(e && std::atoi(e) == 0);
-    }();
-    return v;
-}
-
-// XFK_AMG_F32_SWEEP=1: the level-0 sweeps read the f32 copy of A too (measured
-// slower: the sweep's two gathers per entry, not its value stream, bound it)
-static bool f32_sweep_on()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_AMG_F32_SWEEP");
-        return e && std::atoi(e) != 0;
-    }();
-    return v;
+    return w >= 0 && l == w && l + 1 < nlev - 1;
 }
 
 // f32 copy of a CSR's values (cap: an upper bound of its length, for the allocation)
@@ -3344,38 +3077,12 @@ static int to_f32(hipStream_t s, int n, const int *rowptr, long long cap, const 
     return XFK_OK;
 }
 
-// XFK_MIS_XCD=0: MIS-2 sweeps with round-robin blocks (measurement)
-static bool mis_xcd_on()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_MIS_XCD");
-        return !(e && std::atoi(e) == 0);
-    }();
-    return v;
-}
-
-// XFK_NO_SPEC=1: no setup work enqueued ahead of a host check
-static bool spec_on()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_NO_SPEC");
-        return !(e && std::atoi(e) != 0);
-    }();
-    return v;
-}
-
 // Off by default: on MI355X each cross-stream hop (side stream waits for the
 // main stream, main waits for the exchange) costs more than the interior
 // tiles it overlaps -- configs[4] rank 0 of 8, compute only, 469 vs 304 us
 // per PCG iteration (profiles/r04c_rank0_overlap.txt).  XFK_OVERLAP=1 turns
-// it on (XFK_NO_OVERLAP=1 keeps it off).
-bool overlap_enabled()
-{
-    const char *n = std::getenv("XFK_NO_OVERLAP");
-    if (n && std::atoi(n) != 0) return false;
-    const char *e = std::getenv("XFK_OVERLAP");
-    return e && std::atoi(e) != 0;
-}
+// it on.
+bool overlap_enabled() { return env_int("XFK_OVERLAP", 0) != 0; }
 
 int Amg::resolve_deferred(hipStream_t s, bool &overflow)
 {
@@ -3477,7 +3184,7 @@ int Amg::init(hipStream_t s)
 // the padded rows: round 4 measured the warm setup 2.24 -> 2.64 ms with
 // seeded A P and R (A P) capacities), while a capacity that changes between
 // setups changes the Galerkin products' summation order, so repeated solves
-// would no longer be bit-identical.  XFK_AMG_NO_SEED=1: measure everything.
+// would no longer be bit-identical.
 
 // Hints across problems.  A fresh problem has no hints of its own; the last
 // single-device setup of the process leaves its SpGEMM capacities, MIS-2
@@ -3510,11 +3217,7 @@ HintStore &hint_store()
     static HintStore *h = new HintStore();   // (never destroyed, like the device caches)
     return *h;
 }
-bool foreign_on()
-{
-    static const bool v = std::getenv("XFK_AMG_NO_FOREIGN") == nullptr;
-    return v;
-}
+bool foreign_on() { return !env_set("XFK_AMG_NO_FOREIGN"); }
 }  // namespace
 
 }  // namespace xfk
@@ -3546,7 +3249,7 @@ void Amg::save_hints(int n0, long long nnz0)
     h.cap = cap_hint;
     // XFK_AMG_TEST_FOREIGN_BIG=1 (tests only): store one class too large, so
     // the next problem's device check must refuse it and rebuild
-    if (std::getenv("XFK_AMG_TEST_FOREIGN_BIG"))
+    if (env_set("XFK_AMG_TEST_FOREIGN_BIG"))
         for (auto &c : h.cap) c.second = std::min(2 * c.second, (int)kSortCap);
     h.mis = mis_hint;
     h.nd_key = nd_key;
@@ -3600,8 +3303,7 @@ int Amg::load_hints(hipStream_t s, int n0, long long nnz0)
 
 void Amg::seed_hints()
 {
-    static const bool off = std::getenv("XFK_AMG_NO_SEED") != nullptr;
-    if (off || row_max0 <= 0 || !cap_hint.empty() || !mis_hint.empty()) return;
+    if (row_max0 <= 0 || !cap_hint.empty() || !mis_hint.empty()) return;
     auto cap = [](long long v) { return v <= 16 ? 16 : v <= 32 ? 32 : v <= 64 ? 64 : v <= 128 ? 128 : 256; };
     if (row_max0 <= kSortCap) cap_hint[0] = cap(row_max0);
     for (int l = 0; l < kAmgMaxLevels; ++l) mis_hint[l] = 12;
@@ -3609,12 +3311,7 @@ void Amg::seed_hints()
 
 double Amg::theta_at(int l) const
 {
-    static const double env = [] {
-        const char *e = std::getenv("XFK_AMG_THETA_COARSE");
-        return e ? std::atof(e) : -1.0;
-    }();
     if (l == 0) return theta;
-    if (env >= 0.0) return env;
     return theta_coarse >= 0.0 ? theta_coarse : theta;
 }
 
@@ -3650,40 +3347,19 @@ int Amg::setup(hipStream_t s, int n0, int ncl0, const int *rowptr0, const int *c
 // not coarsen usefully (allow_stop) or has no aggregate.
 // T = M^T of an n x nc CSR whose rows are sorted by column (T's rows come
 // out sorted by row): counting transpose, the fill counting the row counts
-// back down, rows sorted by a wave bitonic network, values looked up in M.
+// back down and carrying the values, then each row's pairs sorted by rank.
 // T's arrays hold as many entries as M (no read-back of the scan).
 // cnt / tmp: scratch of the stream it runs on (the setup's side stream has its own)
-// XFK_RT_TILE=0: the per-entry transpose (global atomics, values looked up after the sort)
-static bool rt_tile_on()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_RT_TILE");
-        return !(e && std::atoi(e) == 0);
-    }();
-    return v;
-}
-
 static int transpose_csr(DBuf<int> &cnt, DBuf<char> &tmp, hipStream_t s, int n, int nc, const int *mrow,
                          const int *mcol, const double *mval, int *trow, int *tcol, double *tval)
 {
     AMG_CHECK(cnt.alloc((size_t)std::max(n, nc) + 1));
     AMG_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)nc + 1), s));
-    const bool tiled = rt_tile_on();
-    if (n > 0) {
-        if (tiled) k_rt_tile<false><<<nb(n), 256, 0, s>>>(n, mrow, mcol, mval, trow, cnt.p, tcol, tval);
-        else k_rt_count<<<nb(n), kB, 0, s>>>(n, mrow, mcol, cnt.p);
-    }
+    if (n > 0) k_rt_tile<false><<<nb(n), 256, 0, s>>>(n, mrow, mcol, mval, trow, cnt.p, tcol, tval);
     int rc = scan_only(tmp, s, cnt.p, trow, nc);
     if (rc != XFK_OK) return rc;
-    if (tiled) {
-        if (n > 0) k_rt_tile<true><<<nb(n), 256, 0, s>>>(n, mrow, mcol, mval, trow, cnt.p, tcol, tval);
-        if (nc > 0) k_rt_sort_pairs<<<(int)((((long long)nc + 3) / 4 * 64 + 255) / 256), 256, 0, s>>>(nc, trow, tcol, tval);
-        AMG_CHECK(hipGetLastError());
-        return XFK_OK;
-    }
-    if (n > 0) k_rt_fill<<<nb(n), kB, 0, s>>>(n, mrow, mcol, trow, cnt.p, tcol);
-    if (nc > 0)
-        k_rt_sort_vals<<<(int)(((long long)nc * 64 + 255) / 256), 256, 0, s>>>(nc, trow, tcol, mrow, mcol, mval, tval);
+    if (n > 0) k_rt_tile<true><<<nb(n), 256, 0, s>>>(n, mrow, mcol, mval, trow, cnt.p, tcol, tval);
+    if (nc > 0) k_rt_sort_pairs<<<(int)((((long long)nc + 3) / 4 * 64 + 255) / 256), 256, 0, s>>>(nc, trow, tcol, tval);
     AMG_CHECK(hipGetLastError());
     return XFK_OK;
 }
@@ -3729,8 +3405,8 @@ int Amg::aggregate(hipStream_t s, int l, long long &nc, bool allow_stop)
     // (levels of a sharded hierarchy replicated on every rank speculate like a
     // single device's: every rank holds the same level and hints, so every
     // rank takes the same decisions; sharded levels keep their host checks)
-    const bool spec = spec_on() && !g_prof && !A.dist && hint != mis_hint.end() && cap_hint.count(4 * l) &&
-                      def_n + 4 <= kAmgDeferSlots && !std::getenv("XFK_AMG_DEBUG");
+    const bool spec = !g_prof && !A.dist && hint != mis_hint.end() && cap_hint.count(4 * l) &&
+                      def_n + 4 <= kAmgDeferSlots && !env_set("XFK_AMG_DEBUG");
     bool joined = false;
     auto joins_and_p = [&]() { return joins_and_p_impl(s, l); };
     AMG_CHECK(mis_out.alloc(4));
@@ -3738,24 +3414,21 @@ int Amg::aggregate(hipStream_t s, int l, long long &nc, bool allow_stop)
         for (int b = 0; b < batch; ++b, ++rounds) {
             int *cur = und2 + (rounds & 1), *prev = und2 + ((rounds + 1) & 1);
             const bool last = b + 1 == batch;   // its update also writes the root flags
-            const int xc = mis_xcd_on() ? 1 : 0;
             if (A.nnz > 9LL * n) {
-                k_mis_max<4><<<nb(4LL * n), kB, 0, s>>>(n, A.rowptr, cv, sflag.p, key.p, t1.p, prev, cur, run,
-                                                         act.p, xc);
+                k_mis_max<4><<<nb(4LL * n), kB, 0, s>>>(n, A.rowptr, cv, sflag.p, key.p, t1.p, prev, cur, run, act.p);
                 if (last)
                     k_mis_update<4, true><<<nb(4LL * n), kB, 0, s>>>(n, A.rowptr, cv, sflag.p, t1.p, key.p, prev, cur,
-                                                                      flag.p, xc);
+                                                                      flag.p);
                 else
                     k_mis_update<4><<<nb(4LL * n), kB, 0, s>>>(n, A.rowptr, cv, sflag.p, t1.p, key.p, prev, cur,
-                                                                nullptr, xc);
+                                                                nullptr);
             } else {
-                k_mis_max<1><<<nb(n), kB, 0, s>>>(n, A.rowptr, cv, sflag.p, key.p, t1.p, prev, cur, run, act.p, xc);
+                k_mis_max<1><<<nb(n), kB, 0, s>>>(n, A.rowptr, cv, sflag.p, key.p, t1.p, prev, cur, run, act.p);
                 if (last)
                     k_mis_update<1, true><<<nb(n), kB, 0, s>>>(n, A.rowptr, cv, sflag.p, t1.p, key.p, prev, cur,
-                                                                flag.p, xc);
+                                                                flag.p);
                 else
-                    k_mis_update<1><<<nb(n), kB, 0, s>>>(n, A.rowptr, cv, sflag.p, t1.p, key.p, prev, cur, nullptr,
-                                                          xc);
+                    k_mis_update<1><<<nb(n), kB, 0, s>>>(n, A.rowptr, cv, sflag.p, t1.p, key.p, prev, cur, nullptr);
             }
         }
         int rc = scan_only(*this, s, flag.p, cursor.p, n);   // cursor = root ids
@@ -3786,13 +3459,13 @@ int Amg::aggregate(hipStream_t s, int l, long long &nc, bool allow_stop)
     }
     if (!joined && (rc = joins_and_p()) != XFK_OK) return rc;
     A.nc = (int)nc;
-    if (std::getenv("XFK_AMG_DEBUG")) std::fprintf(stderr, "[amg] level %d P nnz %lld\n", l, A.pnnz);
+    if (env_set("XFK_AMG_DEBUG")) std::fprintf(stderr, "[amg] level %d P nnz %lld\n", l, A.pnnz);
     // R = P^T: on the side stream (single-device levels) while the main
     // stream forms A P; the Galerkin product R (A P) waits for it
     AMG_CHECK(A.rrow.alloc((size_t)nc + 1));
     AMG_CHECK(A.rcol.alloc((size_t)std::max(1LL, A.pnnz)));
     AMG_CHECK(A.rval.alloc((size_t)std::max(1LL, A.pnnz)));
-    const bool off = side_setup_on() && !A.dist && !dist;
+    const bool off = !A.dist && !dist;
     hipStream_t ts = s;
     if (off) {
         if ((rc = sw.init()) != XFK_OK) return rc;
@@ -3810,10 +3483,7 @@ int Amg::aggregate(hipStream_t s, int l, long long &nc, bool allow_stop)
     }
     if (l == 0 && A.has16 && (rc = build_col16<256>(ts, (int)nc, A.rrow.p, A.rcol.p, A.pnnz, A.r16, A.r16b)) != XFK_OK)
         return rc;
-    if (l == 0 && A.has32 &&
-        ((rc = to_f32(ts, (int)nc, A.rrow.p, A.pnnz, A.rval.p, A.r32)) != XFK_OK ||
-         (f32_sweep_on() && (rc = to_f32(ts, n, A.rowptr, A.nnz, A.val, A.a32)) != XFK_OK)))
-        return rc;
+    if (l == 0 && A.has32 && (rc = to_f32(ts, (int)nc, A.rrow.p, A.pnnz, A.rval.p, A.r32)) != XFK_OK) return rc;
     if (l == 0 && A.has32 && A.dist &&   // the sharded level 0 prolongs through P itself (no fold)
         ((rc = to_f32(ts, n, A.prow.p, A.pnnz, A.pval.p, A.p32)) != XFK_OK ||
          (rc = build_col16<256>(ts, n, A.prow.p, A.pcol.p, A.pnnz, A.p16, A.p16b)) != XFK_OK))
@@ -3846,7 +3516,7 @@ int Amg::joins_and_p_impl(hipStream_t s, int l)
     std::swap(agg.p, agg1.p);   // agg = the joined map
     std::swap(agg.n, agg1.n);
     if (g_prof) g_prof->end();
-    if (std::getenv("XFK_AMG_DEBUG")) {
+    if (env_set("XFK_AMG_DEBUG")) {
         DBuf<int> d;
         AMG_CHECK(d.alloc(3));
         AMG_CHECK(hipMemsetAsync(d.p, 0, 3 * sizeof(int), s));
@@ -3915,7 +3585,7 @@ int Amg::nd_order(hipStream_t s, const AmgLevel &C, int &ld)
     const int n = C.n;
     nd_phases.clear();
     ld = ((n + kBj - 1) / kBj) * kBj;
-    if (n < 8 * kBj || std::getenv("XFK_NO_ND")) {
+    if (n < 8 * kBj || env_set("XFK_NO_ND")) {
         nd_key_n = -1;
         return XFK_OK;
     }
@@ -3989,15 +3659,12 @@ int Amg::nd_order(hipStream_t s, const AmgLevel &C, int &ld)
         for (int lev = 0; lev < D && lev < Dmax; ++lev) nsep += lev_nsep[lev];
         const std::vector<std::vector<int>> &sets = lev_sets[std::min(D, lev_done + 1)];
         const std::vector<std::vector<std::vector<int>>> &seps = lev_seps;
-        if (std::getenv("XFK_AMG_DEBUG")) {
+        if (env_set("XFK_AMG_DEBUG")) {
             std::fprintf(stderr, "[amg] nested dissection depth %d: ok %d separators %zu, sets", D, (int)ok, nsep);
             for (const auto &x : sets) std::fprintf(stderr, " %zu", x.size());
             std::fprintf(stderr, "\n");
         }
-        // (XFK_ND_DEPTH: this depth whatever its separators -- measurement hook)
-        const char *fd = std::getenv("XFK_ND_DEPTH");
-        if (fd && std::atoi(fd) != D) continue;
-        if (!ok || (!fd && 3 * nsep > (size_t)n)) continue;
+        if (!ok || 3 * nsep > (size_t)n) continue;
         if (D > 1)
             for (const auto &x : sets) ok = ok && x.size() >= (size_t)kBj;
         if (!ok) continue;
@@ -4029,7 +3696,7 @@ int Amg::nd_order(hipStream_t s, const AmgLevel &C, int &ld)
             }
     }
     if (g.empty()) return XFK_OK;
-    if (std::getenv("XFK_AMG_DEBUG")) {
+    if (env_set("XFK_AMG_DEBUG")) {
         std::fprintf(stderr, "[amg] coarsest %d rows: nested dissection, %d groups:", n, (int)g.size());
         for (const G &x : g) std::fprintf(stderr, " %d/%d", (int)x.rows.size(), x.phase);
         std::fprintf(stderr, "\n");
@@ -4144,7 +3811,7 @@ int Amg::dense_inverse(hipStream_t s, const AmgLevel &C, int ld)
             st.Rn[c] = Rb(c, 0);
             st.Cn[c] = Cb(c, 0);
         }
-        k_bgj_init<<<st.nn * (1 + 2 * nbk), 256, 0, s>>>(nbk, ld, cinv.p, st, maxd, bgj_inv_mode());
+        k_bgj_init<<<st.nn * (1 + 2 * nbk), 256, 0, s>>>(nbk, ld, cinv.p, st, maxd);
         for (size_t ph = 0; ph < nd_phases.size(); ++ph) {
             const NdPhase &P = nd_phases[ph];
             for (int t = 0; t < P.steps; ++t) {
@@ -4171,7 +3838,7 @@ int Amg::dense_inverse(hipStream_t s, const AmgLevel &C, int ld)
                     x.Cn[c] = Cb(c, qq);
                 }
                 k_bgj_multi<<<P.ntiles + x.nn, 256, 0, s>>>(nbk, ld, cinv.p, x, nd_mask.p + ph * (size_t)nbk,
-                                                            nd_tiles.p + P.tiles_off, maxd, bgj_inv_mode());
+                                                            nd_tiles.p + P.tiles_off, maxd);
                 par = qq;
             }
         }
@@ -4182,18 +3849,18 @@ int Amg::dense_inverse(hipStream_t s, const AmgLevel &C, int ld)
         st.Dn[0] = Db(0, 0);
         st.Rn[0] = Rb(0, 0);
         st.Cn[0] = Cb(0, 0);
-        k_bgj_init<<<1 + 2 * nbk, 256, 0, s>>>(nbk, ld, cinv.p, st, maxd, bgj_inv_mode());
+        k_bgj_init<<<1 + 2 * nbk, 256, 0, s>>>(nbk, ld, cinv.p, st, maxd);
         for (int k = 0; k < nbk; ++k) {
             const int p = k & 1, q = (k + 1) & 1;
             k_bgj_step<<<nbk * nbk, 256, 0, s>>>(k, nbk, ld, cinv.p, Db(0, p), Rb(0, p), Cb(0, p), Db(0, q),
-                                                 Rb(0, q), Cb(0, q), maxd, bgj_inv_mode());
+                                                 Rb(0, q), Cb(0, q), maxd);
         }
     }
     {
         const int ldo = ((C.n + kBj - 1) / kBj) * kBj;
         const dim3 g(ld / 64, ld / 64);
         AMG_CHECK(cinv_sc.alloc((size_t)ldo));
-        cinv_f64 = !(prec32 < 0 ? f32_on() : prec32 != 0);   // (f64 transfers: the f64 inverse too)
+        cinv_f64 = prec32 == 0;   // (f64 transfers: the f64 inverse too)
         if (cinv_f64) {
             AMG_CHECK(cinv_o64.alloc((size_t)ldo * ldo));
             AMG_CHECK(hipMemsetAsync(cinv_o64.p, 0, sizeof(double) * (size_t)ldo * ldo, s));   // (padding columns)
@@ -4252,8 +3919,8 @@ int Amg::build(hipStream_t s, int l0)
         // level 0 (single device): 16-bit tile columns of A for the SpMV and
         // the sweeps, built off the critical path (they are read from the
         // first V-cycle on, after the join at the end of the build)
-        A.has16 = l == 0 && !A.dist && !dist && (col16 < 0 ? col16_on() : col16 != 0);
-        A.has32 = A.has16 && (prec32 < 0 ? f32_on() : prec32 != 0);
+        A.has16 = l == 0 && !A.dist && !dist && col16 != 0;
+        A.has32 = A.has16 && prec32 != 0;
         if (A.has16) {   // (on the main stream: the aggregation reads them too)
             int rc0 = build_col16<kCgBlock>(s, n, A.rowptr, A.col, A.nnz, A.a16, A.a16b);
             if (rc0 != XFK_OK) return rc0;
@@ -4263,7 +3930,7 @@ int Amg::build(hipStream_t s, int l0)
         k_amg_strength<<<nb_str(n), kB, 0, s>>>(n, A.ncol_lim, theta_at(l), A.rowptr,
                                                 ColView{A.col, A.has16 ? A.a16.p : nullptr, A.has16 ? A.a16b.p : nullptr},
                                                 A.val, absd.p, A.dinv.p, sflag.p, cnt.p,
-                                                dfinv.p, wF.p, rho_part.p, signed_strength());
+                                                dfinv.p, wF.p, rho_part.p);
         k_max_reduce<<<1, kMaxReduceT, 0, s>>>(nb_str(n), rho_part.p, omega, rho.p + 2 * l);
         if (g_prof) g_prof->end();
         if (trace) {   // (the P SpGEMM below reuses cnt)
@@ -4303,7 +3970,7 @@ int Amg::build(hipStream_t s, int l0)
         if (g_prof) g_prof->end();
         if (rc != XFK_OK) return rc;
         // folded level (l >= 1): P~ from A P before the next level reuses its buffers
-        A.fold = (fold_on < 0 ? fold_levels() : fold_on != 0) && sweeps == 1 && !A.dist;
+        A.fold = fold_on != 0 && sweeps == 1 && !A.dist;
         A.fold_formed = A.fold;
         if (A.fold) {
             if (g_prof) g_prof->begin(lv + "folded transfer P~ = (I - w D^-1 A) P, R~ = P~^T", 0.0);
@@ -4318,15 +3985,11 @@ int Amg::build(hipStream_t s, int l0)
             }
             // P~ and R~ on the side stream: only the V-cycle reads them; the
             // next level's A P (which reuses A P's buffers) waits for P~
-            const bool off = side_setup_on();
-            hipStream_t fs = s;
-            if (off) {
-                if ((rc = sw.init()) != XFK_OK) return rc;
-                AMG_CHECK(hipEventRecord(sw.a, s));
-                AMG_CHECK(hipStreamWaitEvent(sw.cs, sw.a, 0));
-                fs = sw.cs;
-                sw_used = true;
-            }
+            if ((rc = sw.init()) != XFK_OK) return rc;
+            AMG_CHECK(hipEventRecord(sw.a, s));
+            AMG_CHECK(hipStreamWaitEvent(sw.cs, sw.a, 0));
+            hipStream_t fs = sw.cs;
+            sw_used = true;
             if (n > 0)
                 k_fold_p<<<(int)(((long long)n * kFoldLanes + 255) / 256), 256, 0, fs>>>(
                     n, rho.p + 2 * l, A.dinv.p, A.ftrow.p, ap_col.p, ap_val.p, A.prow.p, A.pcol.p, A.pval.p, A.ftcol.p,
@@ -4335,14 +3998,12 @@ int Amg::build(hipStream_t s, int l0)
                 (rc = build_col16<kCgBlock>(fs, n, A.ftrow.p, A.ftcol.p, ap_nnz, A.f16, A.f16b)) != XFK_OK)
                 return rc;
             if (l == 0 && A.has32 && (rc = to_f32(fs, n, A.ftrow.p, ap_nnz, A.ftval.p, A.f32v)) != XFK_OK) return rc;
-            if (off) {
-                AMG_CHECK(hipEventRecord(sw.c, sw.cs));
-                fold_pending = true;
-            }
+            AMG_CHECK(hipEventRecord(sw.c, sw.cs));
+            fold_pending = true;
             // level 0 folds only its post-step (its pre-step keeps R r'): no R~
             if (l > 0)
-                rc = transpose_csr(off ? cnt2 : cnt, off ? cub_tmp2 : cub_tmp, fs, n, (int)nc, A.ftrow.p, A.ftcol.p,
-                                   A.ftval.p, A.frrow.p, A.frcol.p, A.frval.p);
+                rc = transpose_csr(cnt2, cub_tmp2, fs, n, (int)nc, A.ftrow.p, A.ftcol.p, A.ftval.p, A.frrow.p,
+                                   A.frcol.p, A.frval.p);
             if (rc != XFK_OK) return rc;
             // the exact length picks the V-cycle's lanes per row (and so the
             // summation order): from a deferred slot when A P's length is
@@ -4376,9 +4037,9 @@ int Amg::build(hipStream_t s, int l0)
         // with the deferred lengths), the inverse launched ahead of that read
         // stands -- otherwise (or on overflow) it is redone
         AmgLevel &C = *L[nlev - 1];
-        const bool nd_spec = dense_coarse && spec_on() && !g_prof && def_n > 0 && nlev - 1 > l0 &&
+        const bool nd_spec = dense_coarse && !g_prof && def_n > 0 && nlev - 1 > l0 &&
                              C.n >= 8 * kBj && nd_key_n == C.n && C.col == C.col_o.p &&
-                             (size_t)nd_key_nnz <= C.col_o.n && !std::getenv("XFK_NO_ND");
+                             (size_t)nd_key_nnz <= C.col_o.n && !env_set("XFK_NO_ND");
         if (nd_spec) {
             AMG_CHECK(mis_out.alloc(4));
             AMG_CHECK(hipMemsetAsync(mis_out.p + 3, 0, sizeof(int), s));
@@ -4406,7 +4067,7 @@ int Amg::build(hipStream_t s, int l0)
             return build(s, l0);
         }
         for (int k = l0; k < nlev; ++k) stats.nnz[k] = L[k]->nnz;
-        if (std::getenv("XFK_AMG_HINTS_PRINT")) {   // lab: the capacities / MIS rounds a setup measured
+        if (env_set("XFK_AMG_HINTS_PRINT")) {   // lab: the capacities / MIS rounds a setup measured
             std::fprintf(stderr, "[amg hints] levels %d:", nlev);
             for (auto &h : cap_hint) std::fprintf(stderr, " cap[%d.%d]=%d", h.first / 4, h.first % 4, h.second);
             for (auto &h : mis_hint) std::fprintf(stderr, " mis[%d]=%d", h.first, h.second);
@@ -4469,14 +4130,6 @@ int gather_host(Amg &M, xfk_comm *comm, hipStream_t s, const double *vals, int k
 
 }  // namespace
 
-// XFK_AMG_FOLD_DIST=0: sharded levels keep the unfolded post-step
-// (prolongation, halo exchange, sweep); read per setup
-static bool dist_fold_on()
-{
-    const char *e = std::getenv("XFK_AMG_FOLD_DIST");
-    return !(e && std::atoi(e) == 0);
-}
-
 // a folded sharded level 0: P~ in f32 with 16-bit columns in the V-cycle's
 // 512-row tiles (a tile reaching the halo columns may keep the int columns,
 // decided per tile), as the single-device level 0's
@@ -4496,6 +4149,7 @@ int Amg::setup_dist(hipStream_t s, xfk_comm *comm_, const HaloPlan &halo_, int n
 {
     dist = true;
     comm = comm_;
+    overlap = overlap_enabled();
     nranks = comm->size;
     rank = comm->rank;
     int rc = init(s);
@@ -4514,10 +4168,10 @@ int Amg::setup_dist(hipStream_t s, xfk_comm *comm_, const HaloPlan &halo_, int n
         // 16-bit tile columns of the owned rows (the overlapped PCG SpMV and the
         // level-0 sweeps read them; a boundary tile reaching the halo ids spans
         // more than 65535 columns and keeps the int columns, decided per tile)
-        A.has16 = col16 < 0 ? col16_on() : col16 != 0;
+        A.has16 = col16 != 0;
         if (A.has16 && (rc = build_col16<kCgBlock>(s, n, rowptr, col, nnz, A.a16, A.a16b)) != XFK_OK) return rc;
         // f32 restriction / prolongation (converted after the aggregation)
-        A.has32 = A.has16 && (prec32 < 0 ? f32_on() : prec32 != 0);
+        A.has32 = A.has16 && prec32 != 0;
     }
     for (int l = 0;; ++l) {
         AmgLevel &A = *L[l];
@@ -4533,16 +4187,14 @@ int Amg::setup_dist(hipStream_t s, xfk_comm *comm_, const HaloPlan &halo_, int n
         AMG_CHECK(rho_part.alloc(2 * (size_t)std::max(1, nb_str(nl))));
         k_amg_diag<<<nb(nl), kB, 0, s>>>(nl, A.rowptr, A.col, A.val, absd.p, A.dinv.p);
         k_amg_strength<<<nb_str(nl), kB, 0, s>>>(nl, nl, theta_at(l), A.rowptr, ColView{A.col, nullptr, nullptr}, A.val,
-                                                 absd.p, A.dinv.p, sflag.p, cnt.p, dfinv.p, wF.p, rho_part.p,
-                                                 signed_strength());
+                                                 absd.p, A.dinv.p, sflag.p, cnt.p, dfinv.p, wF.p, rho_part.p);
         k_max_reduce<<<1, kMaxReduceT, 0, s>>>(nb_str(nl), rho_part.p, omega, rho.p + 2 * l);
         long long nc = 0;
         rc = aggregate(s, l, nc, false);
         if (rc != XFK_OK && rc != XFK_ERR_UNSUPPORTED) return rc;
         // test hook: this rank reports an aggregation failure at level 0, so
         // every rank must agree on the Jacobi fallback through the collectives
-        if (const char *fr = std::getenv("XFK_TEST_AMG_FAIL_RANK"))
-            if (l == 0 && std::atoi(fr) == rank) rc = XFK_ERR_UNSUPPORTED;
+        if (l == 0 && env_int("XFK_TEST_AMG_FAIL_RANK", -1) == rank) rc = XFK_ERR_UNSUPPORTED;
         bool rep = false;
         if ((rc = galerkin_dist(s, l, rc == XFK_OK ? 0 : 1, rep)) != XFK_OK) return rc;
         if (rep) {
@@ -4742,7 +4394,7 @@ int Amg::galerkin_dist(hipStream_t s, int l, int st, bool &rep)
     //    replicated one: the global coarse vector every rank holds).
     const bool ok3 = rc == XFK_OK;
     A.fold = A.fold_formed =
-        ok3 && sweeps == 1 && dist_fold_on() && (fold_on < 0 ? fold_levels() : fold_on != 0);
+        ok3 && sweeps == 1 && fold_on != 0;
     if (A.fold) {
         A.fnnz = apnnz;
         AMG_CHECK(A.ftrow.alloc((size_t)n + 1));
@@ -4886,7 +4538,7 @@ int Amg::galerkin_dist(hipStream_t s, int l, int st, bool &rep)
     C.val = C.val_o.p;
     C.dist = false;
     C.plan = HaloPlan();
-    if (std::getenv("XFK_AMG_DEBUG") && rank == 0) {   // symmetry of the gathered A_1
+    if (env_set("XFK_AMG_DEBUG") && rank == 0) {   // symmetry of the gathered A_1
         std::vector<int> hr(NC + 1), hc(NNZ);
         std::vector<double> hv(NNZ);
         AMG_CHECK(hipMemcpyAsync(hr.data(), C.rowptr, sizeof(int) * (NC + 1), hipMemcpyDeviceToHost, s));
@@ -4937,16 +4589,9 @@ void launch_smooth_t(hipStream_t s, int l, const AmgLevel &A, const unsigned lon
     }
     if (l == 0) {
         const int g = tl ? nt : (A.n + kCgBlock - 1) / kCgBlock;
-        if (A.has32 && f32_sweep_on())
-            k_amg_smooth<MODE, kCgBlock><<<g, kCgBlock, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.a32.p,
-                                                                A.dinv.p, rho, b, x, out, rout, done, part_gam, tl,
-                                                                A.has16 ? A.a16.p : nullptr,
-                                                                A.has16 ? A.a16b.p : nullptr);
-        else
-            k_amg_smooth<MODE, kCgBlock><<<g, kCgBlock, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.val, A.dinv.p,
-                                                                rho, b, x, out, rout, done, part_gam, tl,
-                                                                A.has16 ? A.a16.p : nullptr,
-                                                                A.has16 ? A.a16b.p : nullptr);
+        k_amg_smooth<MODE, kCgBlock><<<g, kCgBlock, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.val, A.dinv.p, rho,
+                                                            b, x, out, rout, done, part_gam, tl,
+                                                            A.has16 ? A.a16.p : nullptr, A.has16 ? A.a16b.p : nullptr);
         return;
     }
     if (A.n >= kTileMinRows) {
@@ -5032,8 +4677,7 @@ int smooth_tile(int l, const AmgLevel &A) { return l == 0 ? kCgBlock : (A.n >= k
 // matrix stream, the gathered operand once, b / D^-1, the written vectors
 static double smooth_bytes(const AmgLevel &A, int mode)
 {
-    const double n = A.n, base = ((A.has16 ? 2.0 : 4.0) + (A.has32 && f32_sweep_on() ? 4.0 : 8.0)) * (double)A.nnz +
-                                 4.0 * (n + 1);
+    const double n = A.n, base = ((A.has16 ? 2.0 : 4.0) + 8.0) * (double)A.nnz + 4.0 * (n + 1);
     const bool implicit = mode == kSweepFromZero || mode == kResidFromZero;
     const double rd = (implicit ? 2.0 : 3.0) * 8.0 * n;
     const double wr = (mode == kResidFromZero && !A.fold ? 2.0 : 1.0) * 8.0 * n;
@@ -5183,7 +4827,7 @@ double *Amg::vc_dist(hipStream_t s, int l, const double *b, double *out, const i
     rc = XFK_OK;
     // tile levels: the halo exchange of the iterate overlaps the interior tiles
     const int B = smooth_tile(l, A);
-    const bool ov = B > 0 && overlap_enabled();
+    const bool ov = B > 0 && overlap;
     if (ov && !A.ts.ready()) {
         if ((rc = side.init()) != XFK_OK) return nullptr;
         if ((rc = build_tile_split(s, A.n, B, A.rowptr, A.col, A.ts)) != XFK_OK) return nullptr;
@@ -5333,14 +4977,12 @@ int Amg::tail_read(double &ms_cycle, int &cycles, double &ms_setup)
 // XFK_AMG_REFOLD=0: a Newton refresh runs level 0 unfolded (the former way)
 static bool refold_on()
 {
-    const char *e = std::getenv("XFK_AMG_REFOLD");   // (read per refresh: tests toggle it)
-    return !(e && std::atoi(e) == 0);
+    return env_int("XFK_AMG_REFOLD", 1) != 0;   // (read per refresh: tests toggle it)
 }
 
 static int refold_stage()
 {
-    const char *e = std::getenv("XFK_REFOLD_STAGE");   // (read per refresh: tests toggle it)
-    return (e && std::atoi(e) == 0) ? 0 : 1;
+    return env_int("XFK_REFOLD_STAGE", 1) != 0;   // (read per refresh: tests toggle it)
 }
 
 int Amg::refresh(hipStream_t s, bool fold)
@@ -5359,10 +5001,6 @@ int Amg::refresh(hipStream_t s, bool fold)
                                            ColView{A.col, A.has16 ? A.a16.p : nullptr, A.has16 ? A.a16b.p : nullptr},
                                            A.val, rho_part.p, absd.p, A.dinv.p);
         k_max_reduce<<<1, kMaxReduceT, 0, s>>>(nb_str(n), rho_part.p, omega, rho.p);
-    }
-    if (A.has32 && f32_sweep_on()) {   // the sweeps' f32 copy of the new values
-        int rc = to_f32(s, n, A.rowptr, A.nnz, A.val, A.a32);
-        if (rc != XFK_OK) return rc;
     }
     if (refold && n > 0) {   // P~ = (I - w D^-1 A_new) P over its own pattern (new D^-1 and rho above)
         if (A.has32) AMG_CHECK(A.f32v.alloc((size_t)std::max(1LL, A.fnnz)));   // (the setup's copy: same pattern)

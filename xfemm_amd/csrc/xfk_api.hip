@@ -36,7 +36,7 @@
 namespace {
 // XFK_TRACE_CREATE=1: host milliseconds of each problem-creation stage on stderr
 struct CreateTrace {
-    bool on = std::getenv("XFK_TRACE_CREATE") != nullptr;
+    bool on = xfk::env_set("XFK_TRACE_CREATE");
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
     void mark(const char *what)
     {
@@ -74,13 +74,7 @@ long long now_ns()
 // destroy path knows the device no longer reads the block.
 namespace {
 // cap: XFK_POOL_CAP_MB (default 64 GiB; 0 keeps nothing), read once
-size_t env_mb(const char *name, size_t dflt)
-{
-    const char *v = std::getenv(name);
-    if (!v || !*v) return dflt;
-    return (size_t)std::strtoull(v, nullptr, 10) << 20;
-}
-const size_t kPoolCap = env_mb("XFK_POOL_CAP_MB", 64ull << 30);
+const size_t kPoolCap = (size_t)env_int("XFK_POOL_CAP_MB", 64 << 10) << 20;
 struct BlockPool {
     std::mutex mu;
     std::map<std::pair<int, size_t>, std::vector<void *>> free;
@@ -290,7 +284,7 @@ void dev_free(void *p)
 // destroyed, for the next problem of the process.  Size classes as above; at
 // most kPinCap bytes stay cached.
 namespace {
-const size_t kPinCap = env_mb("XFK_PIN_CAP_MB", 1ull << 30);   // (XFK_PIN_CAP_MB, default 1 GiB)
+const size_t kPinCap = (size_t)env_int("XFK_PIN_CAP_MB", 1 << 10) << 20;   // (default 1 GiB), read once
 struct PinPool {
     std::mutex mu;
     std::map<size_t, std::vector<void *>> free;
@@ -731,7 +725,7 @@ struct SymTmp {
     // zero-initialised block (one memset)
     int *deg, *cursor, *cnt, *hist;
     // uninitialised
-    int *rowcnt, *keys_out, *iota, *flag, *iperm, *rowtmp, *slot_val, *slot_key;
+    int *rowcnt, *keys_out, *iota, *flag, *iperm, *rowtmp;
     unsigned char *active;
     unsigned long long *maxkey, *used;
     size_t zero_bytes = 0, bytes = 0;
@@ -758,8 +752,6 @@ struct SymTmp {
         take(maxkey, N);
         take(used, 2 * (size_t)N);
         take(iperm, NE);
-        take(slot_val, 3 * (size_t)NE);
-        take(slot_key, 3 * (size_t)NE);
         take(rowtmp, (size_t)row_tmp_size(N, NE, nfill));
         bytes = off;
     }
@@ -796,32 +788,11 @@ int build_symbolic(xfk_problem *P)
     XFK_CHECK(P->n2e_ptr.alloc(NL + 1));
     XFK_CHECK(P->n2e.alloc(3 * (size_t)NE));
     // counts, scan, fill, per-node register sort (xfk_device.hip k_n2e_*):
-    // each node's elements ascending (the reference's AddTo order);
-    // XFK_N2E_RADIX=1: the stable radix sort of the element-major incidence
-    // slots by node instead (same lists)
-    static const bool n2e_radix = [] {
-        const char *e = std::getenv("XFK_N2E_RADIX");
-        return e && std::atoi(e) != 0;
-    }();
-    if (!n2e_radix) {
-        launch_n2e_count(s, NE, P->p_raw.p, T.deg);
-        XFK_CHECK(exclusive_scan(P, T.deg, P->n2e_ptr.p, NL));
-        launch_n2e_fill(s, NE, P->p_raw.p, P->n2e_ptr.p, T.cursor, P->n2e.p);
-        launch_n2e_sort(s, N, NL, P->n2e_ptr.p, P->n2e.p);   // rows < N: sorted by the row-length pass
-    } else {
-        launch_slot_elements(s, NE, T.slot_val);
-        int bits = 1;
-        while (bits < 31 && (1LL << bits) <= NL) ++bits;
-        void *tmp = nullptr;
-        size_t bytes = 0;
-        const int n3 = 3 * NE;
-        XFK_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, P->p_raw.p, T.slot_key, T.slot_val, P->n2e.p, n3, 0,
-                                                     bits, s));
-        XFK_CHECK(cub_scratch(P, bytes, &tmp));
-        XFK_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, P->p_raw.p, T.slot_key, T.slot_val, P->n2e.p, n3, 0,
-                                                     bits, s));
-        launch_n2e_ptr(s, NL, T.slot_key, n3, P->n2e_ptr.p);
-    }
+    // each node's elements ascending (the reference's AddTo order)
+    launch_n2e_count(s, NE, P->p_raw.p, T.deg);
+    XFK_CHECK(exclusive_scan(P, T.deg, P->n2e_ptr.p, NL));
+    launch_n2e_fill(s, NE, P->p_raw.p, P->n2e_ptr.p, T.cursor, P->n2e.p);
+    launch_n2e_sort(s, N, NL, P->n2e_ptr.p, P->n2e.p);   // rows < N: sorted by the row-length pass
 
     // periodic fill-in entries, CSR by row
     const int *fp = nullptr, *fc = nullptr;
@@ -847,7 +818,7 @@ int build_symbolic(xfk_problem *P)
 
     // CSR pattern
     XFK_CHECK(P->rowptr.alloc(N + 1));
-    launch_row_build(s, N, P->p_raw.p, P->n2e_ptr.p, P->n2e.p, fp, fc, T.rowtmp, T.rowcnt, n2e_radix ? nullptr : P->n2e.p);
+    launch_row_build(s, N, P->p_raw.p, P->n2e_ptr.p, P->n2e.p, fp, fc, T.rowtmp, T.rowcnt, P->n2e.p);
     XFK_CHECK(exclusive_scan(P, T.rowcnt, P->rowptr.p, N));
     XFK_CHECK(hipMemcpyAsync(P->hpin, P->rowptr.p + N, sizeof(int), hipMemcpyDeviceToHost, s));
     XFK_CHECK(hipMemcpyAsync(P->hpin + 1, P->rowptr.p + P->N, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1164,8 +1135,7 @@ static int assemble(xfk_problem *P, int iter)
     A.mu2_out = P->any_nonlinear ? P->mu2b.p : nullptr;
     A.miss = P->asm_miss.p;
     // (XFK_ASM_STATE=0: the Newton state evaluated per row, as before -- measurement / the test)
-    const char *st = std::getenv("XFK_ASM_STATE");
-    const bool pre = P->any_nonlinear && !P->axi && P->dv_el.p && !(st && std::atoi(st) == 0);
+    const bool pre = P->any_nonlinear && !P->axi && P->dv_el.p && env_int("XFK_ASM_STATE", 1) != 0;
     A.dv_el = pre ? P->dv_el.p : nullptr;
     A.on_el = pre ? P->on_el.p : nullptr;
     A.n_el = P->NE;
@@ -1277,13 +1247,9 @@ static int allreduce_partials(xfk_problem *P, int narrays)
     return P->comm->allreduce_sum(P->part_loc.p, P->part_glob, (size_t)narrays * P->Gpart, P->stream);
 }
 
-static bool trace_newton() { return std::getenv("XFK_TRACE_NEWTON") != nullptr; }
+static bool trace_newton() { return env_set("XFK_TRACE_NEWTON"); }
 // XFK_NEWTON_INEXACT=0 turns the inexact Newton passes off (XFK_OPT_NEWTON_INEXACT)
-static bool newton_inexact_env()
-{
-    const char *e = std::getenv("XFK_NEWTON_INEXACT");
-    return !(e && e[0] == '0');
-}
+static bool newton_inexact_env() { return env_int("XFK_NEWTON_INEXACT", 1) != 0; }
 
 // a Newton refresh re-forms level 0's P~ (~0.32 ms on configs[3]) when the
 // last pass ran at least this many PCG iterations, else level 0 runs
@@ -1309,8 +1275,7 @@ static int amg_setup(xfk_problem *P)
         // level 0 stays folded when the pass is expected to run long enough to
         // repay re-forming P~ (k_refold_p): the last pass's count as the guess
         // (XFK_REFOLD_MIN: that threshold)
-        const char *rm = std::getenv("XFK_REFOLD_MIN");   // (read per refresh: tests set it)
-        const int refold_min = rm ? std::atoi(rm) : kRefoldMinIters;
+        const int refold_min = (int)env_int("XFK_REFOLD_MIN", kRefoldMinIters);   // (read per refresh: tests set it)
         int rc = P->amg->refresh(s, P->amg_last_iters >= refold_min);
         if (rc != XFK_OK) return rc;
         P->pc_used = XFK_PRECOND_AMG;
@@ -1392,6 +1357,7 @@ static int pcg_start(xfk_problem *P, int flag)
     P->pcg_host->tol = tol;
     P->pcg_host->tol_rel = P->pcg_tol_rel;
     launch_cg_state_init(s, P->pcg.p, tol, P->pcg_tol_rel);
+    P->overlap = P->comm && P->comm->size > 1 && overlap_enabled();
     if (P->comm) XFK_CHECK(hipMemsetAsync(P->part_loc.p, 0, sizeof(double) * 4 * P->Gpart, s));
     launch_diag_inv(s, N, P->diag.p, P->val.p, P->dinv.p, P->pcg.p);
     int rc = XFK_OK;
@@ -1461,7 +1427,7 @@ static int pcg_precond_spmv(xfk_problem *P, long long it, bool stamp)
     const double *Rg = A.amg && gam ? A.R : nullptr;
     double *pg = A.amg && gam ? pgam : nullptr;
     const CgState *St = P->pcg.p;
-    if (P->comm && P->comm->size > 1 && overlap_enabled()) {
+    if (P->overlap) {
         // sharded: the halo of u travels on the side stream while the tiles
         // without halo columns multiply (bit-identical to the single launch)
         if (!P->ts.ready()) {
@@ -1606,7 +1572,7 @@ static int pcg_solve_once(xfk_problem *P, int flag, long long max_iters)
             return XFK_ERR_NOCONV;
         }
         // (S is the same on every rank: the decision is collective-safe)
-        const bool force = std::getenv("XFK_TEST_F64_FALLBACK") != nullptr;   // test hook (read per poll)
+        const bool force = env_set("XFK_TEST_F64_FALLBACK");   // test hook (read per poll)
         if (P->pc_used == XFK_PRECOND_AMG && P->amg && P->amg->f32_active() &&
             (force || !std::isfinite(S.er) || (S.iters >= kF32Guard && S.er > 1e-4)))
             return kRetryF64;
@@ -2043,7 +2009,7 @@ void prepare_global(const xfk_problem_desc *d, GlobalPrep &G)
         o.bh_off = (int)G.hB.size();
         // (XFK_BH_SCAN: the reference's knot scan for every table -- the test
         // that the bisection finds the same intervals)
-        o.bh_sorted = std::getenv("XFK_BH_SCAN") ? 0 : 1;
+        o.bh_sorted = env_set("XFK_BH_SCAN") ? 0 : 1;
         for (int i = 0; i < b.BHpoints; ++i) {
             if (i > 0 && !(b.B[i] >= b.B[i - 1])) o.bh_sorted = 0;
             G.hB.push_back(b.B[i]);
@@ -2228,11 +2194,6 @@ int build_local(const xfk_problem_desc *d, const GlobalPrep &G, const PartPlan *
     xfk_problem *P = new xfk_problem();
     ArenaScope arena_scope(&P->arena);
     P->device = device;
-    if (std::getenv("XFK_SPIN_WAIT")) {   // experiment: host waits spin instead of yielding
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) e = hipSetDeviceFlags(hipDeviceScheduleSpin);
-        std::fprintf(stderr, "[xfk] hipDeviceScheduleSpin: %s\n", hipGetErrorString(e));
-    }
     if (hipSetDevice(device) != hipSuccess || stream_acquire(&P->stream) != hipSuccess) {
         set_error("cannot initialise the HIP device/stream");
         delete P;
@@ -2456,7 +2417,7 @@ int build_local(const xfk_problem_desc *d, const GlobalPrep &G, const PartPlan *
 // hipMalloc (16 calls, 0.34 ms of a configs[2] first solve): 4.32 GB of chunks
 // at 1.0M rows (configs[2]), 0.50 GB at 103k rows (tools/lab/mem_probe.py,
 // profiles/r05t_mem_probe.txt) -- ~4.4 kB per owned row.  A larger solve takes
-// further chunks as before.  XFK_ARENA_RESERVE=0: no reservation.
+// further chunks as before.
 // The reservation is only a speed-up: it is skipped when it would take more
 // than half of the device's free memory, and a failed one is dropped (the
 // HIP error cleared) -- creation never fails on it, so the ranks of a sharded
@@ -2464,11 +2425,8 @@ int build_local(const xfk_problem_desc *d, const GlobalPrep &G, const PartPlan *
 int reserve_first_solve(xfk_problem **out)
 {
     xfk_problem *P = *out;
-    static const long long per_row = [] {
-        const char *e = std::getenv("XFK_ARENA_RESERVE");
-        return e ? std::atoll(e) : 4400LL;
-    }();
-    if (!P || per_row <= 0) return XFK_OK;
+    constexpr long long per_row = 4400;
+    if (!P) return XFK_OK;
     XFK_CHECK(hipSetDevice(P->device));
     const size_t bytes = (size_t)per_row * (size_t)std::max(0, P->N) + (64ull << 20);
     size_t free_b = 0, total_b = 0;
@@ -2732,8 +2690,7 @@ int static2d_run(xfk_problem *P, int flags, xfk_result *res)
         // has neither)
         if (!LinearFlag) XFK_CHECK(hipMemcpyAsync(P->Vold.p, P->V.p, sizeof(double) * N, hipMemcpyDeviceToDevice, s));
         XFK_CHECK(hipEventRecord(e1, s));
-        static const bool nws_poll = !std::getenv("XFK_NWS_AT_POLL") || std::atoi(std::getenv("XFK_NWS_AT_POLL")) != 0;
-        P->nws_at_poll = nws_poll && !LinearFlag && !P->comm;
+        P->nws_at_poll = !LinearFlag && !P->comm;
         rc = pcg_solve(P, Iter, cap);
         P->nws_at_poll = false;
         if (rc != XFK_OK) return rc;
@@ -3291,44 +3248,6 @@ int xfk_pcg_time(xfk_problem *P, int iters, double *ms_spmv, double *ms_iter)
     ScopedEvents<2> ev;
     XFK_CHECK(ev.create());
     hipEvent_t t0 = ev[0], t1 = ev[1];
-    if (const char *ge = std::getenv("XFK_PCG_GRAPH")) {
-        // lab: the same iterations launched one by one vs replayed from a
-        // hipGraph of K captured iterations (no events inside); ms_spmv gets
-        // the stream time per iteration, ms_iter the graph time per iteration
-        const int K = std::max(2, std::atoi(ge) & ~1);
-        for (int k = 0; k < 2; ++k)
-            if ((rc = pcg_iteration(P, k, false)) != XFK_OK) return rc;
-        XFK_CHECK(hipEventRecord(t0, s));
-        for (int k = 2; k < 2 + iters; ++k)
-            if ((rc = pcg_iteration(P, k, false)) != XFK_OK) return rc;
-        XFK_CHECK(hipEventRecord(t1, s));
-        XFK_CHECK(hipEventSynchronize(t1));
-        float ts = 0;
-        XFK_CHECK(hipEventElapsedTime(&ts, t0, t1));
-        hipGraph_t g = nullptr;
-        hipGraphExec_t ge2 = nullptr;
-        XFK_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        for (int k = 2; k < 2 + K; ++k)
-            if ((rc = pcg_iteration(P, k, false)) != XFK_OK) {
-                (void)hipStreamEndCapture(s, &g);
-                return rc;
-            }
-        XFK_CHECK(hipStreamEndCapture(s, &g));
-        XFK_CHECK(hipGraphInstantiate(&ge2, g, nullptr, nullptr, 0));
-        XFK_CHECK(hipGraphLaunch(ge2, s));   // warm
-        const int R = std::max(1, iters / K);
-        XFK_CHECK(hipEventRecord(t0, s));
-        for (int q = 0; q < R; ++q) XFK_CHECK(hipGraphLaunch(ge2, s));
-        XFK_CHECK(hipEventRecord(t1, s));
-        XFK_CHECK(hipEventSynchronize(t1));
-        float tg = 0;
-        XFK_CHECK(hipEventElapsedTime(&tg, t0, t1));
-        (void)hipGraphExecDestroy(ge2);
-        (void)hipGraphDestroy(g);
-        if (ms_spmv) *ms_spmv = ts / iters;
-        if (ms_iter) *ms_iter = tg / (R * K);
-        return XFK_OK;
-    }
     P->spmv_used = 0;
     XFK_CHECK(hipEventRecord(t0, s));
     for (int k = 0; k < iters; ++k) {

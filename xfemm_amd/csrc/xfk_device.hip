@@ -107,25 +107,9 @@ __global__ void k_fill_n2e(int NE, const int *__restrict__ p, const int *__restr
 // Node -> element lists by counting: per-node counts (atomic increments, order-
 // free), an exclusive scan, a fill at atomically taken positions (arbitrary
 // order within a node's list), then every node's short list sorted in
-// registers -- each node's elements come out ascending, the order the radix
-// sort below produced (the reference's AddTo order), in ~1/3 of its time
-// (three 8-bit passes over 3 NE pairs)
-__global__ void k_n2e_count(long long n3, const int *__restrict__ p, int *__restrict__ deg)
-{
-    const long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (k < n3) atomicAdd(&deg[p[k]], 1);
-}
-
-__global__ void k_n2e_fill(long long n3, const int *__restrict__ p, const int *__restrict__ ptr,
-                           int *__restrict__ cursor, int *__restrict__ n2e)
-{
-    const long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (k >= n3) return;
-    const int v = p[k];
-    n2e[ptr[v] + atomicAdd(&cursor[v], 1)] = (int)(k / 3);
-}
-
-// The same counts and fill through LDS: a workgroup of 256 elements touches
+// registers -- each node's elements come out ascending (the reference's AddTo
+// order).
+// The counts and the fill go through LDS: a workgroup of 256 elements touches
 // the nodes of a narrow window (element and node numberings are both banded),
 // counts its incidences there and touches the global counters once per
 // (workgroup, node) instead of once per incidence; the fill reserves one
@@ -249,29 +233,6 @@ __global__ void k_n2e_sort(int v0, int NL, const int *__restrict__ ptr, int *__r
     sort_node_list(ptr[v], ptr[v + 1], n2e);
 }
 
-// Node -> element lists by a stable radix sort of the (node, element)
-// incidence pairs (xfk_api.hip: build_symbolic): values k / 3 of the
-// element-major incidence slots, then each node's first slot by a lower
-// bound in the sorted keys (nodes of no element get an empty range)
-__global__ void k_slot_elements(long long n3, int *__restrict__ v)
-{
-    const long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (k < n3) v[k] = (int)(k / 3);
-}
-
-__global__ void k_n2e_ptr(int NL, const int *__restrict__ keys, int n3, int *__restrict__ ptr)
-{
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n > NL) return;
-    int lo = 0, hi = n3;   // first slot with key >= n
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < n) lo = mid + 1;
-        else hi = mid;
-    }
-    ptr[n] = lo;
-}
-
 // Deterministic order of each node's element list (insertion sort, lists are short).
 __global__ void k_sort_segments(int N, const int *__restrict__ ptr, int *__restrict__ a)
 {
@@ -290,11 +251,11 @@ __global__ void k_sort_segments(int N, const int *__restrict__ ptr, int *__restr
 }
 
 // CSR row v = sorted unique {vertices of the elements incident to v} u
-// {periodic fill-in columns of v} u {v}.  One thread per row gathers its
-// candidates into LDS (or, for rows with more than kRowLds candidates, into
-// its own region of `tmp`), sorts and de-duplicates them there, and leaves the
-// row at tmp[cand_base(v)]; k_row_copy moves it to its CSR place after the
-// row-length scan.
+// {periodic fill-in columns of v} u {v}.  Long or periodic rows: one thread
+// gathers the row's candidates into LDS (or, for rows with more than kRowLds
+// candidates, into its own region of `tmp`), sorts and de-duplicates them
+// there, and leaves the row at tmp[rc.base(v)] (k_row_len_reg);
+// k_row_fill_reg moves it to its CSR place after the row-length scan.
 constexpr int kRowLds = 32;
 
 struct RowCands {
@@ -311,50 +272,12 @@ struct RowCands {
     }
 };
 
-__global__ void __launch_bounds__(kBlock) k_row_build(int N, RowCands rc, int *__restrict__ tmp,
-                                                      int *__restrict__ rowcnt)
-{
-    __shared__ int s_c[kBlock * (kRowLds + 1)];
-    const int v = blockIdx.x * kBlock + threadIdx.x;
-    if (v >= N) return;
-    const int m = rc.count(v);
-    int *out = tmp + rc.base(v);
-    int *c = (m <= kRowLds) ? &s_c[threadIdx.x * (kRowLds + 1)] : out;
-    int k = 0;
-    const int t1 = rc.n2e_ptr[v + 1];
-    for (int t = rc.n2e_ptr[v]; t < t1; ++t) {
-        const int f = rc.n2e[t];
-        c[k++] = rc.p[3 * f];
-        c[k++] = rc.p[3 * f + 1];
-        c[k++] = rc.p[3 * f + 2];
-    }
-    if (rc.fill_ptr)
-        for (int t = rc.fill_ptr[v]; t < rc.fill_ptr[v + 1]; ++t) c[k++] = rc.fill_col[t];
-    c[k++] = v;
-    // insertion sort, then unique
-    for (int i = 1; i < m; ++i) {
-        const int key = c[i];
-        int j = i - 1;
-        while (j >= 0 && c[j] > key) {
-            c[j + 1] = c[j];
-            --j;
-        }
-        c[j + 1] = key;
-    }
-    int u = 0;
-    for (int i = 0; i < m; ++i)
-        if (u == 0 || c[i] != c[u - 1]) c[u++] = c[i];
-    if (c != out)
-        for (int i = 0; i < u; ++i) out[i] = c[i];
-    rowcnt[v] = u;
-}
-
 // Rows of up to kRowRegElems incident elements and no periodic fill-in (all
 // but a few rows of a triangle mesh): the candidates -- v and the two other
 // vertices of each incident element -- are sorted by a register bitonic
 // network of 16 or 32 and de-duplicated there, twice: once for the row
 // length, once (after the scan) writing the row in place.  No temporary rows,
-// no copy pass.  Other rows take k_row_build / k_row_copy's path through tmp.
+// no copy pass.  Other rows take the path through tmp.
 constexpr int kRowRegElems = 15;
 
 template <int W>
@@ -449,7 +372,7 @@ __global__ void __launch_bounds__(kBlock) k_row_len_reg(int N, RowCands rc, int 
         rowcnt[v] = ne <= 7 ? row_regs_len<16>(v, s, ne, rc) : row_regs_len<32>(v, s, ne, rc);
         return;
     }
-    // long or periodic rows: candidates through LDS / tmp (k_row_build)
+    // long or periodic rows: candidates through LDS / tmp
     const int m = rc.count(v);
     int *out = tmp + rc.base(v);
     int *c = (m <= kRowLds) ? &s_c[threadIdx.x * (kRowLds + 1)] : out;
@@ -494,20 +417,6 @@ __global__ void k_row_fill_reg(int N, RowCands rc, const int *__restrict__ tmp, 
     }
     const int *src = tmp + rc.base(v);
     const int len = rowptr[v + 1] - r0;
-    for (int i = 0; i < len; ++i) {
-        const int c = src[i];
-        col[r0 + i] = c;
-        if (c == v) diag[v] = r0 + i;
-    }
-}
-
-__global__ void k_row_copy(int N, RowCands rc, const int *__restrict__ tmp, const int *__restrict__ rowptr,
-                           int *__restrict__ col, int *__restrict__ diag)
-{
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= N) return;
-    const int *src = tmp + rc.base(v);
-    const int r0 = rowptr[v], len = rowptr[v + 1] - r0;
     for (int i = 0; i < len; ++i) {
         const int c = src[i];
         col[r0 + i] = c;
@@ -1077,16 +986,16 @@ __device__ __forceinline__ void planar_element(int eb, const AssembleArgs &A, co
 constexpr int kRowBlock = 128;
 constexpr int kRowAcc = 12;
 
-// XCD: consecutive row blocks on one XCD (xcd_tile), so the coordinates and
+// consecutive row blocks on one XCD (xcd_tile), so the coordinates and
 // element data a block shares with the blocks a mesh row away stay in that
 // XCD's L2 (round-robin blocks fetched them once per XCD: 470 MB of HBM
 // traffic per launch for ~100 MB of algorithmic bytes on configs[2])
-template <bool AXI, bool FIRST, bool XCD, bool PRE>
+template <bool AXI, bool FIRST, bool PRE>
 __device__ __forceinline__ void assemble_rows(int N, const AssembleArgs &A)
 {
     __shared__ double s_acc[kRowAcc * kRowBlock];
     __shared__ int s_col[kRowAcc * kRowBlock];
-    const int i0 = (XCD ? xcd_tile(blockIdx.x, gridDim.x) : (int)blockIdx.x) * kRowBlock;
+    const int i0 = xcd_tile(blockIdx.x, gridDim.x) * kRowBlock;
     const int i = i0 + threadIdx.x;
     const bool live = i < N;   // (every thread reaches the barriers below)
     const int rs = live ? A.rowptr[i] : 0, L = live ? A.rowptr[i + 1] - rs : 0;
@@ -1160,17 +1069,17 @@ __device__ __forceinline__ void assemble_rows(int N, const AssembleArgs &A)
     if (live) A.b[i] = bi;
 }
 
-template <bool AXI, bool FIRST, bool XCD = true>
+template <bool AXI, bool FIRST>
 __global__ void __launch_bounds__(kRowBlock) k_assemble_rows(int N, AssembleArgs A)
 {
-    assemble_rows<AXI, FIRST, XCD, false>(N, A);
+    assemble_rows<AXI, FIRST, false>(N, A);
 }
 
 // the planar Newton pass after k_planar_state: 4 waves per SIMD (132 VGPRs
 // unbounded, 3 waves)
 __global__ void __launch_bounds__(kRowBlock, 4) k_assemble_rows_pre(int N, AssembleArgs A)
 {
-    assemble_rows<false, false, true, true>(N, A);
+    assemble_rows<false, false, true>(N, A);
 }
 
 // A planar Newton pass: each element's new state once (planar_newton_state),
@@ -1374,68 +1283,34 @@ void launch_fill_n2e(hipStream_t s, int NE, const int *p, const int *ptr, int *c
 {
     if (NE) k_fill_n2e<<<nblk(NE), kBlock, 0, s>>>(NE, p, ptr, cursor, n2e);
 }
-// XFK_N2E_TILE=0: one global atomic per incidence (measurement)
-static bool n2e_tile_on()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_N2E_TILE");
-        return !(e && std::atoi(e) == 0);
-    }();
-    return v;
-}
 void launch_n2e_count(hipStream_t s, int NE, const int *p, int *deg)
 {
-    const long long n3 = 3LL * NE;
-    if (NE && n2e_tile_on()) k_n2e_tile<false><<<(NE + 255) / 256, 256, 0, s>>>(NE, p, nullptr, deg, nullptr);
-    else if (NE) k_n2e_count<<<(unsigned)((n3 + kBlock - 1) / kBlock), kBlock, 0, s>>>(n3, p, deg);
+    if (NE) k_n2e_tile<false><<<(NE + 255) / 256, 256, 0, s>>>(NE, p, nullptr, deg, nullptr);
 }
 void launch_n2e_fill(hipStream_t s, int NE, const int *p, const int *ptr, int *cursor, int *n2e)
 {
-    const long long n3 = 3LL * NE;
-    if (NE && n2e_tile_on()) k_n2e_tile<true><<<(NE + 255) / 256, 256, 0, s>>>(NE, p, ptr, cursor, n2e);
-    else if (NE) k_n2e_fill<<<(unsigned)((n3 + kBlock - 1) / kBlock), kBlock, 0, s>>>(n3, p, ptr, cursor, n2e);
+    if (NE) k_n2e_tile<true><<<(NE + 255) / 256, 256, 0, s>>>(NE, p, ptr, cursor, n2e);
 }
 void launch_n2e_sort(hipStream_t s, int v0, int NL, const int *ptr, int *n2e)
 {
     if (NL > v0) k_n2e_sort<<<nblk(NL - v0), kBlock, 0, s>>>(v0, NL, ptr, n2e);
 }
-void launch_slot_elements(hipStream_t s, int NE, int *v)
-{
-    const long long n3 = 3LL * NE;
-    if (NE) k_slot_elements<<<(unsigned)((n3 + kBlock - 1) / kBlock), kBlock, 0, s>>>(n3, v);
-}
-void launch_n2e_ptr(hipStream_t s, int NL, const int *keys, int n3, int *ptr)
-{
-    k_n2e_ptr<<<nblk(NL + 1), kBlock, 0, s>>>(NL, keys, n3, ptr);
-}
 void launch_sort_segments(hipStream_t s, int N, const int *ptr, int *a)
 {
     if (N) k_sort_segments<<<nblk(N), kBlock, 0, s>>>(N, ptr, a);
-}
-// XFK_ROW_REG=0: every CSR row through k_row_build / k_row_copy (measurement)
-static bool row_reg_on()
-{
-    static const bool v = [] {
-        const char *e = std::getenv("XFK_ROW_REG");
-        return !(e && std::atoi(e) == 0);
-    }();
-    return v;
 }
 long long row_tmp_size(int N, int NE, int nfill) { return 9LL * NE + nfill + N; }
 void launch_row_build(hipStream_t s, int N, const int *p, const int *n2e_ptr, const int *n2e, const int *fill_ptr,
                       const int *fill_col, int *tmp, int *rowcnt, int *n2e_sort)
 {
-    if (n2e_sort && !row_reg_on()) launch_n2e_sort(s, 0, N, n2e_ptr, n2e_sort);   // (the LDS path sorts nothing)
     RowCands rc{p, n2e_ptr, n2e, fill_ptr, fill_col};
-    if (N && row_reg_on()) k_row_len_reg<<<nblk(N), kBlock, 0, s>>>(N, rc, tmp, rowcnt, n2e_sort);
-    else if (N) k_row_build<<<nblk(N), kBlock, 0, s>>>(N, rc, tmp, rowcnt);
+    if (N) k_row_len_reg<<<nblk(N), kBlock, 0, s>>>(N, rc, tmp, rowcnt, n2e_sort);
 }
 void launch_row_copy(hipStream_t s, int N, const int *p, const int *n2e_ptr, const int *n2e, const int *fill_ptr,
                      const int *fill_col, const int *tmp, const int *rowptr, int *col, int *diag)
 {
     RowCands rc{p, n2e_ptr, n2e, fill_ptr, fill_col};
-    if (N && row_reg_on()) k_row_fill_reg<<<nblk(N), kBlock, 0, s>>>(N, rc, tmp, rowptr, col, diag);
-    else if (N) k_row_copy<<<nblk(N), kBlock, 0, s>>>(N, rc, tmp, rowptr, col, diag);
+    if (N) k_row_fill_reg<<<nblk(N), kBlock, 0, s>>>(N, rc, tmp, rowptr, col, diag);
 }
 void launch_jp_round(hipStream_t s, int N, int NE, int round, unsigned char *active, int *pending_round,
                      const int *p, const int *n2e_ptr, const int *n2e, int *color, unsigned long long *maxkey,
@@ -1479,16 +1354,6 @@ void launch_assemble_rows(hipStream_t s, int N, const AssembleArgs &A)
 {
     if (N <= 0) return;
     const int g = (N + kRowBlock - 1) / kRowBlock;
-    // XFK_ASM_XCD=0: round-robin row blocks (measurement)
-    static const bool xcd = [] {
-        const char *e = std::getenv("XFK_ASM_XCD");
-        return !(e && std::atoi(e) == 0);
-    }();
-    if (!xcd && !A.axi) {
-        if (A.iter == 0) k_assemble_rows<false, true, false><<<g, kRowBlock, 0, s>>>(N, A);
-        else k_assemble_rows<false, false, false><<<g, kRowBlock, 0, s>>>(N, A);
-        return;
-    }
     if (A.axi) {
         if (A.iter == 0) k_assemble_rows<true, true><<<g, kRowBlock, 0, s>>>(N, A);
         else k_assemble_rows<true, false><<<g, kRowBlock, 0, s>>>(N, A);

@@ -1654,7 +1654,7 @@ static int harmonic2d_run(xfk_problem *P, int flags, xfk_result *res)
     // Newton AC solver: auxiliary matrices from the second pass on (the
     // reference's bNewton, set by the first auxiliary Put)
     const bool ac1 = nonlin && P->ac_solver == 1;
-    const bool trace = std::getenv("XFK_TRACE_NONLINEAR") != nullptr;
+    const bool trace = env_set("XFK_TRACE_NONLINEAR");
     if (nonlin) {
         XFK_CHECK(P->hV_old.alloc((size_t)N));
         XFK_CHECK(P->hres_part.alloc(3 * kResGrid));

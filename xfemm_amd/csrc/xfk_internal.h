@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -78,6 +79,17 @@ struct ScopedEvents {
     } while (0)
 
 void set_error(const std::string &msg);
+
+// Environment switches (the table in DESIGN.md, "Environment switches", lists
+// every name).  Both read the environment on every call, so a test may toggle
+// a switch in-process; callers read them per problem, setup or solve, never
+// per iteration.
+inline bool env_set(const char *name) { return std::getenv(name) != nullptr; }
+inline long long env_int(const char *name, long long dflt)
+{
+    const char *v = std::getenv(name);
+    return v && *v ? std::strtoll(v, nullptr, 10) : dflt;
+}
 
 // Per-block material parameters, as read by Static2D (CMSolverMaterialProp).
 struct DevBlock {
@@ -381,6 +393,7 @@ struct xfk_problem {
     xfk::HaloPlan halo2;             // the same for interleaved complex (double2) node vectors
     int Gpart = 0;                   // length of each per-block partial array (agreed by all ranks)
     xfk::TileSplit ts;               // sharded PCG SpMV: interior / boundary tiles (exchange overlap)
+    bool overlap = false;            // ... when XFK_OVERLAP=1 (read per solve, pcg_start)
     int *hpin = nullptr;             // pinned scratch for small device -> host reads
     hipEvent_t nnz_ev = nullptr;     // the pattern's lengths landed in hpin[0..1] (deferred read)
     bool nnz_pending = false;        // nnz / nnz_own not read back yet (xfk_resolve_nnz)
@@ -512,10 +525,10 @@ struct xfk_problem {
     double amg_omega = 1.75;
     int amg_replicate = 250000;
     int amg_dense = 2048;
-    int amg_fold = -1;                // XFK_OPT_AMG_FOLD (-1: the XFK_AMG_FOLD environment default)
-    int amg_col16 = -1;               // XFK_OPT_AMG_COL16 (-1: on unless XFK_NO_COL16)
+    int amg_fold = 1;                 // XFK_OPT_AMG_FOLD
+    int amg_col16 = 1;                // XFK_OPT_AMG_COL16
     int amg_wlevel = -2;              // XFK_OPT_AMG_WLEVEL (-2: the default level)
-    int amg_f32 = -1;                 // XFK_OPT_AMG_F32 (-1: on unless XFK_AMG_F32=0)
+    int amg_f32 = 1;                  // XFK_OPT_AMG_F32
     int newton_inexact = -1;          // XFK_OPT_NEWTON_INEXACT (-1: on unless XFK_NEWTON_INEXACT=0)
     double pcg_tol = 0;               // PCG stopping tolerance of the running pass (0: precision)
     double pcg_tol_rel = 0;           // ... and its relative stop (er <= tol_rel er0; 0: none)

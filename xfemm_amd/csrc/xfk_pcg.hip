@@ -275,12 +275,8 @@ void launch_cg_state_init(hipStream_t s, CgState *S, double tol, double tol_rel)
 int cg_grid(int N) { return (N + kCgBlock - 1) / kCgBlock; }
 int cg_axpy_grid(int N)
 {
-    static const int cap = [] {   // XFK_AX_GRID: measurement override of the fixed grid
-        const char *e = std::getenv("XFK_AX_GRID");
-        return e && std::atoi(e) > 0 ? std::atoi(e) : kAxGrid;
-    }();
     int g = (N / 2 + kAxBlock - 1) / kAxBlock;
-    return g < 1 ? 1 : (g < cap ? g : cap);
+    return g < 1 ? 1 : (g < kAxGrid ? g : kAxGrid);
 }
 
 void launch_cg_init_r(hipStream_t s, int N, int flag, const int *rowptr, const int *col, const double *val,
