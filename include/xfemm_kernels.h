@@ -650,7 +650,7 @@ int xfk_hf_conductor_flow(xfk_problem *prob, int conductor, double *q);
 /* ---------------------------------------------------------------------------
  * Post-processing of a solved electrostatic or heat-flow problem on the
  * device: what the reference's epproc and hpproc compute (getElementD,
- * getNodalD, blockIntegral types 0-4, getPointValues), in the reference's
+ * getNodalD, blockIntegral types 0-6 with makeMask, getPointValues), in the reference's
  * operation order.  Lengths are the problem's own length units, as the
  * reference's post-processors read them.
  *
@@ -683,10 +683,31 @@ int xfk_pot_corner_fields(xfk_problem *prob, double *d);
  *   out7[5..6]  type 4: average E (G), x and y
  * summed in a fixed order, so two runs give the same bits.
  * xfk_pot_block_integral returns one type in the reference's numbering
- * (out2[1] is 0 for the scalar types) and refuses types 5 and 6, the weighted
- * stress tensor integrals. */
+ * (out2[1] is 0 for the scalar types).  Types 5 and 6, the weighted stress
+ * tensor force (N: x and y, or 0 and z on an axisymmetric problem) and torque
+ * about the origin (N m; 0 on an axisymmetric problem), are summed over all
+ * elements against the gradient of the mask: they succeed on an
+ * electrostatic problem that holds a mask made for the same label selection
+ * (xfk_pot_make_mask) and are refused otherwise, and always on a heat-flow
+ * problem. */
 int xfk_pot_block_integrals(xfk_problem *prob, const unsigned char *label_selected, double *out7);
 int xfk_pot_block_integral(xfk_problem *prob, const unsigned char *label_selected, int type, double *out2);
+/* The mask of the weighted stress tensor integrals (the reference's
+ * PostProcessor::makeMask) for the selected labels (one byte per block label),
+ * electrostatic problems only: a Laplace problem of its own on the mesh's
+ * connectivity, weighted per element by sqrt(label_max_area[label]) (the
+ * element's own area where that is <= 0; NULL: everywhere), 1 on the selected
+ * labels' and the selected nodes' nodes (node_selected: one byte per node, may
+ * be NULL), 0 on exterior edges, conductors, fixed points and every other
+ * label that is not air, solved by the problem's own AMG-PCG to its Precision
+ * and thresholded at 0.5.  XFK_ERR_ARG with the reference's message when the
+ * selection abuts a region that is not free space.  A new solution (a solve,
+ * xfk_pot_set_solution) or a new xfk_pot_make_mask drops the mask.
+ * xfk_pot_get_mask: the solved W and the 0/1 mask, n_nodes doubles each;
+ * either may be NULL. */
+int xfk_pot_make_mask(xfk_problem *prob, const unsigned char *label_selected, const unsigned char *node_selected,
+                      const double *label_max_area);
+int xfk_pot_get_mask(xfk_problem *prob, double *W, double *msk);
 /* getPointValues at n points.  elem[i] is the lowest-numbered element that
  * contains point i by the reference's InTriangleTest, or -1 when none does;
  * out holds 8 doubles per point --
@@ -716,6 +737,20 @@ int xfk_pot_corner_branches(xfk_problem *prob, unsigned char *branch);
 int xfk_pot_grid_info(xfk_problem *prob, double *out8);
 int xfk_pot_time(xfk_problem *prob, int n, const double *x, const double *y, int repeats, double *ms7,
                  double *tests_per_point);
+/* ... and of the weighted stress tensor mask.
+ * xfk_pot_mask_info: [0] 1 while the problem holds a mask; of the last
+ * xfk_pot_make_mask [1] the PCG iterations, [2] ms creating the auxiliary
+ * problem (host wall clock; 0 once it exists), [3] ms for the fixed values and
+ * the validity check (wall clock, with its one read-back), [4] - [7] the mask
+ * solve's HIP-event times as xfk_result has them: symbolic phase, assembly,
+ * AMG setup, PCG, [8] ms of the whole call (wall clock).
+ * xfk_pot_mask_problem: the auxiliary problem the mask is solved in (owned by
+ * prob), for xfk_get_csr of its assembled system.
+ * xfk_pot_stress_time: HIP-event ms of the integral launch for types 5 and 6
+ * and its sum, the median of `repeats` runs after a warm-up. */
+int xfk_pot_mask_info(xfk_problem *prob, double *out9);
+int xfk_pot_mask_problem(xfk_problem *prob, xfk_problem **aux);
+int xfk_pot_stress_time(xfk_problem *prob, int repeats, double *ms);
 
 /* Diagnostics of the AMG hierarchy (single device), for tests; not part of the
  * interface a caller should build on.  A probe holds one hierarchy built from

@@ -1141,6 +1141,7 @@ static int assemble(xfk_problem *P, int iter)
     A.n_el = P->NE;
     if (P->electro) launch_electro_rows(s, P);   // (xfk_potential.h's row gather, the electrostatic element)
     else if (P->heat) launch_heat_rows(s, P);    // (likewise, the heat-flow element)
+    else if (P->mask) launch_mask_rows(s, P);    // (likewise, the mask Laplacian of the weighted stress tensor)
     else launch_assemble_rows(s, P->NR, A);   // writes every entry of val and b (assembled rows)
     std::swap(P->mu1.p, P->mu1b.p);     // the state just written is read next iteration
     std::swap(P->mu1.n, P->mu1b.n);
@@ -1819,6 +1820,10 @@ int xfk_device_init(int device)
 void xfk_problem_destroy(xfk_problem *P)
 {
     if (!P) return;
+    if (P->mask_aux) {   // (the auxiliary problem of the weighted stress tensor mask)
+        xfk_problem_destroy(P->mask_aux);
+        P->mask_aux = nullptr;
+    }
     (void)hipSetDevice(P->device);
     if (P->stream) (void)hipStreamSynchronize(P->stream);
     for (auto &ev : P->pass_ev) (void)hipEventDestroy(ev);

@@ -616,6 +616,28 @@ struct xfk_problem {
     xfk::DBuf<double> pp_pts;                    // point batches: x, y in, 8 values out
     xfk::DBuf<int> pp_pel;                       // ... and the element of each point
 
+    // the weighted stress tensor mask of an electrostatic problem
+    // (PostProcessor::makeMask, xfk_postproc.hip): a Laplace problem of its own
+    // on the mesh's connectivity, kept in an auxiliary problem (mask_aux: no
+    // conductors, no periodic pairs, coordinates in user units) that is created
+    // at the first xfk_pot_make_mask and destroyed with this one.  The mask
+    // follows the solution like the fields do (pp_invalidate)
+    std::vector<unsigned char> pot_has_point;    // host, N: the node carries a point property (marker >= 0)
+    xfk_problem *mask_aux = nullptr;
+    bool mask_ready = false, mask_ext_ready = false;
+    std::vector<unsigned char> mask_sel;         // host: the label selection the mask was made for
+    xfk::DBuf<unsigned char> mask_point;         // N: pot_has_point
+    xfk::DBuf<unsigned char> mask_ext;           // N: the node ends an exterior edge (FindBoundaryEdges)
+    xfk::DBuf<unsigned char> mask_nsel;          // N: the selected nodes
+    xfk::DBuf<double> mask_area;                 // per label: MaxArea
+    xfk::DBuf<double> mask_lv;                   // N: the fixed values L.V (-1: free)
+    xfk::DBuf<double> mask_msk;                  // N: W > 0.5 ? 1 : 0
+    xfk::DBuf<int> mask_flag;                    // [0] the selection lies on the axis, [1] it is invalid
+    double mask_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // xfk_pot_mask_info
+    // ... and in the auxiliary problem itself: what its row gather reads
+    bool mask = false;
+    const double *mask_lv_p = nullptr, *mask_area_p = nullptr;
+
     // electrostatic problem (xfk_problem_create_electrostatic, xfk_electro.hip)
     bool electro = false;
     xfk::DBuf<xfk::EsBlock> es_blocks;
@@ -742,11 +764,14 @@ int reserve_first_solve(xfk_problem **out);
 void launch_electro_rows(hipStream_t s, xfk_problem *P);
 // xfk_heat.hip: the same with the heat-flow element (reads P->hf_vo; writes every entry of val and b)
 void launch_heat_rows(hipStream_t s, xfk_problem *P);
+// xfk_postproc.hip: the same with the element of the weighted stress tensor mask (an auxiliary problem, P->mask)
+void launch_mask_rows(hipStream_t s, xfk_problem *P);
 // the integrals of the prescribed-value conductors from the solution in V, into the host conductor tables
 int electro_conductor_integrals(xfk_problem *P);
 int heat_conductor_integrals(xfk_problem *P);
 // xfk_postproc.hip: the cached fields no longer belong to the solution in V
-inline void pp_invalidate(xfk_problem *P) { P->pp_fields_ready = P->pp_corner_ready = false; }
+// (nor does the weighted stress tensor mask: the reference clears bHasMask)
+inline void pp_invalidate(xfk_problem *P) { P->pp_fields_ready = P->pp_corner_ready = P->mask_ready = false; }
 // one pass of the static driver for xfk_heat.hip's outer loop: the numeric
 // assembly with its boundary conditions, and the PCG (flag != 0: from P->V)
 int static_assemble_pass(xfk_problem *P, int iter);

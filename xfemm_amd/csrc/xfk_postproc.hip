@@ -7,6 +7,11 @@
 //   corner fields     getNodalD (PostProcessor.cpp:894-1092)
 //   block integrals   blockIntegral types 0-4 (epproc.cpp:268-397,
 //                     hpproc.cpp:584-646)
+//   the mask          makeMask (PostProcessor.cpp:497-725) with isKosher
+//                     (400-430), FindBoundaryEdges (1097-1150) and
+//                     isSelectionOnAxis (epproc.cpp:471-487); HenrotteVector
+//                     (742-768) and blockIntegral types 5 and 6
+//                     (epproc.cpp:329-389): electrostatics only
 //   point values      InTriangleTest (PostProcessor.cpp:359-398), getPointD
 //                     (1153-1188), getPointValues (epproc.cpp:434-469,
 //                     hpproc.cpp:332-366) over a uniform cell grid
@@ -362,6 +367,253 @@ __global__ void __launch_bounds__(kPotQBlock) k_pp_integrals(int NE, PpArgs A, c
         v[6] = av * Ei;
     }
     block_sums<7>(v, part);
+}
+
+// --- the weighted stress tensor mask (PostProcessor::makeMask) ---------------
+//
+// A second finite-element problem on the same mesh: a Laplacian weighted per
+// element by its label's mesh-size specification, nodal values fixed by the
+// rules of PostProcessor.cpp:545-629, solved and thresholded at 0.5 into a 0/1
+// nodal mask; the force and the torque then sum a stress expression against
+// the gradient of that mask over all elements (epproc.cpp:329-389).  The
+// rules are independent per node apart from their order, so a thread per node
+// applies them in that order; the solve is the static driver's, on an
+// auxiliary problem over the mesh's own connectivity (no conductors, no
+// periodic pairs, as the reference).
+
+// CSMaterialProp::isAir (CMaterialProp.cpp:1603-1609)
+__device__ __forceinline__ bool pp_is_air(const EsBlock &b) { return (b.ex == 1) && (b.ey == 1) && (b.qv == 0); }
+
+// FindBoundaryEdges (PostProcessor.cpp:1097-1150): one thread per (element,
+// side).  Side j runs from p[(j + 1) % 3] to p[(j + 2) % 3]; it is exterior
+// when no other element around its first node holds its second.  ext (zeroed
+// by the caller) marks both ends; every store writes the same 1.
+__global__ void __launch_bounds__(kBlock) k_mask_exterior(int NE, const int *__restrict__ p,
+                                                          const int *__restrict__ n2e_ptr,
+                                                          const int *__restrict__ n2e, unsigned char *__restrict__ ext)
+{
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= 3 * NE) return;
+    const int e = t / 3, j = t - 3 * e;
+    const int org = p[3 * e + (j + 1) % 3], dest = p[3 * e + (j + 2) % 3];
+    bool done = false;
+    for (int m = n2e_ptr[org]; m < n2e_ptr[org + 1] && !done; ++m) {
+        const int ei = n2e[m];
+        if (ei == e) continue;
+        done = p[3 * ei] == dest || p[3 * ei + 1] == dest || p[3 * ei + 2] == dest;
+    }
+    if (!done) {
+        ext[org] = 1;
+        ext[dest] = 1;
+    }
+}
+
+// isSelectionOnAxis (epproc.cpp:471-487, PostProcessor.cpp:479-494), for an
+// axisymmetric problem: a selected element or a selected node at r < 1e-6.
+// One thread per element and per node; flag[0] (zeroed by the caller) is set.
+__global__ void __launch_bounds__(kBlock) k_mask_on_axis(int NE, int N, PpArgs A,
+                                                         const unsigned char *__restrict__ sel,
+                                                         const unsigned char *__restrict__ nsel,
+                                                         int *__restrict__ flag)
+{
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    bool on = false;
+    if (t < NE && sel[A.lbl[t]])
+        for (int j = 0; j < 3; ++j) on |= A.x[A.p[3 * t + j]] < 1.e-6;
+    if (t < N && nsel && nsel[t]) on |= A.x[t] < 1.e-6;
+    if (on) flag[0] = 1;
+}
+
+// The fixed values L.V of makeMask (PostProcessor.cpp:545-629), one thread per
+// node, the rules in the reference's order so that a later one overwrites an
+// earlier one as the sequential code does; -1: free.
+__global__ void __launch_bounds__(kBlock) k_mask_fix(int N, PpArgs A, const int *__restrict__ Q,
+                                                     const int *__restrict__ n2e_ptr, const int *__restrict__ n2e,
+                                                     const unsigned char *__restrict__ ext,
+                                                     const unsigned char *__restrict__ sel,
+                                                     const unsigned char *__restrict__ point,
+                                                     const unsigned char *__restrict__ nsel,
+                                                     const int *__restrict__ flag, double *__restrict__ lv)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    const int l0 = n2e_ptr[i], l1 = n2e_ptr[i + 1];
+    // a fixed point property or any conductor node
+    double v = (Q[i] != -2) ? 0. : -1.;
+    // the ends of exterior edges; with the selection on the axis only where isKosher (PostProcessor.cpp:400-430)
+    if (ext[i]) {
+        bool kosher = true;
+        if (flag[0] && A.axi && !(A.x[i] > 1.e-6)) {
+            int score = 0;
+            for (int m = l0; m < l1; ++m)
+                for (int j = 0; j < 3; ++j) {
+                    const int n = A.p[3 * n2e[m] + j];
+                    if ((n != i) && (A.x[n] < 1.e-6)) score++;
+                }
+            kosher = !(score > 1);
+        }
+        if (kosher) v = 0.;
+    }
+    // the nodes of selected elements 1, of unselected elements that are not
+    // air 0, in element order: the highest-numbered such element decides
+    int last = -1;
+    bool last_sel = false;
+    for (int m = l0; m < l1; ++m) {
+        const int e = n2e[m];
+        if (e < last) continue;
+        const int lb = A.lbl[e];
+        const bool s = sel[lb] != 0;
+        if (s || !pp_is_air(A.es[A.labels[lb].blk])) {
+            last = e;
+            last_sel = s;
+        }
+    }
+    if (last >= 0) v = last_sel ? 1. : 0.;
+    // a still-free node with a point property
+    if (point[i] && (v < 0)) v = 0.;
+    // a selected node
+    if (nsel && nsel[i]) v = 1.;
+    lv[i] = v;
+}
+
+// makeMask's consistency check (PostProcessor.cpp:655-671): an unselected
+// element that is not air with a node not fixed at exactly 0 sets flag[1]
+__global__ void __launch_bounds__(kBlock) k_mask_valid(int NE, PpArgs A, const unsigned char *__restrict__ sel,
+                                                       const double *__restrict__ lv, int *__restrict__ flag)
+{
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= NE) return;
+    const int lb = A.lbl[e];
+    if (sel[lb] || pp_is_air(A.es[A.labels[lb].blk])) return;
+    int k = 0;
+    for (int j = 0; j < 3; ++j)
+        if (lv[A.p[3 * e + j]] == 0) k++;
+    if (k < 3) flag[1] = 1;
+}
+
+// One element of makeMask (PostProcessor.cpp:631-708) for the row gather of
+// xfk_potential.h: Me = v (p_j p_k + q_j q_k) / area with v the square root of
+// the label's MaxArea (of the element's area when that is <= 0), prescribed
+// values eliminated per element.  The reference stores the negated system
+// (L.Put(L.Get - Me), b -= be), which is what the gather's "-=" builds; the
+// element hands it -Me and -be, so the assembled system is the positive
+// definite one the PCG needs.  It has the same solution.  The mask Laplacian
+// is planar for both problem types.
+struct MaskPhys {
+    struct Args {
+        const double *lv, *max_area;
+    };
+
+    template <bool AXI>
+    static __device__ __forceinline__ void element(int e, const int (&g)[3], const RowArgs &A, const Args &S,
+                                                   const double (&X)[3], const double (&Y)[3], const PotLabel &,
+                                                   double (&Me)[3][3], double (&be)[3])
+    {
+        double p[3], q[3];
+        p[0] = Y[1] - Y[2]; p[1] = Y[2] - Y[0]; p[2] = Y[0] - Y[1];
+        q[0] = X[2] - X[1]; q[1] = X[0] - X[2]; q[2] = X[1] - X[0];
+        const double area = (p[0] * q[1] - p[1] * q[0]) / 2.;
+        double v = S.max_area ? S.max_area[A.lbl[e]] : 0.;
+        if (v <= 0) v = sqrt(area);
+        else v = sqrt(v);
+        const double V[3] = {S.lv[g[0]], S.lv[g[1]], S.lv[g[2]]};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            be[j] = 0.;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) Me[j][k] = v * (p[j] * p[k] + q[j] * q[k]) / area;
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            if (V[j] >= 0) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    if (j != k) {
+                        be[k] -= Me[k][j] * V[j];
+                        Me[k][j] = 0.;
+                        Me[j][k] = 0.;
+                    }
+                }
+                be[j] = V[j] * Me[j][j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            be[j] = -be[j];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) Me[j][k] = -Me[j][k];
+        }
+    }
+};
+
+void launch_mask_rows(hipStream_t s, xfk_problem *P)
+{
+    launch_pot_rows<MaskPhys>(s, P, MaskPhys::Args{P->mask_lv_p, P->mask_area_p});
+}
+
+__global__ void __launch_bounds__(kBlock) k_mask_threshold(int N, const double *__restrict__ W,
+                                                           double *__restrict__ msk)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < N) msk[i] = (W[i] > 0.5) ? 1. : 0.;
+}
+
+// blockIntegral types 5 and 6 (epproc.cpp:329-389) with HenrotteVector
+// (PostProcessor.cpp:742-768): one thread per element over all elements; per
+// workgroup the sums of the x (planar) and y (z) force terms and of the torque
+// term (planar) into part.  The reference's planar case 5 adds its x term to
+// the imaginary part as well -- the y term of FEMM's own integral was lost
+// when its three integrals were merged into two -- which is not restated: the
+// y force is a F2 AECF, F2 as case 6 writes it.
+__global__ void __launch_bounds__(kPotQBlock) k_pp_stress(int NE, PpArgs A, const double *__restrict__ msk,
+                                                          const double *__restrict__ D, double lc2,
+                                                          double *__restrict__ part)
+{
+    const int e = blockIdx.x * kPotQBlock + threadIdx.x;
+    double v[3] = {0., 0., 0.};
+    if (e < NE) {
+        PpElem E;
+        pp_load(A, e, E);
+        double b[3], c[3];
+        b[0] = E.Y[1] - E.Y[2]; b[1] = E.Y[2] - E.Y[0]; b[2] = E.Y[0] - E.Y[1];
+        c[0] = E.X[2] - E.X[1]; c[1] = E.X[0] - E.X[2]; c[2] = E.X[1] - E.X[0];
+        double a = ((b[0] * c[1] - b[1] * c[0]) / 2.) * lc2;
+        if (A.axi) {
+            const double r0 = E.X[0] * A.lc, r1 = E.X[1] * A.lc, r2 = E.X[2] * A.lc;
+            const double R = (r0 + r1 + r2) / 3.;
+            a *= (2. * kPI * R);
+        } else {
+            a *= A.depth;
+        }
+        const double B1 = D[2 * e], B2 = D[2 * e + 1];
+        const double da = (b[0] * c[1] - b[1] * c[0]);
+        double cr = 0., ci = 0.;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double m = msk[E.n[i]];
+            cr -= (m * b[i]) / (da * A.lc);
+            ci -= (m * c[i]) / (da * A.lc);
+        }
+        double cx, cy;
+        pp_ctr(E.X, E.Y, cx, cy);
+        const double aecf = pp_aecf(A, E.external, cx, cy);
+        const double F1 = (((B1 * B1) - (B2 * B2)) * cr + 2. * (B1 * B2) * ci) / (2. * kPpEo);
+        const double F2 = (((B2 * B2) - (B1 * B1)) * ci + 2. * (B1 * B2) * cr) / (2. * kPpEo);
+        if (!A.axi) v[0] = a * (F1 * aecf);
+        v[1] = a * (F2 * aecf);
+        if (!A.axi) {
+            double tr = 0., ti = 0.;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                tr += (E.X[k] * A.lc) / 3.;
+                ti += (E.Y[k] * A.lc) / 3.;
+            }
+            double y = tr * F2 - ti * F1;
+            y *= aecf;
+            v[2] = a * y;
+        }
+    }
+    block_sums<3>(v, part);
 }
 
 // --- the cell grid ----------------------------------------------------------
@@ -911,6 +1163,204 @@ static int pp_upload_points(xfk_problem *P, int n, const double *x, const double
     return XFK_OK;
 }
 
+// --- the weighted stress tensor mask: host side --------------------------------
+
+static double wall_ms(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The auxiliary problem of the mask: the mesh's own connectivity (pot_p: a
+// floating conductor's nodes stay apart), coordinates in user units, no
+// boundary data at all -- the element eliminates the prescribed values
+// itself.  Created once and kept with P.
+static int mask_aux_create(xfk_problem *P)
+{
+    if (P->mask_aux) return XFK_OK;
+    hipStream_t s = P->stream;
+    const int N = P->N, NE = P->NE;
+    std::vector<double> x(N), y(N);
+    std::vector<int> p(3 * (size_t)NE), lbl(NE);
+    std::vector<PotLabel> lab(P->pot_labels.n);
+    XFK_CHECK(d2h(x.data(), P->pp_x.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(y.data(), P->pp_y.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(p.data(), P->pot_p.p, sizeof(int) * 3 * (size_t)NE, s));
+    XFK_CHECK(d2h(lbl.data(), P->lbl_raw.p, sizeof(int) * NE, s));
+    XFK_CHECK(d2h(lab.data(), P->pot_labels.p, sizeof(PotLabel) * lab.size(), s));
+    GlobalPrep G;
+    G.blk.assign(1, DevBlock{});
+    G.lab.assign(1, DevLabel{});
+    G.lin.assign(1, DevLine{});
+    G.circ.assign(1, DevCirc{});
+    G.hB.assign(1, 0.);
+    G.hH.assign(1, 0.);
+    G.hS.assign(1, 0.);
+    G.ebits.assign(NE, 0);
+    G.fixed.assign(N, 0);
+    G.first.assign(N, 0.0);
+    G.last = G.first;
+    xfk_problem_desc md = {};
+    md.n_nodes = N;
+    md.x = x.data();
+    md.y = y.data();
+    md.n_elems = NE;
+    md.p = p.data();
+    md.lbl = lbl.data();
+    md.n_blocks = 1;
+    md.n_labels = (int)lab.size();
+    md.precision = P->precision;
+    md.length_units = P->pot_length_units;
+    md.relax = 1.0;
+    md.problem_type = XFK_PLANAR;
+    xfk_problem *Q = nullptr;
+    int rc = build_local(&md, G, nullptr, P->device, nullptr, &Q);
+    if (rc != XFK_OK) return rc;
+    {
+        ArenaScope arena_scope(&Q->arena);
+        const std::vector<unsigned char> none(N, 0);
+        hipError_t e = upload(Q->pot_p, p.data(), p.size(), Q->stream);
+        if (e == hipSuccess) e = upload(Q->pot_labels, lab.data(), lab.size(), Q->stream);
+        if (e == hipSuccess) e = upload(Q->pot_slave, none.data(), none.size(), Q->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(Q->stream);
+        if (e != hipSuccess) {
+            set_error(std::string("upload failed: ") + hipGetErrorString(e));
+            xfk_problem_destroy(Q);
+            return XFK_ERR_HIP;
+        }
+    }
+    Q->mask = true;
+    Q->pot_depth = 1;
+    rc = reserve_first_solve(&Q);
+    if (rc != XFK_OK) {
+        xfk_problem_destroy(Q);
+        return rc;
+    }
+    P->mask_aux = Q;
+    return XFK_OK;
+}
+
+static const char *const kMaskInvalid =
+    "The selected region is invalid. A valid selection cannot abut a region which is not free space.";
+
+// PostProcessor::makeMask for the selection (one byte per label; nsel, one
+// byte per node, may be null; max_area, one double per label, may be null: the
+// element areas weight the Laplacian)
+static int mask_make(xfk_problem *P, const unsigned char *sel, const unsigned char *nsel, const double *max_area)
+{
+    XFK_REQUIRE(P->electro, XFK_ERR_ARG,
+                "the weighted stress tensor mask is for electrostatic problems: heat-flow problems have no "
+                "integrals 5 and 6");
+    XFK_REQUIRE(sel, XFK_ERR_ARG, "null selection mask (one byte per block label)");
+    P->mask_ready = false;
+    const auto t_all = std::chrono::steady_clock::now();
+    int rc = pp_mesh(P);
+    if (rc != XFK_OK) return rc;
+    hipStream_t s = P->stream;
+    const int N = P->N, NE = P->NE;
+    const size_t nlab = P->pot_labels.n;
+    auto t0 = std::chrono::steady_clock::now();
+    const bool fresh = !P->mask_aux;
+    if ((rc = mask_aux_create(P)) != XFK_OK) return rc;
+    xfk_problem *Q = P->mask_aux;
+    const double ms_create = fresh ? wall_ms(t0) : 0.;
+
+    // the fixed values and the validity of the selection
+    t0 = std::chrono::steady_clock::now();
+    const PpArgs A = pp_args(P);
+    XFK_CHECK(P->pp_sel.alloc(nlab));
+    XFK_CHECK(hipMemcpyAsync(P->pp_sel.p, sel, nlab, hipMemcpyHostToDevice, s));
+    std::vector<double> area(nlab, 0.);
+    if (max_area) area.assign(max_area, max_area + nlab);
+    XFK_CHECK(upload(P->mask_area, area.data(), area.size(), s));
+    if (nsel) XFK_CHECK(upload(P->mask_nsel, nsel, (size_t)N, s));
+    const unsigned char *nsel_dev = nsel ? P->mask_nsel.p : nullptr;
+    if (!P->mask_ext_ready) {   // (the exterior edges and the point marks are the mesh's)
+        XFK_CHECK(upload(P->mask_point, P->pot_has_point.data(), (size_t)N, s));
+        XFK_CHECK(P->mask_ext.alloc((size_t)N));
+        XFK_CHECK(hipMemsetAsync(P->mask_ext.p, 0, (size_t)N, s));
+        k_mask_exterior<<<(3 * NE + kBlock - 1) / kBlock, kBlock, 0, s>>>(NE, P->pot_p.p, P->pp_n2e_ptr.p,
+                                                                         P->pp_n2e.p, P->mask_ext.p);
+        P->mask_ext_ready = true;
+    }
+    XFK_CHECK(P->mask_flag.alloc(2));
+    XFK_CHECK(P->mask_lv.alloc((size_t)N));
+    XFK_CHECK(P->mask_msk.alloc((size_t)N));
+    XFK_CHECK(hipMemsetAsync(P->mask_flag.p, 0, 2 * sizeof(int), s));
+    if (P->axi)
+        k_mask_on_axis<<<(std::max(NE, N) + kBlock - 1) / kBlock, kBlock, 0, s>>>(NE, N, A, P->pp_sel.p, nsel_dev,
+                                                                                 P->mask_flag.p);
+    k_mask_fix<<<(N + kBlock - 1) / kBlock, kBlock, 0, s>>>(N, A, P->pp_q.p, P->pp_n2e_ptr.p, P->pp_n2e.p,
+                                                            P->mask_ext.p, P->pp_sel.p, P->mask_point.p, nsel_dev,
+                                                            P->mask_flag.p, P->mask_lv.p);
+    k_mask_valid<<<(NE + kBlock - 1) / kBlock, kBlock, 0, s>>>(NE, A, P->pp_sel.p, P->mask_lv.p, P->mask_flag.p);
+    XFK_CHECK(hipGetLastError());
+    int flag[2] = {0, 0};
+    XFK_CHECK(d2h(flag, P->mask_flag.p, sizeof(flag), s));   // (the stream is idle after this: area and nsel were read)
+    XFK_REQUIRE(!flag[1], XFK_ERR_ARG, kMaskInvalid);
+    const double ms_rules = wall_ms(t0);
+
+    // the Laplace solve: symbolic phase (first call), row gather, AMG-PCG to
+    // the problem's Precision
+    Q->mask_lv_p = P->mask_lv.p;
+    Q->mask_area_p = P->mask_area.p;
+    Q->precision = P->precision;
+    Q->precond = P->precond;
+    xfk_result res{};
+    {
+        ArenaScope arena_scope(&Q->arena);
+        rc = static2d_run(Q, 0, &res);
+        problem_recycle(Q);
+    }
+    if (rc != XFK_OK) return rc;
+    k_mask_threshold<<<(N + kBlock - 1) / kBlock, kBlock, 0, s>>>(N, Q->V.p, P->mask_msk.p);
+    XFK_CHECK(hipGetLastError());
+    XFK_CHECK(hipStreamSynchronize(s));
+    P->mask_sel.assign(sel, sel + nlab);
+    P->mask_ready = true;
+    double *o = P->mask_info;
+    o[0] = (double)res.cg_iters;
+    o[1] = ms_create;
+    o[2] = ms_rules;
+    o[3] = res.ms_symbolic;
+    o[4] = res.ms_assemble;
+    o[5] = res.ms_amg_setup;
+    o[6] = res.ms_solve;
+    o[7] = wall_ms(t_all);
+    return XFK_OK;
+}
+
+// the mask P holds was made for the selection sel
+static bool mask_matches(const xfk_problem *P, const unsigned char *sel)
+{
+    if (!P->mask_ready || !sel || P->mask_sel.size() != P->pot_labels.n) return false;
+    for (size_t k = 0; k < P->mask_sel.size(); ++k)
+        if ((P->mask_sel[k] != 0) != (sel[k] != 0)) return false;
+    return true;
+}
+
+// the three sums of k_pp_stress over all elements, in a fixed order: the x and
+// y (z) force, the torque about the origin
+static int pp_launch_stress(xfk_problem *P)
+{
+    const int NE = P->NE, G = (NE + kPotQBlock - 1) / kPotQBlock;
+    const PpArgs A = pp_args(P);
+    k_pp_stress<<<G, kPotQBlock, 0, P->stream>>>(NE, A, P->mask_msk.p, P->pp_D.p, A.lc * A.lc, P->pp_part.p);
+    k_pot_sum<3><<<1, kPotQBlock, 0, P->stream>>>(G, P->pp_part.p, P->pp_part.p + 7 * (size_t)G);
+    XFK_CHECK(hipGetLastError());
+    return XFK_OK;
+}
+
+static int pp_stress_integrals(xfk_problem *P, double *out3)
+{
+    int rc = pp_fields(P);
+    if (rc != XFK_OK) return rc;
+    const int G = (P->NE + kPotQBlock - 1) / kPotQBlock;
+    XFK_CHECK(P->pp_part.alloc(7 * ((size_t)G + 1)));
+    if ((rc = pp_launch_stress(P)) != XFK_OK) return rc;
+    XFK_CHECK(d2h(out3, P->pp_part.p + 7 * (size_t)G, 3 * sizeof(double), P->stream));
+    return XFK_OK;
+}
+
 extern "C" {
 
 int xfk_pot_set_solution(xfk_problem *P, const double *V)
@@ -977,11 +1427,23 @@ int xfk_pot_block_integrals(xfk_problem *P, const unsigned char *label_selected,
 int xfk_pot_block_integral(xfk_problem *P, const unsigned char *label_selected, int type, double *out2)
 {
     return pp_entry(P, true, [&]() -> int {
-        XFK_REQUIRE(type >= 0 && type <= 6, XFK_ERR_ARG, "block integral type out of range (0-4)");
-        XFK_REQUIRE(type <= 4, XFK_ERR_ARG,
-                    "block integral types 5 and 6 (weighted stress tensor force and torque) are not supported: "
-                    "they need the mask of a Laplace solve of their own");
+        XFK_REQUIRE(type >= 0 && type <= 6, XFK_ERR_ARG, "block integral type out of range (0-6)");
+        XFK_REQUIRE(type <= 4 || P->electro, XFK_ERR_ARG,
+                    "block integral types 5 and 6 (weighted stress tensor force and torque) are not supported "
+                    "on a heat-flow problem: the reference's hpproc has none");
+        XFK_REQUIRE(type <= 4 || mask_matches(P, label_selected), XFK_ERR_ARG,
+                    "block integral types 5 and 6 (weighted stress tensor force and torque) need the mask of a "
+                    "Laplace solve of their own, made for this label selection and this solution: call "
+                    "xfk_pot_make_mask");
         XFK_REQUIRE(out2, XFK_ERR_ARG, "null output");
+        if (type >= 5) {
+            double o[3];
+            const int rc = pp_stress_integrals(P, o);
+            if (rc != XFK_OK) return rc;
+            out2[0] = type == 5 ? o[0] : o[2];
+            out2[1] = type == 5 ? o[1] : 0.;
+            return XFK_OK;
+        }
         double o[7];
         const int rc = pp_block_integrals(P, label_selected, o);
         if (rc != XFK_OK) return rc;
@@ -991,6 +1453,70 @@ int xfk_pot_block_integral(xfk_problem *P, const unsigned char *label_selected, 
             out2[0] = o[type == 3 ? 3 : 5];
             out2[1] = o[type == 3 ? 4 : 6];
         }
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_make_mask(xfk_problem *P, const unsigned char *label_selected, const unsigned char *node_selected,
+                      const double *label_max_area)
+{
+    return pp_entry(P, true, [&]() -> int { return mask_make(P, label_selected, node_selected, label_max_area); });
+}
+
+int xfk_pot_get_mask(xfk_problem *P, double *W, double *msk)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(P->mask_ready && P->mask_aux, XFK_ERR_ARG,
+                    "no mask (xfk_pot_make_mask; a new solution drops the mask)");
+        const size_t bytes = sizeof(double) * (size_t)P->N;
+        if (W) XFK_CHECK(d2h(W, P->mask_aux->V.p, bytes, P->stream));
+        if (msk) XFK_CHECK(d2h(msk, P->mask_msk.p, bytes, P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_mask_info(xfk_problem *P, double *out9)
+{
+    return pp_entry(P, false, [&]() -> int {
+        XFK_REQUIRE(out9, XFK_ERR_ARG, "null output");
+        out9[0] = P->mask_ready ? 1. : 0.;
+        for (int k = 0; k < 8; ++k) out9[1 + k] = P->mask_info[k];
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_mask_problem(xfk_problem *P, xfk_problem **aux)
+{
+    return pp_entry(P, false, [&]() -> int {
+        XFK_REQUIRE(aux, XFK_ERR_ARG, "null output");
+        XFK_REQUIRE(P->mask_aux && P->mask_aux->symbolic_ready, XFK_ERR_ARG, "no mask problem yet (xfk_pot_make_mask)");
+        *aux = P->mask_aux;
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_stress_time(xfk_problem *P, int repeats, double *ms)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(repeats > 0 && ms, XFK_ERR_ARG, "xfk_pot_stress_time needs repeats > 0 and its output");
+        XFK_REQUIRE(P->mask_ready, XFK_ERR_ARG, "no mask (xfk_pot_make_mask; a new solution drops the mask)");
+        int rc = pp_fields(P);
+        if (rc != XFK_OK) return rc;
+        XFK_CHECK(P->pp_part.alloc(7 * ((size_t)(P->NE + kPotQBlock - 1) / kPotQBlock + 1)));
+        ScopedEvents<2> ev;
+        XFK_CHECK(ev.create());
+        std::vector<double> t;
+        for (int k = 0; k <= repeats; ++k) {   // (the first a warm-up)
+            XFK_CHECK(hipEventRecord(ev[0], P->stream));
+            if ((rc = pp_launch_stress(P)) != XFK_OK) return rc;
+            XFK_CHECK(hipEventRecord(ev[1], P->stream));
+            XFK_CHECK(hipEventSynchronize(ev[1]));
+            float m = 0;
+            XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
+            if (k) t.push_back(m);
+        }
+        std::sort(t.begin(), t.end());
+        *ms = t[t.size() / 2];
         return XFK_OK;
     });
 }

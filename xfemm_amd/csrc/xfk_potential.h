@@ -604,6 +604,9 @@ hipError_t upload_potential_common(xfk_problem *P, const PotentialPrep &R, const
     P->pot_cel_ptr = R.cel_ptr;
     P->pot_nslave = (int)R.slave_node.size();
     P->pot_qmark = R.qmark;
+    P->pot_has_point.assign(d->n_nodes, 0);
+    if (d->marker)
+        for (int i = 0; i < d->n_nodes; ++i) P->pot_has_point[i] = d->marker[i] >= 0;
     P->pot_length_units = d->length_units;
     P->pot_unit = R.unit;
     P->pot_depth_user = d->depth;

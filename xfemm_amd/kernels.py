@@ -61,6 +61,7 @@ EXPORTED = (
     "xfk_heatflow_advance", "xfk_hf_get_conductors", "xfk_hf_conductor_flow",
     "xfk_pot_set_solution", "xfk_pot_element_fields", "xfk_pot_corner_fields", "xfk_pot_corner_branches",
     "xfk_pot_block_integrals", "xfk_pot_block_integral", "xfk_pot_point_values", "xfk_pot_grid_info", "xfk_pot_time",
+    "xfk_pot_make_mask", "xfk_pot_get_mask", "xfk_pot_mask_info", "xfk_pot_mask_problem", "xfk_pot_stress_time",
     "xfk_amg_probe_create", "xfk_amg_probe_info", "xfk_amg_probe_level_size", "xfk_amg_probe_level_csr",
     "xfk_amg_probe_tiles", "xfk_amg_probe_vector", "xfk_amg_probe_trace", "xfk_amg_probe_apply",
     "xfk_amg_probe_refresh", "xfk_amg_probe_destroy",
@@ -322,6 +323,11 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_pot_corner_branches.argtypes = [C.c_void_p, ubptr]
     L.xfk_pot_block_integrals.argtypes = [C.c_void_p, ubptr, dptr]
     L.xfk_pot_block_integral.argtypes = [C.c_void_p, ubptr, C.c_int, dptr]
+    L.xfk_pot_make_mask.argtypes = [C.c_void_p, ubptr, ubptr, dptr]
+    L.xfk_pot_get_mask.argtypes = [C.c_void_p, dptr, dptr]
+    L.xfk_pot_mask_info.argtypes = [C.c_void_p, dptr]
+    L.xfk_pot_mask_problem.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.xfk_pot_stress_time.argtypes = [C.c_void_p, C.c_int, dptr]
     L.xfk_pot_grid_info.argtypes = [C.c_void_p, dptr]
     L.xfk_pot_time.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, dptr, dptr]
     L.xfk_pot_point_values.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, iptr, dptr]
@@ -770,7 +776,9 @@ class _PotentialPostProc:
         return {n[0]: o[0], n[1]: o[1], n[2]: o[2], n[3]: o[3:5].copy(), n[4]: o[5:7].copy(), "raw": o}
 
     def block_integral(self, selected_labels, kind: int) -> complex:
-        """One block integral in the reference's numbering (0-4)."""
+        """One block integral in the reference's numbering: 0-4, and on an
+        electrostatic problem holding a mask made for this selection
+        (make_mask) 5 and 6, the weighted stress tensor force and torque."""
         keep, mp = self._mask(selected_labels)
         o = np.zeros(2)
         _check(_lib.xfk_pot_block_integral(self._h, mp, int(kind), o.ctypes.data_as(dptr)))
@@ -899,6 +907,85 @@ class ElectrostaticProblem(_PotentialPostProc):
         q = C.c_double()
         _check(_lib.xfk_conductor_charge(self._h, int(i), C.byref(q)))
         return q.value
+
+    # -- the weighted stress tensor force and torque (block integrals 5 and 6) --
+
+    def _mask_args(self, selected_labels, selected_nodes, max_area):
+        sel, _ = self._mask(selected_labels)
+        nodes = None
+        if selected_nodes is not None:
+            nodes = np.zeros(self.n_nodes, np.uint8)
+            s = np.asarray(selected_nodes)
+            if s.dtype == np.bool_:
+                if s.shape != (self.n_nodes,):
+                    raise ValueError("expected one flag per node (%d), got shape %s" % (self.n_nodes, s.shape))
+                nodes[:] = s
+            else:
+                nodes[s.astype(np.int64)] = 1
+        area = None
+        if max_area is not None:
+            area = np.ascontiguousarray(max_area, dtype=np.float64)
+            if area.shape != (self.n_labels,):
+                raise ValueError("expected one MaxArea per label (%d), got shape %s" % (self.n_labels, area.shape))
+        return sel, nodes, area
+
+    def mask_info(self) -> dict:
+        """Whether the problem holds a mask, and the last make_mask's PCG
+        iterations and times in ms (xfk_pot_mask_info)."""
+        o = np.zeros(9)
+        _check(_lib.xfk_pot_mask_info(self._h, o.ctypes.data_as(dptr)))
+        return dict(ready=bool(o[0]), cg_iters=int(o[1]),
+                    times=dict(create=o[2], fixed_values=o[3], symbolic=o[4], assemble=o[5], amg_setup=o[6],
+                               solve=o[7], total=o[8]))
+
+    def make_mask(self, selected_labels, selected_nodes=None, max_area=None) -> dict:
+        """PostProcessor::makeMask for the selected labels (indices or a boolean
+        mask per label) and nodes (likewise); max_area: the labels' MaxArea
+        (None: the element areas weight the Laplacian).  Returns W (the solved
+        nodal values), msk (W > 0.5 as 0 / 1), cg_iters and times (ms)."""
+        ubp = C.POINTER(C.c_ubyte)
+        sel, nodes, area = self._mask_args(selected_labels, selected_nodes, max_area)
+        self._mask_key = None
+        _check(_lib.xfk_pot_make_mask(self._h, None if sel is None else sel.ctypes.data_as(ubp),
+                                      None if nodes is None else nodes.ctypes.data_as(ubp),
+                                      None if area is None else area.ctypes.data_as(dptr)))
+        self._mask_key = tuple(None if a is None else a.tobytes() for a in (sel, nodes, area))
+        W = np.zeros(self.n_nodes)
+        msk = np.zeros(self.n_nodes)
+        _check(_lib.xfk_pot_get_mask(self._h, W.ctypes.data_as(dptr), msk.ctypes.data_as(dptr)))
+        info = self.mask_info()
+        return dict(W=W, msk=msk, cg_iters=info["cg_iters"], times=info["times"])
+
+    def mask_csr(self):
+        """Diagnostic: the assembled system of the last mask solve, as csr()."""
+        h = C.c_void_p()
+        _check(_lib.xfk_pot_mask_problem(self._h, C.byref(h)))
+        nnz = _lib.xfk_get_nnz(h)
+        rp = np.zeros(self.n_nodes + 1, np.int32)
+        col = np.zeros(nnz, np.int32)
+        val = np.zeros(nnz)
+        b = np.zeros(self.n_nodes)
+        _check(_lib.xfk_get_csr(h, rp.ctypes.data_as(iptr), col.ctypes.data_as(iptr), val.ctypes.data_as(dptr),
+                                b.ctypes.data_as(dptr)))
+        return rp, col, val, b
+
+    def weighted_stress(self, selected_labels, selected_nodes=None, max_area=None) -> dict:
+        """The weighted stress tensor force (N) and torque about the origin
+        (N m) on the selection: block integrals 5 and 6, the mask made first
+        unless the problem holds the one of these very arguments."""
+        key = tuple(None if a is None else a.tobytes()
+                    for a in self._mask_args(selected_labels, selected_nodes, max_area))
+        if getattr(self, "_mask_key", None) != key or not self.mask_info()["ready"]:
+            self.make_mask(selected_labels, selected_nodes, max_area)
+        f = self.block_integral(selected_labels, 5)
+        t = self.block_integral(selected_labels, 6)
+        return dict(force=np.array([f.real, f.imag]), torque=t.real)
+
+    def time_stress(self, repeats: int = 5) -> float:
+        """Diagnostic: HIP-event ms (median) of the integral launch of types 5 and 6."""
+        ms = C.c_double()
+        _check(_lib.xfk_pot_stress_time(self._h, int(repeats), C.byref(ms)))
+        return ms.value
 
 
 class HeatFlowProblem(_PotentialPostProc):
