@@ -798,6 +798,7 @@ struct SgX {
     const double *wF;              // PMODE: per-row smoothing weight
     const unsigned short *c16 = nullptr;   // level 0: 16-bit tile columns (k_spgemm_sort reads them)
     const int *cbase = nullptr;
+    int pack = 0;                  // k_spgemm_sort: sort (column, slot) words, not (column, value) pairs
 };
 struct SgY {
     const int *rowptr, *col;
@@ -1025,6 +1026,26 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// w of lane (lane ^ LM), LM < 16: DPP moves inside the 16-lane row (no LDS
+// pipe); LM = 16 through the shuffle
+__device__ __forceinline__ unsigned xor_lanes(unsigned w, int lm)
+{
+    const int x = (int)w;
+    switch (lm) {
+    case 1: return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false);    // quad_perm:[1,0,3,2]
+    case 2: return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false);    // quad_perm:[2,3,0,1]
+    case 4: {
+        const int t = __builtin_amdgcn_update_dpp(x, x, 0x104, 0xF, 0x5, false);          // row_shl:4 -> lanes 0-3, 8-11
+        return (unsigned)__builtin_amdgcn_update_dpp(t, x, 0x114, 0xF, 0xA, false);       // row_shr:4 -> lanes 4-7, 12-15
+    }
+    case 8: return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0x128, 0xF, 0xF, false);   // row_ror:8
+    default: return (unsigned)__shfl_xor(x, lm, 64);
+    }
+}
+
+// columns a packed sort word can hold next to the slot index of the largest class
+constexpr int kPackMaxCol = (1 << (32 - 8)) - 1;
+
 // Sort-based single-pass SpGEMM for rows of at most CAP products: a group of
 // G lanes per row (64 / G rows per wavefront).  Lane l expands X entries
 // l, l + G, ... (its Y row) into the row's product list in LDS -- the fixed
@@ -1042,7 +1063,13 @@ __device__ __forceinline__ void wave_lds_sync()
 // the slab's length; k_spgemm_compact_slab moves each slab -- one dense run
 // on both sides -- to its CSR place after the length scan.  slab_n == null
 // (XFK_SPGEMM_SLAB=0): every row padded at row * CAP, moved by k_spgemm_compact.
-template <bool PMODE, int G, int CAP>
+// PACK (the Galerkin products, columns < kPackMaxCol): the network moves one 32-bit word per
+// slot, column << log2(CAP) | slot, compared by its column alone, and the
+// values are fetched from the product list once the slots are final.  The
+// network makes the same comparisons and never exchanges equal columns in
+// either form, so every product ends in the same slot and the sums keep
+// their bits; a third of the registers move, and across lanes by DPP.
+template <bool PMODE, int G, int CAP, bool PACK = false>
 __global__ void __launch_bounds__(64) k_spgemm_sort(int nrows, SgX X, SgY Y, int *__restrict__ cnt_out,
                                                     int *__restrict__ pcol, double *__restrict__ pval, int *ovf,
                                                     int *need, int *__restrict__ slab_n)
@@ -1140,46 +1167,96 @@ __global__ void __launch_bounds__(64) k_spgemm_sort(int nrows, SgX X, SgY Y, int
     wave_lds_sync();
     int key[S];
     double val[S];
+    if constexpr (PACK) {
+        constexpr int B = ilog2(CAP);
+        unsigned w[S];
 #pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const int v = l * S + s;
-        key[s] = v < np ? pk[v] : INT_MAX;
-        val[s] = v < np ? pv[v] : 0.0;
-    }
-    // bitonic sort of the CAP slots (slot v = l * S + s) by key
+        for (int s = 0; s < S; ++s) {
+            const int v = l * S + s;
+            w[s] = v < np ? ((unsigned)pk[v] << B) | (unsigned)v : ~0u;
+        }
+        // the same network as below on the words' columns (an empty slot's
+        // column, all ones, is above every real one, as INT_MAX is there)
 #pragma unroll
-    for (int k = 2; k <= CAP; k <<= 1) {
+        for (int k = 2; k <= CAP; k <<= 1) {
 #pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (j < S) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                if (j < S) {
 #pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    const int t = s ^ j;
-                    if (t > s) {
-                        const bool up = ((l * S + s) & k) == 0;
-                        if ((key[s] > key[t]) == up && key[s] != key[t]) {
-                            const int tk = key[s];
-                            key[s] = key[t];
-                            key[t] = tk;
-                            const double tv = val[s];
-                            val[s] = val[t];
-                            val[t] = tv;
+                    for (int s = 0; s < S; ++s) {
+                        const int t = s ^ j;
+                        if (t > s) {
+                            const bool up = ((l * S + s) & k) == 0;
+                            const unsigned a = w[s] >> B, b = w[t] >> B;
+                            if ((a > b) == up && a != b) {
+                                const unsigned tw = w[s];
+                                w[s] = w[t];
+                                w[t] = tw;
+                            }
                         }
                     }
-                }
-            } else {
-                const int lm = j / S;
-                const bool lower = (l & lm) == 0;
+                } else {
+                    const int lm = j / S;
+                    const bool lower = (l & lm) == 0;
 #pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    const int ok = __shfl_xor(key[s], lm, G);
-                    const double ov = __shfl_xor(val[s], lm, G);
-                    const bool up = ((l * S + s) & k) == 0;
-                    // the lower slot of an ascending pair keeps the smaller key
-                    const bool take = (lower == up) ? (ok < key[s]) : (ok > key[s]);
-                    if (take) {
-                        key[s] = ok;
-                        val[s] = ov;
+                    for (int s = 0; s < S; ++s) {
+                        const unsigned ow = xor_lanes(w[s], lm);
+                        const unsigned a = w[s] >> B, b = ow >> B;
+                        const bool up = ((l * S + s) & k) == 0;
+                        const bool take = (lower == up) ? (b < a) : (b > a);
+                        if (take) w[s] = ow;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const bool real = w[s] != ~0u;
+            key[s] = real ? (int)(w[s] >> B) : INT_MAX;
+            val[s] = real ? pv[w[s] & (unsigned)(CAP - 1)] : 0.0;
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const int v = l * S + s;
+            key[s] = v < np ? pk[v] : INT_MAX;
+            val[s] = v < np ? pv[v] : 0.0;
+        }
+        // bitonic sort of the CAP slots (slot v = l * S + s) by key
+#pragma unroll
+        for (int k = 2; k <= CAP; k <<= 1) {
+#pragma unroll
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                if (j < S) {
+#pragma unroll
+                    for (int s = 0; s < S; ++s) {
+                        const int t = s ^ j;
+                        if (t > s) {
+                            const bool up = ((l * S + s) & k) == 0;
+                            if ((key[s] > key[t]) == up && key[s] != key[t]) {
+                                const int tk = key[s];
+                                key[s] = key[t];
+                                key[t] = tk;
+                                const double tv = val[s];
+                                val[s] = val[t];
+                                val[t] = tv;
+                            }
+                        }
+                    }
+                } else {
+                    const int lm = j / S;
+                    const bool lower = (l & lm) == 0;
+#pragma unroll
+                    for (int s = 0; s < S; ++s) {
+                        const int ok = __shfl_xor(key[s], lm, G);
+                        const double ov = __shfl_xor(val[s], lm, G);
+                        const bool up = ((l * S + s) & k) == 0;
+                        // the lower slot of an ascending pair keeps the smaller key
+                        const bool take = (lower == up) ? (ok < key[s]) : (ok > key[s]);
+                        if (take) {
+                            key[s] = ok;
+                            val[s] = ov;
+                        }
                     }
                 }
             }
@@ -2685,6 +2762,12 @@ static bool spgemm_slab_on()
 {
     return env_int("XFK_SPGEMM_SLAB", 1) != 0;
 }
+// XFK_SPGEMM_PACK=0: the Galerkin products sort (column, value) pairs like the
+// prolongator's (read per setup: tests toggle it)
+static bool spgemm_pack_on()
+{
+    return env_int("XFK_SPGEMM_PACK", 1) != 0;
+}
 
 // rows per k_spgemm_sort wavefront (64 / G of the instance launch_sort takes for `cap`)
 static int sort_rows_per_wave(int cap) { return cap == 16 ? 16 : cap <= 64 ? 8 : cap == 128 ? 4 : 2; }
@@ -2725,21 +2808,26 @@ int spgemm(Amg &M, hipStream_t s, int nrows, const SgX &X, const SgY &Y, DBuf<in
         if (nrows > 0) {
             // few lanes per row, 4-8 sorted slots per lane: many rows per
             // wavefront to overlap their dependent gathers
-            if (cap == 16)
-                k_spgemm_sort<PMODE, 4, 16><<<(nrows + 15) / 16, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
-                                                                             slab_n);
-            else if (cap == 32)
-                k_spgemm_sort<PMODE, 8, 32><<<(nrows + 7) / 8, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
-                                                                             slab_n);
-            else if (cap == 64)
-                k_spgemm_sort<PMODE, 8, 64><<<(nrows + 7) / 8, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
-                                                                             slab_n);
-            else if (cap == 128)
-                k_spgemm_sort<PMODE, 16, 128><<<(nrows + 3) / 4, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
-                                                                             slab_n);
-            else
-                k_spgemm_sort<PMODE, 32, 256><<<(nrows + 1) / 2, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need,
-                                                                             slab_n);
+#define XFK_SORT(GG, CC, WW)                                                                                  \
+    do {                                                                                                      \
+        bool packed = false;                                                                                  \
+        if constexpr (!PMODE) {                                                                               \
+            if (X.pack) {                                                                                     \
+                k_spgemm_sort<PMODE, GG, CC, true><<<(nrows + WW - 1) / WW, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, \
+                                                                                         ovf, need, slab_n); \
+                packed = true;                                                                                \
+            }                                                                                                 \
+        }                                                                                                     \
+        if (!packed)                                                                                          \
+            k_spgemm_sort<PMODE, GG, CC><<<(nrows + WW - 1) / WW, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need, \
+                                                                               slab_n);                       \
+    } while (0)
+            if (cap == 16) XFK_SORT(4, 16, 16);
+            else if (cap == 32) XFK_SORT(8, 32, 8);
+            else if (cap == 64) XFK_SORT(8, 64, 8);
+            else if (cap == 128) XFK_SORT(16, 128, 4);
+            else XFK_SORT(32, 256, 2);
+#undef XFK_SORT
         }
     };
     // single pass into padded rows of `cap` slots (sort-based), then scan +
@@ -3954,12 +4042,16 @@ int Amg::build(hipStream_t s, int l0)
         if (g_prof) g_prof->begin(lv + "SpGEMM A P", 0.0);
         // A P's row pointers go straight to the level (they are P~'s when it
         // folds): no copy before the next level reuses the A P buffers
+        // packed sort words (level 0: 164 -> 134 us and 135 -> 98 us on configs[2])
+        const bool pack = !A.dist && nc < kPackMaxCol && spgemm_pack_on();
+        XA.pack = pack;
         rc = spgemm<false>(*this, s, n, XA, YP, A.ftrow, ap_col, ap_val, ap_nnz, 4 * l + 1);
         if (g_prof) g_prof->end();
         if (rc != XFK_OK) return rc;
         if ((int)L.size() <= l + 1) L.emplace_back(new AmgLevel());
         AmgLevel &C = *L[l + 1];
         SgX XR{A.rrow.p, A.rcol.p, A.rval.p, INT_MAX, nullptr, nullptr, nullptr};
+        XR.pack = pack;
         SgY YAP{A.ftrow.p, ap_col.p, ap_val.p, nullptr};
         if (rt_pending) {   // R = P^T from the side stream
             AMG_CHECK(hipStreamWaitEvent(s, sw.b, 0));
