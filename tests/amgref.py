@@ -1,4 +1,4 @@
-"""The AMG setup rules and cycle of xfemm_amd/csrc/xfk_amg.hip restated in
+"""The AMG setup rules and cycle of xfemm_amd/csrc/xfk_amg*.hip restated in
 plain numpy / scipy, as the reference of tests/test_gpu_amg_levels.py.
 
 Nothing here runs on a device.  The setup rules (strength, prolongator,

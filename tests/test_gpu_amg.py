@@ -1,4 +1,4 @@
-"""The AMG-preconditioned PCG (xfemm_amd/csrc/xfk_amg.hip) against the oracle.
+"""The AMG-preconditioned PCG (xfemm_amd/csrc/xfk_amg*.hip) against the oracle.
 
 The reference preconditions CBigLinProb::PCGSolve with SSOR
 (cfemm/libfemm/spars.cpp:186-236); the device's default is a smoothed-

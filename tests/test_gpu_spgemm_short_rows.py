@@ -1,4 +1,4 @@
-"""The Galerkin products with packed sort words (xfk_amg.hip:
+"""The Galerkin products with packed sort words (xfk_amg_spgemm.hip:
 k_spgemm_sort<..., PACK>) against the generic (column, value) network that
 stays in the tree (the prolongator and sharded levels keep using it).
 

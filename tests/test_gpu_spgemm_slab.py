@@ -1,4 +1,4 @@
-"""Dense per-wavefront slabs of the sub-wave SpGEMM (xfk_amg.hip: k_spgemm_sort,
+"""Dense per-wavefront slabs of the sub-wave SpGEMM (xfk_amg_spgemm.hip: k_spgemm_sort,
 k_spgemm_compact_slab) against the padded rows they replace.
 
 Only addresses differ between the two layouts: the products' CSR must come

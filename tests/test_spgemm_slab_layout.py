@@ -1,4 +1,4 @@
-"""Address arithmetic of the SpGEMM slab layout (xfk_amg.hip: k_spgemm_sort,
+"""Address arithmetic of the SpGEMM slab layout (xfk_amg_spgemm.hip: k_spgemm_sort,
 k_spgemm_compact_slab), replayed in numpy without a GPU.
 
 A k_spgemm_sort wavefront handles W = 64 / G consecutive rows of at most CAP

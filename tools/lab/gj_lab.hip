@@ -1,10 +1,10 @@
 // Dense-coarsest lab: times the pivot-block inverse (bgj_diag_inv) and the
-// whole blocked Gauss-Jordan of xfk_amg.hip on synthetic SPD matrices, plus
+// whole blocked Gauss-Jordan of xfk_amg_dense.hip on synthetic SPD matrices, plus
 // variants.  Build (dev container) and run (GPU box):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I xfemm_amd/csrc -I include tools/lab/gj_lab.hip \
 //         -o tools/lab/gj_lab -L xfemm_amd/lib -lxfemm_kernels -Wl,-rpath,$PWD/xfemm_amd/lib
 //   timeout -k 10 60 tools/lab/gj_lab
-#include "../../xfemm_amd/csrc/xfk_amg.hip"
+#include "../../xfemm_amd/csrc/xfk_amg_dense.hip"
 
 #include <cstdio>
 #include <random>
@@ -340,7 +340,6 @@ int main()
         (void)hipFree(dmax);
     }
     // 2. the whole blocked Gauss-Jordan at the configs[2] coarsest size
-    for (int inv_mode = 0; inv_mode < 2; ++inv_mode)
     for (int n : {64, 128, 1024, 1600}) {
         const int nbk = (n + kBj - 1) / kBj, ld = nbk * kBj;
         const size_t T2 = (size_t)kBj * kBj;
@@ -363,7 +362,7 @@ int main()
             for (int k = 0; k < nbk; ++k) {
                 const int p = k & 1, q = (k + 1) & 1;
                 k_bgj_step<<<nbk * nbk, 256, 0, s>>>(k, nbk, ld, dM, Dbuf + p * T2, Rs[p], Cs[p], Dbuf + q * T2, Rs[q],
-                                                     Cs[q], maxd, inv_mode);
+                                                     Cs[q], maxd);
             }
         };
         std::vector<double> X((size_t)ld * ld);
@@ -374,19 +373,18 @@ int main()
         const int k = nbk / 2;
         const float t_step = time_launches(
             [&] {
-                k_bgj_step<<<nbk * nbk, 256, 0, s>>>(k, nbk, ld, dM, Dbuf, Rs[0], Cs[0], Dbuf + T2, Rs[1], Cs[1], maxd,
-                                                     inv_mode);
+                k_bgj_step<<<nbk * nbk, 256, 0, s>>>(k, nbk, ld, dM, Dbuf, Rs[0], Cs[0], Dbuf + T2, Rs[1], Cs[1], maxd);
             },
             50, s);
         const float t_step_last = time_launches(
             [&] {
                 k_bgj_step<<<nbk * nbk, 256, 0, s>>>(nbk - 1, nbk, ld, dM, Dbuf, Rs[0], Cs[0], Dbuf + T2, Rs[1], Cs[1],
-                                                     maxd, inv_mode);
+                                                     maxd);
             },
             50, s);
-        std::printf("{\"test\": \"bgj n=%d inv_mode %d\", \"nbk\": %d, \"us_new\": %.1f, "
+        std::printf("{\"test\": \"bgj n=%d\", \"nbk\": %d, \"us_new\": %.1f, "
                     "\"res_new\": %.3e, \"us_step\": %.2f, \"us_step_no_pivot\": %.2f}\n",
-                    n, inv_mode, nbk, t_new - t_reset, res_new, t_step, t_step_last);
+                    n, nbk, t_new - t_reset, res_new, t_step, t_step_last);
         (void)hipFree(dA);
         (void)hipFree(dM);
         (void)hipFree(tmp);

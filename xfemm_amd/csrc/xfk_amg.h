@@ -1,5 +1,5 @@
 // Smoothed-aggregation algebraic multigrid preconditioner of the PCG
-// (xfk_amg.hip), device resident on one GPU.
+// (xfk_amg*.hip; layout: xfk_amg_impl.h), device resident on one GPU.
 //
 // The reference preconditions CBigLinProb::PCGSolve with a sequential SSOR
 // sweep (cfemm/libfemm/spars.cpp:186-236, MultPC); a triangular sweep has no
@@ -61,7 +61,7 @@ struct AmgLevel {
     long long pnnz = 0;
     DBuf<int> prow, pcol, rrow, rcol;
     DBuf<double> pval, rval;
-    // folded level (xfk_amg.hip: k_fold_pre): P~ = (I - w D^-1 A) P and R~ = P~^T
+    // folded level (xfk_amg_cycle.hip: k_fold_pre): P~ = (I - w D^-1 A) P and R~ = P~^T
     bool fold = false;
     bool fold_formed = false;         // the setup formed P~ (a refresh may fold or not)
     long long fnnz = 0;

@@ -10,6 +10,11 @@
 // are used only where the result does not depend on their order (set
 // membership, counts, max of non-negative values, positions that are sorted
 // afterwards).
+//
+// This file: strength, MIS-2 aggregation and joins, R = P^T, the folded
+// transfer's setup, the hierarchy's host side (scans, stream pool, hints,
+// build, the sharded Galerkin path) and the probes.  The SpGEMM, the dense
+// coarsest inverse and the cycle have files of their own (xfk_amg_impl.h).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -22,9 +27,8 @@
 #include <mutex>
 #include <vector>
 
-#include "xfk_amg.h"
+#include "xfk_amg_impl.h"
 #include "xfk_comm.h"
-#include "xfk_spmv.h"
 
 namespace xfk {
 
@@ -34,8 +38,6 @@ namespace {
 // small helpers
 // --------------------------------------------------------------------------
 
-constexpr int kB = 256;
-inline int nb(long long n) { return (int)((n + kB - 1) / kB); }
 
 // MIS key: (state:2 | perm(i):30), perm a bijection of [0, 2^30) (odd
 // multipliers and xor-shifts): unique per node, so the max over a
@@ -61,25 +63,9 @@ __device__ __forceinline__ MisKey mis_key(MisKey st, int i) { return (st << 30) 
 __device__ __forceinline__ MisKey key_st(MisKey k) { return k >> 30; }
 __device__ __forceinline__ MisKey key_low(MisKey k) { return k & kKeyMask; }
 
-// The columns of a level's CSR as the aggregation reads them: the int array,
-// or (level 0) the 16-bit offsets from the row's 512-row tile base
-// (xfk_spmv.h k_tile_col16; a tile without a base reads the int array)
-struct ColView {
-    const int *col;
-    const unsigned short *c16;   // null: int columns only
-    const int *cbase;
-    __device__ __forceinline__ int base(int i) const { return c16 ? cbase[i / kCgBlock] : kNoColBase; }
-    __device__ __forceinline__ int at(int cb, int k) const { return cb != kNoColBase ? cb + (int)c16[k] : col[k]; }
-};
-
 // entries of a row whose loads are issued together in the aggregation sweeps
 // (per row; G lanes take kMisChunk / G each)
 constexpr int kMisChunk = 8;
-
-__device__ __forceinline__ double rho_of(const unsigned long long *p)
-{
-    return __longlong_as_double((long long)*p);
-}
 
 // max of two values over the workgroup (kB threads), result in thread 0
 __device__ __forceinline__ void block_max2(double &a, double &b, double *red)
@@ -767,1515 +753,8 @@ __global__ void __launch_bounds__(256) k_rt_sort_pairs(int nc, const int *__rest
 }
 
 // --------------------------------------------------------------------------
-// setup: row-merge SpGEMM C = X Y, one wavefront per row
+// setup: the folded transfer P~
 // --------------------------------------------------------------------------
-//
-// Products of row r are enumerated in a fixed order (X entries in row order,
-// each Y row in column order), 64 at a time: a wave prefix sum of the Y-row
-// lengths of up to 64 X entries maps lane products to (X entry, Y position).
-// Pass COUNT inserts the output columns into an LDS hash set and returns the
-// row length; pass FILL inserts them again, ranks them (sorted columns) and
-// accumulates each product into its column in enumeration order: within a
-// group of 64 products, the first lane of each column sums the group's
-// products of that column in lane order, then adds the group sum to the LDS
-// accumulator -- the same operation order on every run.
-//
-// PMODE builds the smoothed prolongator P = S P_tent directly: X is the level
-// matrix masked to its strong entries and diagonal, with values
-// S = I - omega D_F^-1 A_F, and Y = P_tent is given by the aggregate map
-// (row k = {agg[k] : 1}, empty when k is not aggregated).
-
-constexpr int kSgMax = 512;        // distinct output columns per row (COUNT pass hash: 2 kSgMax slots)
-
-constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
-
-struct SgX {
-    const int *rowptr, *col;
-    const double *val;
-    int col_lim;                   // X columns >= col_lim are skipped (sharded halo)
-    const unsigned char *mask;     // PMODE: sflag (1 strong, 2 diagonal)
-    const double *dfinv;           // PMODE: D_F^-1
-    const double *wF;              // PMODE: per-row smoothing weight
-    const unsigned short *c16 = nullptr;   // level 0: 16-bit tile columns (k_spgemm_sort reads them)
-    const int *cbase = nullptr;
-    int pack = 0;                  // k_spgemm_sort: sort (column, slot) words, not (column, value) pairs
-};
-struct SgY {
-    const int *rowptr, *col;
-    const double *val;
-    const int *agg;                // PMODE: P_tent
-};
-
-// CAP: distinct columns a row may have (FILL is launched with the smallest
-// CAP that covers the longest row the COUNT pass found, so typical levels run
-// with a few KiB of LDS per wave and full occupancy); hash slots = 2 CAP.
-template <bool FILL, bool PMODE, int CAP>
-__global__ void __launch_bounds__(64) k_spgemm(int nrows, SgX X, SgY Y, int *__restrict__ cnt_out,
-                                               const int *__restrict__ crow, int *__restrict__ ccol,
-                                               double *__restrict__ cval, int *overflow)
-{
-    constexpr int kSgHash = 2 * CAP;
-    constexpr int kHashShift = 32 - ilog2(kSgHash);
-    __shared__ int hk[kSgHash];
-    __shared__ int hr[FILL ? kSgHash : 1];
-    __shared__ int lst[FILL ? CAP : 1], lslot[FILL ? CAP : 1];
-    __shared__ double acc[FILL ? CAP : 1];
-    __shared__ int c_off[64], c_ys[64];
-    __shared__ double c_xv[64];
-    __shared__ __attribute__((aligned(16))) int s_rank[64];
-    __shared__ double s_val[64];
-    __shared__ int s_cnt, s_ovf, s_m;
-
-    const int row = blockIdx.x;
-    const int lane = threadIdx.x;
-    if (row >= nrows) return;
-    for (int t = lane; t < kSgHash; t += 64) hk[t] = -1;
-    if (lane == 0) {
-        s_cnt = 0;
-        s_ovf = 0;
-        s_m = 0;
-    }
-    __syncthreads();
-    const int xs = X.rowptr[row], xe = X.rowptr[row + 1];
-    double omega = 0.0, dfi = 0.0;
-    if (PMODE) {
-        omega = X.wF[row];
-        dfi = X.dfinv[row];
-    }
-
-    auto insert = [&](int key) {
-        unsigned h = ((unsigned)key * 2654435761u) >> kHashShift;
-        for (int probe = 0; probe < kSgHash; ++probe) {
-            const int old = atomicCAS(&hk[h], -1, key);
-            if (old == -1) {
-                atomicAdd(&s_cnt, 1);
-                return;
-            }
-            if (old == key) return;
-            h = (h + 1) & (kSgHash - 1);
-        }
-        s_ovf = 1;
-    };
-    auto lookup = [&](int key) -> int {
-        unsigned h = ((unsigned)key * 2654435761u) >> kHashShift;
-        for (int probe = 0; probe < kSgHash; ++probe) {
-            const int k = hk[h];
-            if (k == key) return (int)h;
-            if (k == -1) return -1;
-            h = (h + 1) & (kSgHash - 1);
-        }
-        return -1;
-    };
-    // stage up to 64 X entries of [e0, xe); returns the group's product count
-    auto stage = [&](int e0) -> int {
-        const int e = e0 + lane;
-        int len = 0, ys = 0;
-        double xv = 0.0;
-        if (e < xe) {
-            const int k = X.col[e];
-            if (k < X.col_lim) {
-                if (PMODE) {
-                    const unsigned char f = X.mask[e];
-                    if (f != 0 && Y.agg[k] >= 0) {
-                        ys = k;
-                        len = 1;
-                        xv = (f == 2) ? 1.0 - omega : -omega * dfi * X.val[e];
-                    }
-                } else {
-                    ys = Y.rowptr[k];
-                    len = Y.rowptr[k + 1] - ys;
-                    xv = X.val[e];
-                }
-            }
-        }
-        int incl = len;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        const int total = __shfl(incl, 63, 64);
-        c_off[lane] = incl - len;
-        c_ys[lane] = ys;
-        c_xv[lane] = xv;
-        __syncthreads();
-        return total;
-    };
-    // product p of the staged group -> (column, value)
-    auto product = [&](int p, int &key, double &v) {
-        int lo = 0, hi = 63;   // largest staged entry with c_off <= p
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (c_off[mid] <= p) lo = mid;
-            else hi = mid - 1;
-        }
-        if (PMODE) {
-            key = Y.agg[c_ys[lo]];
-            v = c_xv[lo];
-        } else {
-            const int q = c_ys[lo] + (p - c_off[lo]);
-            key = Y.col[q];
-            if (FILL) v = c_xv[lo] * Y.val[q];
-        }
-    };
-
-    // pass 1: the set of output columns
-    for (int e0 = xs; e0 < xe; e0 += 64) {
-        const int total = stage(e0);
-        for (int p = lane; p < total; p += 64) {
-            int key;
-            double v;
-            product(p, key, v);
-            insert(key);
-        }
-        __syncthreads();
-    }
-    if (!FILL) {
-        if (lane == 0) {
-            cnt_out[row] = s_cnt;
-            if (s_ovf || s_cnt > CAP) atomicOr(overflow, 1);
-        }
-        return;
-    }
-    // rank the columns (sorted order) and map hash slot -> rank
-    for (int t = lane; t < kSgHash; t += 64)
-        if (hk[t] != -1) {
-            const int m = atomicAdd(&s_m, 1);
-            if (m < CAP) {
-                lst[m] = hk[t];
-                lslot[m] = t;
-            }
-        }
-    __syncthreads();
-    const int cnt = min(s_m, CAP);
-    const int cb = crow[row];
-    for (int m = lane; m < cnt; m += 64) {
-        const int key = lst[m];
-        int rank = 0;
-        for (int q = 0; q < cnt; ++q) rank += lst[q] < key;
-        hr[lslot[m]] = rank;
-        ccol[cb + rank] = key;
-        acc[rank] = 0.0;
-    }
-    __syncthreads();
-    // pass 2: values in enumeration order
-    const int4 *r4 = reinterpret_cast<const int4 *>(s_rank);
-    for (int e0 = xs; e0 < xe; e0 += 64) {
-        const int total = stage(e0);
-        for (int p0 = 0; p0 < total; p0 += 64) {
-            const int p = p0 + lane;
-            int rank = -1;
-            double v = 0.0;
-            if (p < total) {
-                int key;
-                product(p, key, v);
-                const int h = lookup(key);
-                rank = (h >= 0) ? hr[h] : -1;
-            }
-            s_rank[lane] = rank;
-            s_val[lane] = v;
-            __syncthreads();
-            if (rank >= 0) {
-                bool leader = true;
-                double sum = 0.0;
-#pragma unroll
-                for (int m4 = 0; m4 < 16; ++m4) {
-                    const int4 q = r4[m4];
-                    const int m = 4 * m4;
-                    if (q.x == rank) { leader &= (m < lane) ? false : true; sum += s_val[m]; }
-                    if (q.y == rank) { leader &= (m + 1 < lane) ? false : true; sum += s_val[m + 1]; }
-                    if (q.z == rank) { leader &= (m + 2 < lane) ? false : true; sum += s_val[m + 2]; }
-                    if (q.w == rank) { leader &= (m + 3 < lane) ? false : true; sum += s_val[m + 3]; }
-                }
-                if (leader) acc[rank] += sum;
-            }
-            __syncthreads();
-        }
-    }
-    for (int m = lane; m < cnt; m += 64) cval[cb + m] = acc[m];
-}
-
-// Products per row (upper bound of the output row length), for the choice
-// between the sub-wave and the wave-per-row SpGEMM.
-template <bool PMODE>
-__global__ void k_spgemm_nprod(int nrows, SgX X, SgY Y, int *__restrict__ nprod)
-{
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= nrows) return;
-    int c = 0;
-    for (int e = X.rowptr[row]; e < X.rowptr[row + 1]; ++e) {
-        const int k = X.col[e];
-        if (k >= X.col_lim) continue;
-        if (PMODE) c += (X.mask[e] != 0 && Y.agg[k] >= 0);
-        else c += Y.rowptr[k + 1] - Y.rowptr[k];
-    }
-    nprod[row] = c;
-}
-
-// Sub-wave SpGEMM (the fine levels: A P, the prolongator, R (A P)): G lanes
-// per row, 64 / G rows per wavefront.  Groups of one wavefront advance
-// independently; their LDS regions are private, and LDS traffic inside a
-// wavefront is ordered, so no workgroup barriers are needed (wave_barrier
-// keeps the compiler from reordering).
-constexpr int kSortCap = 256;         // k_spgemm_sort: rows of at most this many products
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// w of lane (lane ^ LM), LM < 16: DPP moves inside the 16-lane row (no LDS
-// pipe); LM = 16 through the shuffle
-__device__ __forceinline__ unsigned xor_lanes(unsigned w, int lm)
-{
-    const int x = (int)w;
-    switch (lm) {
-    case 1: return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false);    // quad_perm:[1,0,3,2]
-    case 2: return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false);    // quad_perm:[2,3,0,1]
-    case 4: {
-        const int t = __builtin_amdgcn_update_dpp(x, x, 0x104, 0xF, 0x5, false);          // row_shl:4 -> lanes 0-3, 8-11
-        return (unsigned)__builtin_amdgcn_update_dpp(t, x, 0x114, 0xF, 0xA, false);       // row_shr:4 -> lanes 4-7, 12-15
-    }
-    case 8: return (unsigned)__builtin_amdgcn_update_dpp(x, x, 0x128, 0xF, 0xF, false);   // row_ror:8
-    default: return (unsigned)__shfl_xor(x, lm, 64);
-    }
-}
-
-// columns a packed sort word can hold next to the slot index of the largest class
-constexpr int kPackMaxCol = (1 << (32 - 8)) - 1;
-
-// Sort-based single-pass SpGEMM for rows of at most CAP products: a group of
-// G lanes per row (64 / G rows per wavefront).  Lane l expands X entries
-// l, l + G, ... (its Y row) into the row's product list in LDS -- the fixed
-// enumeration order -- then the list is loaded as CAP virtual slots, S = CAP / G
-// consecutive slots per lane in registers, and sorted by column with a bitonic
-// network (in-lane compare-exchanges for distances < S, shuffles across the
-// group for the others).  A segmented inclusive scan then sums each column's
-// products and counts the distinct columns; the last slot of each column
-// writes it at its rank.  The network and the scan are fixed, so the sums
-// are the same bits on every run.  Only the product list (12 B per product)
-// lives in LDS: several times more rows in flight than the hash kernels.
-// The wavefront's W rows are written back to back into its slab
-// (blockIdx.x * W * CAP: the exclusive prefix of the W lengths, which the
-// wavefront holds in registers, places each row) with the row lengths and
-// the slab's length; k_spgemm_compact_slab moves each slab -- one dense run
-// on both sides -- to its CSR place after the length scan.  slab_n == null
-// (XFK_SPGEMM_SLAB=0): every row padded at row * CAP, moved by k_spgemm_compact.
-// PACK (the Galerkin products, columns < kPackMaxCol): the network moves one 32-bit word per
-// slot, column << log2(CAP) | slot, compared by its column alone, and the
-// values are fetched from the product list once the slots are final.  The
-// network makes the same comparisons and never exchanges equal columns in
-// either form, so every product ends in the same slot and the sums keep
-// their bits; a third of the registers move, and across lanes by DPP.
-template <bool PMODE, int G, int CAP, bool PACK = false>
-__global__ void __launch_bounds__(64) k_spgemm_sort(int nrows, SgX X, SgY Y, int *__restrict__ cnt_out,
-                                                    int *__restrict__ pcol, double *__restrict__ pval, int *ovf,
-                                                    int *need, int *__restrict__ slab_n)
-{
-    constexpr int W = 64 / G;
-    constexpr int S = CAP / G;
-    static_assert(S >= 1 && S * G == CAP, "CAP must be a multiple of G");
-    __shared__ int pk_all[W][CAP];
-    __shared__ double pv_all[W][CAP];
-    const int g = threadIdx.x / G, l = threadIdx.x % G;
-    const int row = blockIdx.x * W + g;
-    int *pk = pk_all[g];
-    double *pv = pv_all[g];
-    const bool live = row < nrows;
-    int np = 0;
-    if (live) {
-        const int xs = X.rowptr[row], xe = X.rowptr[row + 1];
-        const ColView xc{X.col, X.c16, X.cbase};
-        const int cb = xc.base(row);
-        double omega = 0.0, dfi = 0.0;
-        if (PMODE) {
-            omega = X.wF[row];
-            dfi = X.dfinv[row];
-        }
-        for (int e0 = xs; e0 < xe; e0 += G) {
-            const int e = e0 + l;
-            int len = 0, ys = 0;
-            double xv = 0.0;
-            if (e < xe) {
-                const int k = xc.at(cb, e);
-                if (k < X.col_lim) {
-                    if (PMODE) {
-                        const unsigned char f = X.mask[e];
-                        if (f != 0 && Y.agg[k] >= 0) {
-                            ys = Y.agg[k];
-                            len = 1;
-                            xv = (f == 2) ? 1.0 - omega : -omega * dfi * X.val[e];
-                        }
-                    } else {
-                        ys = Y.rowptr[k];
-                        len = Y.rowptr[k + 1] - ys;
-                        xv = X.val[e];
-                    }
-                }
-            }
-            int incl = len;
-#pragma unroll
-            for (int off = 1; off < G; off <<= 1) {
-                const int t = __shfl_up(incl, off, G);
-                if (l >= off) incl += t;
-            }
-            const int total = __shfl(incl, G - 1, G);
-            const int o = np + incl - len;
-            if (PMODE) {
-                if (len && o < CAP) {
-                    pk[o] = ys;
-                    pv[o] = xv;
-                }
-            } else {
-                // the first U entries of the Y row loaded together (rows of P
-                // hold ~2.5, of A P ~5: one memory latency instead of one per entry)
-                constexpr int U = CAP >= 128 ? 8 : 4;
-                int yc[U];
-                double yv[U];
-#pragma unroll
-                for (int q = 0; q < U; ++q)
-                    if (q < len) {
-                        yc[q] = Y.col[ys + q];
-                        yv[q] = Y.val[ys + q];
-                    }
-#pragma unroll
-                for (int q = 0; q < U; ++q)
-                    if (q < len && o + q < CAP) {
-                        pk[o + q] = yc[q];
-                        pv[o + q] = xv * yv[q];
-                    }
-                for (int q = U; q < len && o + q < CAP; ++q) {
-                    pk[o + q] = Y.col[ys + q];
-                    pv[o + q] = xv * Y.val[ys + q];
-                }
-            }
-            np += total;
-        }
-        // a capacity taken from another problem (need != null): some row must
-        // need more than half of it, else a measurement would have taken a
-        // smaller class (whose sort order -- and so whose bits -- differ)
-        if (need && np > CAP / 2 && l == 0 && *(volatile int *)need == 0) *need = 1;
-        // more products than slots (a capacity taken from an earlier setup):
-        // the row is garbage, the host redoes the product with a measured capacity
-        if (np > CAP) {
-            if (l == 0) *ovf = 1;
-            np = CAP;
-        }
-    }
-    wave_lds_sync();
-    int key[S];
-    double val[S];
-    if constexpr (PACK) {
-        constexpr int B = ilog2(CAP);
-        unsigned w[S];
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const int v = l * S + s;
-            w[s] = v < np ? ((unsigned)pk[v] << B) | (unsigned)v : ~0u;
-        }
-        // the same network as below on the words' columns (an empty slot's
-        // column, all ones, is above every real one, as INT_MAX is there)
-#pragma unroll
-        for (int k = 2; k <= CAP; k <<= 1) {
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                if (j < S) {
-#pragma unroll
-                    for (int s = 0; s < S; ++s) {
-                        const int t = s ^ j;
-                        if (t > s) {
-                            const bool up = ((l * S + s) & k) == 0;
-                            const unsigned a = w[s] >> B, b = w[t] >> B;
-                            if ((a > b) == up && a != b) {
-                                const unsigned tw = w[s];
-                                w[s] = w[t];
-                                w[t] = tw;
-                            }
-                        }
-                    }
-                } else {
-                    const int lm = j / S;
-                    const bool lower = (l & lm) == 0;
-#pragma unroll
-                    for (int s = 0; s < S; ++s) {
-                        const unsigned ow = xor_lanes(w[s], lm);
-                        const unsigned a = w[s] >> B, b = ow >> B;
-                        const bool up = ((l * S + s) & k) == 0;
-                        const bool take = (lower == up) ? (b < a) : (b > a);
-                        if (take) w[s] = ow;
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const bool real = w[s] != ~0u;
-            key[s] = real ? (int)(w[s] >> B) : INT_MAX;
-            val[s] = real ? pv[w[s] & (unsigned)(CAP - 1)] : 0.0;
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const int v = l * S + s;
-            key[s] = v < np ? pk[v] : INT_MAX;
-            val[s] = v < np ? pv[v] : 0.0;
-        }
-        // bitonic sort of the CAP slots (slot v = l * S + s) by key
-#pragma unroll
-        for (int k = 2; k <= CAP; k <<= 1) {
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                if (j < S) {
-#pragma unroll
-                    for (int s = 0; s < S; ++s) {
-                        const int t = s ^ j;
-                        if (t > s) {
-                            const bool up = ((l * S + s) & k) == 0;
-                            if ((key[s] > key[t]) == up && key[s] != key[t]) {
-                                const int tk = key[s];
-                                key[s] = key[t];
-                                key[t] = tk;
-                                const double tv = val[s];
-                                val[s] = val[t];
-                                val[t] = tv;
-                            }
-                        }
-                    }
-                } else {
-                    const int lm = j / S;
-                    const bool lower = (l & lm) == 0;
-#pragma unroll
-                    for (int s = 0; s < S; ++s) {
-                        const int ok = __shfl_xor(key[s], lm, G);
-                        const double ov = __shfl_xor(val[s], lm, G);
-                        const bool up = ((l * S + s) & k) == 0;
-                        // the lower slot of an ascending pair keeps the smaller key
-                        const bool take = (lower == up) ? (ok < key[s]) : (ok > key[s]);
-                        if (take) {
-                            key[s] = ok;
-                            val[s] = ov;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    // segmented inclusive scan: head = first slot of a column
-    const int prev_last = __shfl_up(key[S - 1], 1, G);
-    int head[S], nh = 0;
-    double run[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const int pk_ = s > 0 ? key[s - 1] : (l > 0 ? prev_last : -1);
-        head[s] = (key[s] != INT_MAX && key[s] != pk_) ? 1 : 0;
-        run[s] = (s > 0 && !head[s]) ? run[s - 1] + val[s] : val[s];
-        nh += head[s];
-    }
-    // carry from earlier lanes into this lane's leading (headless) slots
-    int seg_open = 1;   // no head in this lane yet: the lane continues the previous segment
-#pragma unroll
-    for (int s = 0; s < S; ++s) seg_open &= !head[s];
-    double carry = run[S - 1];   // this lane's trailing partial
-    int hpre = nh;
-    int open = seg_open;
-#pragma unroll
-    for (int off = 1; off < G; off <<= 1) {
-        const double oc = __shfl_up(carry, off, G);
-        const int oo = __shfl_up(open, off, G);
-        const int oh = __shfl_up(hpre, off, G);
-        if (l >= off) {
-            if (open) carry = oc + carry;
-            open = open && oo;
-            hpre += oh;
-        }
-    }
-    // carry / head count of the lanes before this one
-    double cin = __shfl_up(carry, 1, G);
-    int hin = __shfl_up(hpre, 1, G);
-    if (l == 0) {
-        cin = 0.0;
-        hin = 0;
-    }
-    const int cnt = __shfl(hpre, G - 1, G);
-    // slab layout: the wavefront's W rows back to back from blockIdx.x * W * CAP
-    // (inclusive scan of the W counts, every lane of a group holding its row's;
-    // a dead row counts 0)
-    int upto = cnt;
-#pragma unroll
-    for (int off = G; off < 64; off <<= 1) {
-        const int t = __shfl_up(upto, off, 64);
-        if ((int)threadIdx.x >= off) upto += t;
-    }
-    if (slab_n && threadIdx.x == 63) slab_n[blockIdx.x] = upto;
-    if (!live) return;
-    const size_t base = slab_n ? (size_t)blockIdx.x * (W * CAP) + (upto - cnt) : (size_t)row * CAP;
-    int h = hin;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        bool lead = true;   // slots before this lane's first head continue the incoming segment
-#pragma unroll
-        for (int q = 0; q <= s; ++q) lead = lead && !head[q];
-        const double tot = lead ? cin + run[s] : run[s];
-        h += head[s];
-        const int nk = s + 1 < S ? key[s + 1] : __shfl_down(key[0], 1, G);
-        const bool tail = key[s] != INT_MAX && (nk != key[s] || (s + 1 == S && l == G - 1));
-        if (tail) {
-            pcol[base + h - 1] = key[s];
-            pval[base + h - 1] = tot;
-        }
-    }
-    if (l == 0) cnt_out[row] = cnt;
-}
-
-// padded rows (row * cap) -> CSR; 16 lanes per row, so a row's reads and
-// writes are contiguous runs
-// nnz_out (optional): the product's length, for a deferred host read;
-// L lanes per row (a quarter of the slot capacity: the rows hold about that many)
-template <int L>
-__global__ void k_spgemm_compact(int nrows, int cap, const int *__restrict__ crow, const int *__restrict__ pcol,
-                                 const double *__restrict__ pval, int *__restrict__ ccol, double *__restrict__ cval,
-                                 int *nnz_out)
-{
-    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (t == 0 && nnz_out) *nnz_out = crow[nrows];
-    const int row = (int)(t / L), l = (int)(t % L);
-    if (row >= nrows) return;
-    const int b = crow[row], n = crow[row + 1] - b;
-    for (int m = l; m < n; m += L) {
-        ccol[b + m] = pcol[(size_t)row * cap + m];
-        cval[b + m] = pval[(size_t)row * cap + m];
-    }
-}
-
-// dense slabs (k_spgemm_sort: slab b holds rows b * W ... back to back, slab_n[b]
-// entries from b * stride) -> CSR.  A slab's rows are consecutive, so it lands
-// as one run at crow[b * W]: both sides are dense, whatever the row lengths.
-// kSlabLanes lanes per slab (slabs of level-0 products hold 40-100 entries),
-// a workgroup moves 16 slabs.
-constexpr int kSlabLanes = 16;
-__global__ void k_spgemm_compact_slab(int nrows, int nslab, int W, int stride, const int *__restrict__ crow,
-                                      const int *__restrict__ slab_n, const int *__restrict__ pcol,
-                                      const double *__restrict__ pval, int *__restrict__ ccol,
-                                      double *__restrict__ cval, int *nnz_out)
-{
-    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (t == 0 && nnz_out) *nnz_out = crow[nrows];
-    const int b = (int)(t / kSlabLanes), l = (int)(t % kSlabLanes);
-    if (b >= nslab) return;
-    const int d = crow[b * W], n = slab_n[b];
-    const size_t src = (size_t)b * stride;
-    for (int m = l; m < n; m += kSlabLanes) {
-        ccol[d + m] = pcol[src + m];
-        cval[d + m] = pval[src + m];
-    }
-}
-
-// --------------------------------------------------------------------------
-// setup: coarsest level, dense inverse
-// --------------------------------------------------------------------------
-
-// The coarsest level (<= kAmgDenseMax rows) becomes a dense matrix padded to
-// a multiple of kBj with an identity tail (ld = padded size), inverted in
-// place by blocked Gauss-Jordan without pivoting (the level operators are
-// symmetric positive semi-definite).  Step k of kBj-wide block columns
-// (k_bgj_step, one launch):
-//     D  = inv(M_kk)                      k_bgj_diag for k = 0, else workgroup 0
-//                                         of step k-1 (once its tile is final)
-//     M_kj = D M_kj          (j != k),    M_kk = D
-//     M_ij -= M_ik (D M_kj)  (i, j != k)
-//     M_ik = -M_ik D         (i != k)     (old values of row k / column k)
-// The matrix is first scaled symmetrically to unit diagonal and the inverse
-// unscaled at the end.  A pivot below 1e-11 of the (unit) scaled diagonal
-// marks a null direction -- roundoff leaves the exact null pivot of a
-// pure-Neumann operator near 1e-13 (tools/lab/gj_emul.py) -- and its row and
-// column are zeroed (generalised inverse on the range).
-constexpr int kBj = 64;
-
-// the matrix has been zeroed (hipMemsetAsync); entries of row i, identity tail
-// symmetric diagonal scaling sc_q = 1 / sqrt(a_qq) (1 for a zero diagonal
-// and the padding rows): the scaled matrix has unit diagonal, so every
-// Gauss-Jordan pivot (a Schur-complement diagonal) lies in (0, 1].
-// perm / iperm (nested-dissection order, nullptr: identity): dense index of
-// coarse row r is perm[r]; iperm[q] the coarse row of dense index q (-1: padding)
-// kDsG lanes per dense row (consecutive entries on consecutive lanes): the
-// row's column, permutation and scale loads of 16 entries in flight at once
-// instead of one dependent chain per row (one thread per row took 11 + 26 us
-// for the 1.6k-row coarsest level of configs[2]).  The coarse operator's rows
-// hold distinct columns (SpGEMM output), so every entry is written once:
-// 0 + v, the value the former accumulation into the zeroed matrix produced.
-constexpr int kDsG = 16;
-__global__ void k_dense_dscale(int n, int ld, const int *__restrict__ rowptr, const int *__restrict__ col,
-                               const double *__restrict__ val, const int *__restrict__ iperm, double *__restrict__ sc)
-{
-    const int q = (blockIdx.x * blockDim.x + threadIdx.x) / kDsG, l = threadIdx.x % kDsG;
-    if (q >= ld) return;   // (whole groups: ld * kDsG threads exactly cover the rows)
-    const int i = iperm ? iperm[q] : (q < n ? q : -1);
-    int kd = -1;
-    if (i >= 0)
-        for (int k = rowptr[i] + l; k < rowptr[i + 1]; k += kDsG)
-            if (col[k] == i) kd = k;
-#pragma unroll
-    for (int off = 1; off < kDsG; off <<= 1) kd = max(kd, __shfl_xor(kd, off, kDsG));
-    if (l != 0) return;
-    const double d = kd >= 0 ? 0.0 + val[kd] : 0.0;
-    sc[q] = d > 0.0 ? 1.0 / sqrt(d) : 1.0;
-}
-__global__ void k_dense_scatter(int n, int ld, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                const double *__restrict__ val, const int *__restrict__ perm,
-                                const int *__restrict__ iperm, const double *__restrict__ sc, double *__restrict__ M)
-{
-    const int q = (blockIdx.x * blockDim.x + threadIdx.x) / kDsG, l = threadIdx.x % kDsG;
-    if (q >= ld) return;
-    const int i = iperm ? iperm[q] : (q < n ? q : -1);
-    if (i < 0) {
-        if (l == 0) M[(size_t)q * ld + q] = 1.0;
-        return;
-    }
-    const double sq = sc[q];
-    for (int k = rowptr[i] + l; k < rowptr[i + 1]; k += kDsG) {
-        const int cj = col[k];
-        if (cj >= n) continue;
-        const int c = perm ? perm[cj] : cj;
-        M[(size_t)q * ld + c] = 0.0 + val[k] * sq * sc[c];
-    }
-}
-
-// The coarsest inverse the V-cycle applies, unpermuted: M is the inverse of
-// the unit-diagonal scaled level (S A_c S)^-1, so A_c^-1 = S M S; the apply
-// keeps S in f64 (osc, original order) and stores M symmetrised -- entries
-// (i, j) and (j, i) both from the one value (M_qr + M_rq) / 2, rounded once --
-// in f32 (V = float, the default: half the bytes of the per-iteration coarse
-// solve) or f64.  Rounding the scaled, symmetrised inverse keeps the coarse
-// correction exactly symmetric; the f32 perturbation is relative to the entries
-// of a unit-diagonal matrix's inverse (not of A_c^-1 itself, whose entries span
-// the coefficient contrast).  One 64 x 64 output tile per block, its mirror
-// tile read through LDS.
-template <class V>
-__global__ void __launch_bounds__(256) k_dense_unperm(int n, int ld, int ldo, const double *__restrict__ M,
-                                                      const double *__restrict__ sc, const int *__restrict__ iperm,
-                                                      V *__restrict__ out, double *__restrict__ osc)
-{
-    __shared__ double t[64][65];
-    const int bq = blockIdx.y * 64, br = blockIdx.x * 64;
-    for (int k = threadIdx.x; k < 64 * 64; k += 256) {   // t[a][b] = M[br + b][bq + a]
-        const int a = k & 63, b = k >> 6;
-        t[a][b] = M[(size_t)(br + b) * ld + bq + a];
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < 64 * 64; k += 256) {
-        const int a = k >> 6, b = k & 63, q = bq + a, r = br + b;
-        const int i = iperm ? iperm[q] : (q < n ? q : -1), j = iperm ? iperm[r] : (r < n ? r : -1);
-        if (i >= 0 && j >= 0) out[(size_t)i * ldo + j] = (V)(0.5 * (M[(size_t)q * ld + r] + t[a][b]));
-    }
-    if (blockIdx.x == 0)
-        for (int a = threadIdx.x; a < 64; a += 256) {
-            const int q = bq + a, i = iperm ? iperm[q] : (q < n ? q : -1);
-            if (i >= 0) osc[i] = sc[q];
-        }
-}
-
-__global__ void __launch_bounds__(1024) k_dense_maxdiag(int n, int ld, const double *__restrict__ M,
-                                                        double *__restrict__ maxd)
-{
-    __shared__ double red[16];
-    double m = 0.0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) m = fmax(m, fabs(M[(size_t)i * ld + i]));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = fmax(m, red[w]);
-        *maxd = m;
-    }
-}
-
-// D = inv(M_kk) by in-place Gauss-Jordan: 256 threads, thread t keeps the 16
-// entries (rows 16 (t >> 6) + m, column t & 63) in registers for the whole
-// inversion.  Pivots are taken four at a time: with P = {p0 .. p0+3},
-// Dinv = inv(A_PP) (every thread inverts the 4 x 4 block in registers) and
-//     c_i = A_iP,  r_j = Dinv A_Pj (j not in P),  r_j = e_t + Dinv[:, t] (j = p0 + t),
-// one uniform rank-4 update a_ij -= c_i . r_j followed by a_sj += r_j[s] on
-// the rows of P leaves Dinv A_Pj in rows P, -A_iP Dinv in columns P and Dinv
-// in the pivot block; the scaled pivots lie in (0, 1], so no step cancels
-// more than a few bits.  A pivot block with a vanishing pivot is eliminated
-// by four scalar steps instead, which zero the row and column of a null
-// direction.  Rows P and columns P go through LDS, double-buffered: one
-// barrier per step.
-__device__ __forceinline__ void gj_scalar_step(int p, double (&a)[16], double thr, double *slab, double *colk)
-{
-    const int j = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (w == (p >> 4))   // the wave holding row p publishes its slab
-#pragma unroll
-        for (int m = 0; m < 16; ++m) slab[m * kBj + j] = a[m];
-    if (j == p)
-#pragma unroll
-        for (int m = 0; m < 16; ++m) colk[16 * w + m] = a[m];
-    __syncthreads();
-    const double *rowp = slab + (p & 15) * kBj;
-    const double piv = rowp[p];
-    if (!(fabs(piv) > thr)) {   // null direction: zero row p and column p
-#pragma unroll
-        for (int m = 0; m < 16; ++m)
-            if (16 * w + m == p || j == p) a[m] = 0.0;
-        return;
-    }
-    const double ip = 1.0 / piv;
-    const double r = j == p ? 1.0 + ip : rowp[j] * ip;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) a[m] -= (colk[16 * w + m] - (16 * w + m == p ? 1.0 : 0.0)) * r;
-}
-
-// lds: 2 * 16 * kBj + 2 * 4 * kBj doubles (16-byte aligned): the double-
-// buffered 16-row slab holding P ([m][j]) and columns P ([i][t])
-constexpr int kBjDiagLds = 2 * 16 * kBj + 2 * 4 * kBj;
-__device__ __forceinline__ void bgj_diag_inv(double (&a)[16], double thr, double *lds)
-{
-    const int tid = threadIdx.x;
-    const int j = tid & 63, w = tid >> 6;
-    // (buffer pointers by arithmetic on lds: a runtime-indexed pointer array
-    // would hide the LDS address space and turn every access into a flat op)
-    int phase = 0;
-    for (int p0 = 0; p0 < kBj; p0 += 4) {
-        const int buf = phase & 1;
-        const int mb = p0 & 15, wp = p0 >> 4;
-        double *R4 = lds + buf * 16 * kBj, *C4 = lds + 32 * kBj + buf * 4 * kBj;
-        if (w == wp)   // this wave holds rows P: publish its whole slab (no dynamic register index)
-#pragma unroll
-            for (int m = 0; m < 16; ++m) R4[m * kBj + j] = a[m];
-        R4 += mb * kBj;   // rows P = slab rows mb .. mb+3
-        if (j >= p0 && j < p0 + 4)   // these lanes hold columns P
-#pragma unroll
-            for (int m = 0; m < 16; ++m) C4[(16 * w + m) * 4 + (j - p0)] = a[m];
-        __syncthreads();
-        ++phase;
-        // Dinv = inv(A_PP), in-place Gauss-Jordan in registers
-        double Dv[4][4];
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) Dv[s2][t] = R4[s2 * kBj + p0 + t];
-        bool ok = true;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const double piv = Dv[q][q];
-            ok = ok && (fabs(piv) > thr);
-            const double ip = 1.0 / piv;
-            Dv[q][q] = 1.0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) Dv[q][t] *= ip;
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) {
-                if (s2 == q) continue;
-                const double f = Dv[s2][q];
-                Dv[s2][q] = 0.0;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) Dv[s2][t] -= f * Dv[q][t];
-            }
-        }
-        if (!ok) {   // a (near) null direction inside the block: scalar steps
-            for (int p = p0; p < p0 + 4; ++p) {
-                const int b2 = phase & 1;
-                gj_scalar_step(p, a, thr, lds + b2 * 16 * kBj, lds + 32 * kBj + b2 * 4 * kBj);
-                ++phase;
-            }
-            continue;
-        }
-        double r[4];
-        if (j >= p0 && j < p0 + 4) {
-            const int t = j - p0;
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) {
-                double d = Dv[s2][0];
-#pragma unroll
-                for (int tt = 1; tt < 4; ++tt)
-                    if (tt == t) d = Dv[s2][tt];
-                r[s2] = (s2 == t ? 1.0 : 0.0) + d;
-            }
-        } else {
-            const double x0 = R4[j], x1 = R4[kBj + j], x2 = R4[2 * kBj + j], x3 = R4[3 * kBj + j];
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) r[s2] = Dv[s2][0] * x0 + Dv[s2][1] * x1 + Dv[s2][2] * x2 + Dv[s2][3] * x3;
-        }
-        const double4 *cr = reinterpret_cast<const double4 *>(&C4[16 * w * 4]);
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-            const double4 c = cr[m];
-            a[m] -= c.x * r[0] + c.y * r[1] + c.z * r[2] + c.w * r[3];
-        }
-        if (w == wp)
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const int s2 = m - mb;
-                a[m] += (s2 == 0 ? r[0] : 0.0) + (s2 == 1 ? r[1] : 0.0) + (s2 == 2 ? r[2] : 0.0) +
-                        (s2 == 3 ? r[3] : 0.0);
-            }
-    }
-}
-
-__global__ void __launch_bounds__(256) k_bgj_diag(int k, int ld, const double *__restrict__ M,
-                                                  const double *__restrict__ maxd, double *__restrict__ D)
-{
-    __shared__ __attribute__((aligned(16))) double lds[kBjDiagLds];
-    const int j = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const size_t base = (size_t)k * kBj * ld + (size_t)k * kBj;
-    double a[16];
-#pragma unroll
-    for (int m = 0; m < 16; ++m) a[m] = M[base + (size_t)(16 * w + m) * ld + j];
-    bgj_diag_inv(a, 1e-11 * (*maxd), lds);
-#pragma unroll
-    for (int m = 0; m < 16; ++m) D[(16 * w + m) * kBj + j] = a[m];
-}
-
-// C = X Y for 64 x 64 blocks staged in LDS on the f64 matrix cores: 4 waves,
-// wave w computes the 32 x 32 quadrant (w >> 1, w & 1) as 2 x 2 tiles of
-// v_mfma_f64_16x16x4_f64 (A[l & 15][k = l >> 4], B[k = l >> 4][l & 15];
-// C/D col = l & 15, row = (l >> 4) + 4 r).  c[ti][tj][r] is element
-// (32 (w >> 1) + 16 ti + (l >> 4) + 4 r, 32 (w & 1) + 16 tj + (l & 15)).
-// LDS row strides (doubles) that make the operand reads conflict-free: a
-// 32-lane half reads 16 rows x 2 k of X (stride 66 -> banks 4 li + 2 lk) and
-// 2 k-rows x 16 columns of Y (stride 80 -> the two rows 32 banks apart).
-typedef double dbl4 __attribute__((ext_vector_type(4)));
-constexpr int kXs = 66, kYs = 80;
-
-template <bool ZERO = true>
-__device__ __forceinline__ void bgj_mm(const double *__restrict__ Xs, const double *__restrict__ Ys, dbl4 (&c)[2][2])
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int r0 = 32 * (w >> 1), c0 = 32 * (w & 1);
-    const int li = lane & 15, lk = lane >> 4;
-    if (ZERO)
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) c[ti][tj] = dbl4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (int s = 0; s < kBj / 4; ++s) {
-        double a[2], b[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            a[t] = Xs[(r0 + 16 * t + li) * kXs + 4 * s + lk];
-            b[t] = Ys[(4 * s + lk) * kYs + c0 + 16 * t + li];
-        }
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-                c[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[tj], c[ti][tj], 0, 0, 0);
-    }
-}
-
-// (row, col) of element r of tile (ti, tj) of this thread
-__device__ __forceinline__ int bgj_row(int ti, int r) { return 32 * ((threadIdx.x >> 6) >> 1) + 16 * ti + ((threadIdx.x & 63) >> 4) + 4 * r; }
-__device__ __forceinline__ int bgj_col(int tj) { return 32 * ((threadIdx.x >> 6) & 1) + 16 * tj + (threadIdx.x & 15); }
-
-// inv(A) of a 64 x 64 block held in bgj_mm's accumulator layout
-// (c[ti][tj][r] = element (bgj_row(ti, r), bgj_col(tj))), in place: 16
-// rank-4 Gauss-Jordan steps whose updates run on the f64 matrix cores.  Step
-// s publishes rows and columns P = 4s .. 4s+3 to LDS; every lane forms
-// D = inv(A_PP) in registers and its B operand r = D A_Pj (r = I + D on the
-// pivot columns); then c -= A_iP r on the MFMA, and rows P += r -- the update
-// of bgj_diag_inv without its 64 FMAs and 32 LDS reads per lane and step.
-// A (near) null pivot (|piv| <= thr) zeroes its row and column, as there.
-// lds: kBjInvLds doubles (two buffers of a 4 x 64 row slab and a 64 x 4 column slab).
-constexpr int kBjInvLds = 2 * 8 * kBj;
-static_assert(kBjInvLds <= kBjDiagLds && kBjInvLds <= kBj * kYs, "bgj_inv_mfma's LDS exceeds its callers' buffers");
-__device__ __forceinline__ void bgj_inv_mfma(dbl4 (&c)[2][2], double thr, double *lds)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const int R0 = 32 * (w >> 1), C0 = 32 * (w & 1);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-        const int p0 = 4 * s;
-        const int tp = (p0 >> 4) & 1, rp = (p0 & 15) >> 2;   // tile / element index of rows (columns) P
-        double *RS = lds + (s & 1) * 8 * kBj;   // RS[t][j] = A(p0 + t, j)
-        double *CS = RS + 4 * kBj;              // CS[i][t] = A(i, p0 + t)
-        const bool rowhold = (w >> 1) == (p0 >> 5);
-        if (rowhold)   // this lane holds row p0 + lk
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) RS[lk * kBj + C0 + 16 * tj + li] = c[tp][tj][rp];
-        if ((w & 1) == (p0 >> 5) && li >= (p0 & 15) && li < (p0 & 15) + 4)   // ... column p0 + li - (p0 & 15)
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) CS[(R0 + 16 * ti + lk + 4 * r) * 4 + li - (p0 & 15)] = c[ti][tp][r];
-        __syncthreads();
-        double W[4][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) W[q][t] = RS[q * kBj + p0 + t];
-        // a null pivot takes ip = 0: its row of D becomes 0 and the
-        // elimination leaves the other rows alone, i.e. D is the inverse on
-        // the other directions; the update then zeroes column p0 + q of the
-        // block by itself (r = e_q there), and row p0 + q is zeroed below
-        unsigned nul = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const double piv = W[q][q];
-            const bool ok = fabs(piv) > thr;
-            nul |= ok ? 0u : 1u << q;
-            double ip = __builtin_amdgcn_rcp(piv);   // 1 / piv: v_rcp_f64 + two Newton steps
-            ip = fma(fma(-piv, ip, 1.0), ip, ip);
-            ip = fma(fma(-piv, ip, 1.0), ip, ip);
-            ip = ok ? ip : 0.0;
-            W[q][q] = 1.0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) W[q][t] *= ip;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                if (t == q) continue;
-                const double f = W[t][q];
-                W[t][q] = 0.0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) W[t][u] -= f * W[q][u];
-            }
-        }
-        // row lk of D: this lane's B operand row
-        double Dk[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) Dk[t] = lk == 0 ? W[0][t] : lk == 1 ? W[1][t] : lk == 2 ? W[2][t] : W[3][t];
-        double bop[2], aop[2];
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-            const int jj = C0 + 16 * tj + li, tc = jj - p0;
-            if (tc >= 0 && tc < 4) {
-                const double d = tc == 0 ? Dk[0] : tc == 1 ? Dk[1] : tc == 2 ? Dk[2] : Dk[3];
-                bop[tj] = (lk == tc ? 1.0 : 0.0) + d;
-            } else {
-                bop[tj] = Dk[0] * RS[jj] + Dk[1] * RS[kBj + jj] + Dk[2] * RS[2 * kBj + jj] + Dk[3] * RS[3 * kBj + jj];
-            }
-        }
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) aop[ti] = -CS[(R0 + 16 * ti + li) * 4 + lk];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) c[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[ti], bop[tj], c[ti][tj], 0, 0, 0);
-        if (rowhold) {
-            const bool zr = (nul >> lk) & 1u;   // row p0 + lk of a null pivot
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) c[tp][tj][rp] = zr ? 0.0 : c[tp][tj][rp] + bop[tj];
-        }
-    }
-}
-
-template <int S>
-__device__ __forceinline__ void bgj_load(double *__restrict__ dst, const double *__restrict__ src, size_t ld)
-{
-    // 2048 double2 per tile, 8 per thread, all issued before the first use
-    double2 v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int e = threadIdx.x + 256 * q, r = e >> 5, c = 2 * (e & 31);
-        v[q] = *reinterpret_cast<const double2 *>(src + (size_t)r * ld + c);
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int e = threadIdx.x + 256 * q, r = e >> 5, c = 2 * (e & 31);
-        dst[r * S + c] = v[q].x;
-        dst[r * S + c + 1] = v[q].y;
-    }
-}
-
-// One launch per block step k.
-// Step k reads only snapshots written by step k-1 (or the prologue), so every
-// tile is finalised in the same launch with no ordering between workgroups:
-//     D    = inv(M_kk)                               Dk
-//     R[j] = M_kj after step k-1 (row k, unscaled)    Rk + j T2
-//     C[i] = M_ik after step k-1 (column k)           Ck + i T2
-// tile (i, j):  i == k:  M_kj = D R[j]          (j == k: M_kk = D)
-//               j == k:  M_ik = -C[i] D
-//               else:    M_ij -= C[i] (D R[j])  (T_kj = D R[j] recomputed per
-//                                                tile: no row launch, no wait)
-// Row k+1 of the result goes to Rn, column k+1 to Cn; workgroup 0 takes tile
-// (k+1, k+1) -- the next pivot block -- and inverts it into Dn once written.
-// The chain per step is one launch: the pivot workgroup's two tile GEMMs and
-// the 64 x 64 inversion.
-// snapshots of row k (R[j] = M_kj) and column k (C[i] = M_ik) before step k
-__global__ void __launch_bounds__(256) k_bgj_snap(int k, int nbk, int ld, const double *__restrict__ M,
-                                                  double *__restrict__ R, double *__restrict__ C)
-{
-    const int t = blockIdx.x % nbk;
-    const bool row = blockIdx.x < nbk;
-    const double *src = row ? M + (size_t)k * kBj * ld + (size_t)t * kBj : M + (size_t)t * kBj * ld + (size_t)k * kBj;
-    double *dst = (row ? R : C) + (size_t)t * kBj * kBj;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int e = threadIdx.x + 256 * q, r = e >> 5, c = 2 * (e & 31);
-        *reinterpret_cast<double2 *>(dst + r * kBj + c) = *reinterpret_cast<const double2 *>(src + (size_t)r * ld + c);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_bgj_step(int k, int nbk, int ld, double *__restrict__ M,
-                                                  const double *__restrict__ Dk, const double *__restrict__ Rk,
-                                                  const double *__restrict__ Ck, double *__restrict__ Dn,
-                                                  double *__restrict__ Rn, double *__restrict__ Cn,
-                                                  const double *__restrict__ maxd)
-{
-    const int nt = nbk * nbk, kn = k + 1 < nbk ? k + 1 : 0;
-    const int b = (int)((blockIdx.x + (unsigned)(kn * nbk + kn)) % (unsigned)nt);
-    const int i = b / nbk, j = b % nbk;
-    const bool piv = k + 1 < nbk && blockIdx.x == 0;
-    const size_t T2 = (size_t)kBj * kBj;
-    __shared__ __attribute__((aligned(16))) double Xs[kBj * kXs];
-    __shared__ __attribute__((aligned(16))) double Ys[kBj * kYs];
-    double *Mij = M + (size_t)i * kBj * ld + (size_t)j * kBj;
-    if (i == k && j == k) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int e = threadIdx.x + 256 * q, r = e >> 5, c = 2 * (e & 31);
-            *reinterpret_cast<double2 *>(Mij + (size_t)r * ld + c) = *reinterpret_cast<const double2 *>(Dk + r * kBj + c);
-        }
-        return;
-    }
-    dbl4 c[2][2];
-    double sgn = 1.0;
-    bool rmw = false;
-    if (i == k) {   // T = D R[j]
-        bgj_load<kXs>(Xs, Dk, kBj);
-        bgj_load<kYs>(Ys, Rk + j * T2, kBj);
-        __syncthreads();
-        bgj_mm(Xs, Ys, c);
-    } else if (j == k) {   // -C[i] D
-        bgj_load<kXs>(Xs, Ck + i * T2, kBj);
-        bgj_load<kYs>(Ys, Dk, kBj);
-        __syncthreads();
-        bgj_mm(Xs, Ys, c);
-        sgn = -1.0;
-    } else {   // M_ij - C[i] (D R[j])
-        double2 pre[8];   // C[i], in flight during the first product
-        const double *Ci = Ck + i * T2;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int e = threadIdx.x + 256 * q, r = e >> 5, cc = 2 * (e & 31);
-            pre[q] = *reinterpret_cast<const double2 *>(Ci + r * kBj + cc);
-        }
-        bgj_load<kXs>(Xs, Dk, kBj);
-        bgj_load<kYs>(Ys, Rk + j * T2, kBj);
-        __syncthreads();
-        bgj_mm(Xs, Ys, c);
-        __syncthreads();
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Ys[bgj_row(ti, r) * kYs + bgj_col(tj)] = c[ti][tj][r];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int e = threadIdx.x + 256 * q, r = e >> 5, cc = 2 * (e & 31);
-            Xs[r * kXs + cc] = pre[q].x;
-            Xs[r * kXs + cc + 1] = pre[q].y;
-        }
-        __syncthreads();
-        bgj_mm(Xs, Ys, c);
-        sgn = -1.0;
-        rmw = true;
-    }
-    double *rn = (i == k + 1) ? Rn + j * T2 : nullptr;
-    double *cn = (j == k + 1) ? Cn + i * T2 : nullptr;
-    if (piv) __syncthreads();   // Ys is reused below
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = bgj_row(ti, r), col = bgj_col(tj);
-                double *e = &Mij[(size_t)row * ld + col];
-                const double v = rmw ? *e - c[ti][tj][r] : sgn * c[ti][tj][r];
-                *e = v;
-                if (rn) rn[row * kBj + col] = v;
-                if (cn) cn[row * kBj + col] = v;
-                if (piv) c[ti][tj][r] = v;
-            }
-    if (!piv) return;
-    bgj_inv_mfma(c, 1e-11 * (*maxd), Ys);
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Dn[bgj_row(ti, r) * kBj + bgj_col(tj)] = c[ti][tj][r];
-}
-
-// Nested-dissection steps.  The coarsest operator is reordered by a
-// recursive bisection: leaves (parts that share no entry), then their
-// separators, the top separator last.  Gauss-Jordan keeps distinct leaves
-// decoupled: eliminating a block column of a leaf touches only the tiles of
-// its region -- the leaf plus its ancestor separators -- and the updates of
-// different leaves commute.  So the leaves' block columns are eliminated side
-// by side, one pivot chain per leaf in each launch (up to four), then the
-// separators of the next tree level the same way (region: their subtree plus
-// ancestors), the top separator last.  Each tile applies the update of every
-// chain whose region holds it (separator tiles: several, summed on the MFMA
-// in chain order); per block, bit c of `mask` marks chain c's region.
-constexpr int kNdChains = 8;
-struct BgjStep {
-    int n;                                             // chains of this step
-    int k[kNdChains];                                  // their pivot blocks
-    const double *D[kNdChains], *R[kNdChains], *C[kNdChains];   // inv(M_kk), row / column snapshots
-    int nn;                                            // distinct next pivot blocks
-    int nx[kNdChains];
-    double *Dn[kNdChains], *Rn[kNdChains], *Cn[kNdChains];
-};
-
-// (chain fields are selected by unrolled comparisons: a dynamically indexed
-// by-value kernel argument would be placed in scratch memory)
-__global__ void __launch_bounds__(256, 2) k_bgj_multi(int nbk, int ld, double *__restrict__ M, BgjStep st,
-                                                      const unsigned char *__restrict__ mask,
-                                                      const int *__restrict__ tiles, const double *maxd)
-{
-    const size_t T2 = (size_t)kBj * kBj;
-    int i, j;
-    double *Dpiv = nullptr;
-    if ((int)blockIdx.x < st.nn) {   // workgroups 0 .. nn-1 finalise and invert the next pivot blocks
-#pragma unroll
-        for (int t = 0; t < kNdChains; ++t)
-            if (t == (int)blockIdx.x) {
-                i = j = st.nx[t];
-                Dpiv = st.Dn[t];
-            }
-    } else {
-        const int t = tiles[blockIdx.x - st.nn];
-        i = t / nbk;
-        j = t % nbk;
-        if (i == j)
-#pragma unroll
-            for (int u = 0; u < kNdChains; ++u)
-                if (u < st.nn && st.nx[u] == i) return;   // taken by a pivot workgroup
-    }
-    const unsigned act = (unsigned)mask[i] & (unsigned)mask[j];
-    int pc = -1;
-    const double *pD = nullptr, *pR = nullptr, *pC = nullptr;
-    int pk = -1;
-#pragma unroll
-    for (int c = 0; c < kNdChains; ++c)
-        if (c < st.n && ((act >> c) & 1u) && (i == st.k[c] || j == st.k[c])) {
-            pc = c;
-            pk = st.k[c];
-            pD = st.D[c];
-            pR = st.R[c];
-            pC = st.C[c];
-        }
-    __shared__ __attribute__((aligned(16))) double Xs[kBj * kXs];
-    __shared__ __attribute__((aligned(16))) double Ys[kBj * kYs];
-    double *Mij = M + (size_t)i * kBj * ld + (size_t)j * kBj;
-    if (pc >= 0 && i == pk && j == pk) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int e = threadIdx.x + 256 * q, r = e >> 5, c = 2 * (e & 31);
-            *reinterpret_cast<double2 *>(Mij + (size_t)r * ld + c) = *reinterpret_cast<const double2 *>(pD + r * kBj + c);
-        }
-        return;
-    }
-    dbl4 acc[2][2];
-    double sgn = 1.0;
-    bool rmw = false;
-    if (pc >= 0 && i == pk) {   // row of a pivot: D R[j]
-        bgj_load<kXs>(Xs, pD, kBj);
-        bgj_load<kYs>(Ys, pR + j * T2, kBj);
-        __syncthreads();
-        bgj_mm(Xs, Ys, acc);
-    } else if (pc >= 0) {       // column of a pivot: -C[i] D
-        bgj_load<kXs>(Xs, pC + i * T2, kBj);
-        bgj_load<kYs>(Ys, pD, kBj);
-        __syncthreads();
-        bgj_mm(Xs, Ys, acc);
-        sgn = -1.0;
-    } else {                    // M_ij - sum over the chains holding the tile of C[i] (D R[j])
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = dbl4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int c = 0; c < kNdChains; ++c) {
-            if (!(c < st.n && ((act >> c) & 1u))) continue;
-            double2 pre[8];
-            const double *Ci = st.C[c] + i * T2;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int e = threadIdx.x + 256 * u, r = e >> 5, cc = 2 * (e & 31);
-                pre[u] = *reinterpret_cast<const double2 *>(Ci + r * kBj + cc);
-            }
-            __syncthreads();   // the LDS of the previous chain's product is free
-            bgj_load<kXs>(Xs, st.D[c], kBj);
-            bgj_load<kYs>(Ys, st.R[c] + j * T2, kBj);
-            __syncthreads();
-            dbl4 t[2][2];
-            bgj_mm(Xs, Ys, t);
-            __syncthreads();
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) Ys[bgj_row(ti, r) * kYs + bgj_col(tj)] = t[ti][tj][r];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int e = threadIdx.x + 256 * u, r = e >> 5, cc = 2 * (e & 31);
-                Xs[r * kXs + cc] = pre[u].x;
-                Xs[r * kXs + cc + 1] = pre[u].y;
-            }
-            __syncthreads();
-            bgj_mm<false>(Xs, Ys, acc);
-        }
-        rmw = true;
-    }
-    // row / column snapshots of the next pivot blocks this tile belongs to
-    double *rs[kNdChains], *cs[kNdChains];
-#pragma unroll
-    for (int t = 0; t < kNdChains; ++t) {
-        rs[t] = (t < st.nn && i == st.nx[t]) ? st.Rn[t] + j * T2 : nullptr;
-        cs[t] = (t < st.nn && j == st.nx[t]) ? st.Cn[t] + i * T2 : nullptr;
-    }
-    if (Dpiv) __syncthreads();   // Ys is reused below
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = bgj_row(ti, r), col = bgj_col(tj);
-                double *e = &Mij[(size_t)row * ld + col];
-                const double v = rmw ? *e - acc[ti][tj][r] : sgn * acc[ti][tj][r];
-                *e = v;
-#pragma unroll
-                for (int t = 0; t < kNdChains; ++t) {
-                    if (rs[t]) rs[t][row * kBj + col] = v;
-                    if (cs[t]) cs[t][row * kBj + col] = v;
-                }
-                if (Dpiv) acc[ti][tj][r] = v;
-            }
-    if (!Dpiv) return;
-    bgj_inv_mfma(acc, 1e-11 * (*maxd), Ys);
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Dpiv[bgj_row(ti, r) * kBj + bgj_col(tj)] = acc[ti][tj][r];
-}
-
-// first step of the first phase: pivot-block inverses (workgroups 0 .. n-1)
-// and row / column snapshots of the chains' first pivot blocks
-__global__ void __launch_bounds__(256) k_bgj_init(int nbk, int ld, const double *__restrict__ M, BgjStep st,
-                                                  const double *__restrict__ maxd)
-{
-    const int b = blockIdx.x;
-    if (b < st.nn) {
-        __shared__ __attribute__((aligned(16))) double lds[kBjInvLds];
-        int k = 0;
-        double *D = nullptr;
-#pragma unroll
-        for (int t = 0; t < kNdChains; ++t)
-            if (t == b) {
-                k = st.nx[t];
-                D = st.Dn[t];
-            }
-        const size_t base = (size_t)k * kBj * ld + (size_t)k * kBj;
-        dbl4 c[2][2];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) c[ti][tj][r] = M[base + (size_t)bgj_row(ti, r) * ld + bgj_col(tj)];
-        bgj_inv_mfma(c, 1e-11 * (*maxd), lds);
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) D[bgj_row(ti, r) * kBj + bgj_col(tj)] = c[ti][tj][r];
-        return;
-    }
-    const int e0 = b - st.nn, ch = e0 / (2 * nbk), rem = e0 % (2 * nbk);
-    const int t = rem % nbk;
-    const bool row = rem < nbk;
-    int k = 0;
-    double *dst = nullptr;
-#pragma unroll
-    for (int u = 0; u < kNdChains; ++u)
-        if (u == ch) {
-            k = st.nx[u];
-            dst = (row ? st.Rn[u] : st.Cn[u]) + (size_t)t * kBj * kBj;
-        }
-    const double *src = row ? M + (size_t)k * kBj * ld + (size_t)t * kBj : M + (size_t)t * kBj * ld + (size_t)k * kBj;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int e = threadIdx.x + 256 * q, r = e >> 5, c = 2 * (e & 31);
-        *reinterpret_cast<double2 *>(dst + r * kBj + c) = *reinterpret_cast<const double2 *>(src + (size_t)r * ld + c);
-    }
-}
-
-// --------------------------------------------------------------------------
-// V-cycle kernels
-// --------------------------------------------------------------------------
-
-enum SmoothMode {
-    kSweepFromZero = 0,   // x1 = w D^-1 b implicit, out = x1 + w D^-1 (b - A x1)
-    kSweep = 1,           // out = x + w D^-1 (b - A x)
-    kResid = 2,           // r = b - A x
-    kResidFromZero = 3    // x1 = w D^-1 b (written to out), r = b - A x1
-};
-
-template <int MODE>
-__device__ __forceinline__ void smooth_finish(int i, double ax, double w, const double *__restrict__ dinv,
-                                              const double *__restrict__ b, const double *__restrict__ x,
-                                              double *__restrict__ out, double *__restrict__ rout)
-{
-    constexpr bool implicit = (MODE == kSweepFromZero || MODE == kResidFromZero);
-    const double bi = b[i], di = dinv[i];
-    const double xi = implicit ? w * di * bi : x[i];
-    const double res = bi - ax;
-    if constexpr (MODE == kSweepFromZero || MODE == kSweep) out[i] = xi + w * di * res;
-    if constexpr (MODE == kResid || MODE == kResidFromZero) rout[i] = res;
-    if constexpr (MODE == kResidFromZero)
-        if (out) out[i] = xi;   // (a folded level-0 post-step recomputes x_pre: not written)
-}
-
-// smooth_finish with the row's b, D^-1 and x already loaded; returns out[i]
-template <int MODE>
-__device__ __forceinline__ double smooth_finish_v(int i, double ax, double w, double di, double bi, double xv,
-                                                  double *__restrict__ out, double *__restrict__ rout)
-{
-    constexpr bool implicit = (MODE == kSweepFromZero || MODE == kResidFromZero);
-    const double xi = implicit ? w * di * bi : xv;
-    const double res = bi - ax;
-    double o = xi;
-    if constexpr (MODE == kSweepFromZero || MODE == kSweep) {
-        o = xi + w * di * res;
-        out[i] = o;
-    }
-    if constexpr (MODE == kResid || MODE == kResidFromZero) rout[i] = res;
-    if constexpr (MODE == kResidFromZero)
-        if (out) out[i] = xi;   // (a folded level-0 post-step recomputes x_pre: not written)
-    return o;
-}
-
-// CSR-stream tile SpMV (the PCG's kernel shape): B = 1024 on level 0, 256 on
-// large coarse levels (more workgroups than CUs)
-// part_gam (the PCG's last level-0 sweep only): per-tile partials of
-// b . out, i.e. gamma = r . u of the CG, in the layout and summation order of
-// k_cg_spmv's (same tiles, same workgroup sum), so the SpMV need not read r
-template <int MODE, int B, int SLOTS = 2, class V = double>
-__global__ void __launch_bounds__(B) k_amg_smooth(int n, int ncl, const int *__restrict__ rowptr,
-                                                         const int *__restrict__ col, const V *__restrict__ val,
-                                                         const double *__restrict__ dinv,
-                                                         const unsigned long long *rho, const double *__restrict__ b,
-                                                         const double *__restrict__ x, double *__restrict__ out,
-                                                         double *__restrict__ rout, const int *done,
-                                                         double *__restrict__ part_gam, const int *__restrict__ tl,
-                                                         const unsigned short *__restrict__ c16 = nullptr,
-                                                         const int *__restrict__ cbase = nullptr)
-{
-    // the convergence flag, rho, the tile's row range and this row's b,
-    // D^-1, x are loaded together before the first branch
-    const int dn = load_flag_v(done);
-    __shared__ __attribute__((aligned(16))) double lds[4 * SLOTS * B];
-    const double ra = rho_of(rho);
-    const int t = tl ? tl[xcd_tile(blockIdx.x, gridDim.x)] : xcd_tile(blockIdx.x, gridDim.x);
-    const int r0 = t * B;
-    const int i = r0 + threadIdx.x;
-    constexpr bool implicit = (MODE == kSweepFromZero || MODE == kResidFromZero);
-    const TileRows tr = tile_rows<B>(r0, n, rowptr);
-    const int cb = load_col_base(cbase, t);
-    const double bi = i < n ? b[i] : 0.0, di = i < n ? dinv[i] : 0.0;
-    const double xv = (!implicit && i < n) ? x[i] : 0.0;
-    if (dn) return;
-    const double w = ra > 0.0 ? 1.0 / ra : 0.0;
-    double ax;
-    if constexpr (implicit)
-        ax = cg_tile_spmv16<B, SLOTS>(tr, c16, cb, col, val,
-                                      [&](int j) { return j < ncl ? w * dinv[j] * b[j] : 0.0; }, lds);
-    else
-        ax = cg_tile_spmv16<B, SLOTS>(tr, c16, cb, col, val, [&](int j) { return j < ncl ? x[j] : 0.0; }, lds);
-    double oi = 0.0;
-    if (i < n) oi = smooth_finish_v<MODE>(i, ax, w, di, bi, xv, out, rout);
-    if constexpr (MODE == kSweep) {
-        if (part_gam) {   // uniform per launch
-            __shared__ double red[2 * (B / 64)];
-            double g = 0.0, zero = 0.0;
-            if (i < n) g = bi * oi;
-            cg_block_sum2(zero, g, red);
-            if (threadIdx.x == 0) part_gam[t] = g;
-        }
-    }
-}
-
-// G lanes per row, strided over the row, butterfly sum inside the group
-template <int G, class XF>
-__device__ __forceinline__ double group_row_dot(int i, int n, const int *__restrict__ rowptr,
-                                                const int *__restrict__ col, const double *__restrict__ val, XF X)
-{
-    const int g = threadIdx.x & (G - 1);
-    double s = 0.0;
-    if (i < n)
-        for (int k = rowptr[i] + g; k < rowptr[i + 1]; k += G) s += val[k] * X(col[k]);
-#pragma unroll
-    for (int off = G >> 1; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
-
-// coarse levels: G lanes per row
-template <int MODE, int G>
-__global__ void __launch_bounds__(256) k_amg_smooth_g(int n, int ncl, const int *__restrict__ rowptr,
-                                                      const int *__restrict__ col, const double *__restrict__ val,
-                                                      const double *__restrict__ dinv, const unsigned long long *rho,
-                                                      const double *__restrict__ b, const double *__restrict__ x,
-                                                      double *__restrict__ out, double *__restrict__ rout,
-                                                      const int *done)
-{
-    if (done && *done) return;
-    const double ra = rho_of(rho);
-    const double w = ra > 0.0 ? 1.0 / ra : 0.0;
-    const int i = (xcd_tile(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x) / G;
-    constexpr bool implicit = (MODE == kSweepFromZero || MODE == kResidFromZero);
-    double ax;
-    if constexpr (implicit)
-        ax = group_row_dot<G>(i, n, rowptr, col, val, [&](int j) { return j < ncl ? w * dinv[j] * b[j] : 0.0; });
-    else
-        ax = group_row_dot<G>(i, n, rowptr, col, val, [&](int j) { return j < ncl ? x[j] : 0.0; });
-    if (i < n && (threadIdx.x & (G - 1)) == 0) smooth_finish<MODE>(i, ax, w, dinv, b, x, out, rout);
-}
-
-// y = M x (ACC: y += M x), tile form (large transfer operators)
-template <int B, bool ACC, int SLOTS = 2, class V = double>
-__global__ void __launch_bounds__(B) k_csr_mv_tile(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                   const V *__restrict__ val, const double *__restrict__ x,
-                                                   double *__restrict__ y, const int *done,
-                                                   const unsigned short *__restrict__ c16 = nullptr,
-                                                   const int *__restrict__ cbase = nullptr)
-{
-    const int dn = load_flag_v(done);
-    __shared__ __attribute__((aligned(16))) double lds[4 * SLOTS * B];
-    const int t = xcd_tile(blockIdx.x, gridDim.x);
-    const int r0 = t * B;
-    const int i = r0 + threadIdx.x;
-    const TileRows tr = tile_rows<B>(r0, n, rowptr);
-    const int cb = load_col_base(cbase, t);
-    const double y0 = (ACC && i < n) ? y[i] : 0.0;
-    if (dn) return;
-    const double s = cg_tile_spmv16<B, SLOTS>(tr, c16, cb, col, val, [&](int j) { return x[j]; }, lds);
-    if (i < n) y[i] = ACC ? y0 + s : s;
-}
-
-// y = M x (ACC: y += M x), G lanes per row (restriction R r, prolongation x += P xc)
-template <int G, bool ACC>
-__global__ void __launch_bounds__(256) k_csr_mv_g(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                  const double *__restrict__ val, const double *__restrict__ x,
-                                                  double *__restrict__ y, const int *done)
-{
-    if (done && *done) return;
-    const int i = (xcd_tile(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x) / G;
-    const double s = group_row_dot<G>(i, n, rowptr, col, val, [&](int j) { return x[j]; });
-    if (i < n && (threadIdx.x & (G - 1)) == 0) y[i] = ACC ? y[i] + s : s;
-}
 
 // Folded coarse level (V(1,1) with one Jacobi sweep, x_pre = w D^-1 b):
 //   pre   y  = x_pre + w D^-1 (b - A x_pre),  b_c = P~^T b
@@ -2397,141 +876,6 @@ __global__ void __launch_bounds__(256) k_refold_p(int n, const unsigned long lon
     }
 }
 
-// level 0, folded post-step (the pre-step stays sweep-from-0 + residual and
-// R r'): u = x_pre + w D^-1 r' + P~ x_c, i.e. the prolongation and the
-// post-sweep in one pass over P~ instead of P and A.  Tile shape and r.u
-// partials as k_amg_smooth's last sweep (the SpMV's tiles and summation order).
-template <int B, int SLOTS, class V>
-__global__ void __launch_bounds__(B) k_fold_post0(int n, const int *__restrict__ frow, const int *__restrict__ fcol,
-                                                  const V *__restrict__ fval, const double *__restrict__ xc,
-                                                  const double *__restrict__ dinv, const unsigned long long *rho,
-                                                  const double *__restrict__ rres,
-                                                  const double *__restrict__ b, double *__restrict__ out,
-                                                  const int *done, double *__restrict__ part_gam,
-                                                  const unsigned short *__restrict__ c16,
-                                                  const int *__restrict__ cbase)
-{
-    const int dn = load_flag_v(done);
-    __shared__ __attribute__((aligned(16))) double lds[4 * SLOTS * B];
-    const double ra = rho_of(rho);
-    const int t = xcd_tile(blockIdx.x, gridDim.x);
-    const int r0 = t * B;
-    const int i = r0 + threadIdx.x;
-    const TileRows tr = tile_rows<B>(r0, n, frow);
-    const int cb = load_col_base(cbase, t);
-    const double di = i < n ? dinv[i] : 0.0, bi = i < n ? b[i] : 0.0, ri = i < n ? rres[i] : 0.0;
-    if (dn) return;
-    const double w = ra > 0.0 ? 1.0 / ra : 0.0;
-    const double pc = cg_tile_spmv16<B, SLOTS>(tr, c16, cb, fcol, fval, [&](int j) { return xc[j]; }, lds);
-    double u = 0.0;
-    if (i < n) {
-        u = (w * di * bi + w * di * ri) + pc;
-        out[i] = u;
-    }
-    if (part_gam) {   // uniform per launch
-        __shared__ double red[2 * (B / 64)];
-        double g = 0.0, zero = 0.0;
-        if (i < n) g = bi * u;
-        cg_block_sum2(zero, g, red);
-        if (threadIdx.x == 0) part_gam[t] = g;
-    }
-}
-
-// the folded pre-step: workgroups [0, blocks_a) form y (GA lanes per fine
-// row), the rest b_c = P~^T b (GB lanes per coarse row)
-template <int GA, int GB>
-__global__ void __launch_bounds__(256) k_fold_pre(int n, int ncl, const int *__restrict__ rowptr,
-                                                  const int *__restrict__ col, const double *__restrict__ val,
-                                                  const double *__restrict__ dinv, const unsigned long long *rho,
-                                                  const double *__restrict__ b, double *__restrict__ y, int nc,
-                                                  const int *__restrict__ rrow, const int *__restrict__ rcol,
-                                                  const double *__restrict__ rval, double *__restrict__ bc,
-                                                  int blocks_a, const int *done, const double *__restrict__ yadd)
-{
-    if (done && *done) return;
-    // XCD-contiguous row blocks in each range (blocks_a is a multiple of 8):
-    // an XCD's L2 serves the vector entries its neighbouring rows share
-    if ((int)blockIdx.x < blocks_a) {
-        const double ra = rho_of(rho);
-        const double w = ra > 0.0 ? 1.0 / ra : 0.0;
-        const int i = (xcd_tile(blockIdx.x, blocks_a) * blockDim.x + threadIdx.x) / GA;
-        const double ax =
-            group_row_dot<GA>(i, n, rowptr, col, val, [&](int j) { return j < ncl ? w * dinv[j] * b[j] : 0.0; });
-        if (i < n && (threadIdx.x & (GA - 1)) == 0) {
-            const double di = dinv[i], bi = b[i], xi = w * di * bi;
-            const double yi = xi + w * di * (bi - ax);
-            y[i] = yadd ? yadd[i] + yi : yi;   // (a W-cycle's second correction adds onto the first)
-        }
-    } else {
-        const int c = (xcd_tile(blockIdx.x - blocks_a, gridDim.x - blocks_a) * blockDim.x + threadIdx.x) / GB;
-        const double sc = group_row_dot<GB>(c, nc, rrow, rcol, rval, [&](int j) { return b[j]; });
-        if (c < nc && (threadIdx.x & (GB - 1)) == 0) bc[c] = sc;
-    }
-}
-
-// x = M b, one 256-thread workgroup per row of the f32 inverse (ld a multiple
-// of 64, padding columns zero): every thread issues its 16-B loads (4 floats)
-// of the row at once, so the whole inverse is in flight (one wave per row
-// left a 1.6k-row inverse at 2.3 TB/s: 6 waves per CU, each walking its row
-// in dependent batches); products and sums in f64
-constexpr int kDmvLoads = 2;
-template <class V>
-struct DmvVec;
-template <>
-struct DmvVec<float> {
-    using T = float4;
-};
-template <>
-struct DmvVec<double> {
-    struct T {
-        double x, y, z, w;
-    };
-};
-// x = S M S b: row i of the symmetrised scaled inverse M (f32 or f64), the
-// scale osc in f64, products and sums in f64
-template <class V>
-__global__ void __launch_bounds__(256) k_dense_mv(int n, int ld, const V *__restrict__ M,
-                                                  const double *__restrict__ osc, const double *__restrict__ b,
-                                                  double *__restrict__ x, const int *done)
-{
-    if (done && *done) return;
-    using V4 = typename DmvVec<V>::T;
-    __shared__ double red[4];
-    const int i = blockIdx.x;
-    const V4 *Mi = reinterpret_cast<const V4 *>(M + (size_t)i * ld);
-    const int n4 = ld >> 2;
-    double s0 = 0.0, s1 = 0.0;
-    for (int j0 = 0; j0 < n4; j0 += 256 * kDmvLoads) {
-        V4 m[kDmvLoads];
-#pragma unroll
-        for (int q = 0; q < kDmvLoads; ++q) {
-            const int j = j0 + threadIdx.x + 256 * q;
-            if (j < n4) m[q] = Mi[j];
-            else m[q] = V4{0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int q = 0; q < kDmvLoads; ++q) {
-            const int c = 4 * (j0 + threadIdx.x + 256 * q);
-            if (c + 3 < n) {
-                const double2 b0 = *reinterpret_cast<const double2 *>(b + c);
-                const double2 b1 = *reinterpret_cast<const double2 *>(b + c + 2);
-                const double2 c0 = *reinterpret_cast<const double2 *>(osc + c);
-                const double2 c1 = *reinterpret_cast<const double2 *>(osc + c + 2);
-                s0 += (double)m[q].x * (c0.x * b0.x) + (double)m[q].z * (c1.x * b1.x);
-                s1 += (double)m[q].y * (c0.y * b0.y) + (double)m[q].w * (c1.y * b1.y);
-            } else {
-                if (c < n) s0 += (double)m[q].x * (osc[c] * b[c]);
-                if (c + 1 < n) s1 += (double)m[q].y * (osc[c + 1] * b[c + 1]);
-                if (c + 2 < n) s0 += (double)m[q].z * (osc[c + 2] * b[c + 2]);
-            }
-        }
-    }
-    const double w = cg_wave_sum(s0 + s1);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) x[i] = osc[i] * ((red[0] + red[1]) + (red[2] + red[3]));
-}
-
 // diagnostics (XFK_AMG_DEBUG): rows left without an aggregate, split by
 // whether they have strong (owned) couplings / any off-diagonal coupling
 __global__ void k_setup_zero(int *__restrict__ a, int na, unsigned long long *__restrict__ b, int nb_)
@@ -2554,17 +898,6 @@ __global__ void k_debug_unagg(int n, const int *__restrict__ rowptr, const int *
 // sharded level 0: helpers of the distributed Galerkin product and V-cycle
 // --------------------------------------------------------------------------
 
-// x = w D^-1 b: the first Jacobi sweep from zero, written out (its halo is
-// exchanged before the residual)
-__global__ void k_jacobi_first(int n, const unsigned long long *rho, const double *__restrict__ dinv,
-                               const double *__restrict__ b, double *__restrict__ x, const int *done)
-{
-    if (done && *done) return;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double ra = rho_of(rho);
-    x[i] = (ra > 0.0 ? 1.0 / ra : 0.0) * dinv[i] * b[i];
-}
 __global__ void k_row_len_d(int n, const int *__restrict__ rowptr, double *__restrict__ len)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2617,17 +950,6 @@ __global__ void k_concat_rowptr(int NC, int nranks, const int *__restrict__ c0, 
     while (c0[q + 1] <= I) ++q;
     out[I] = e0[q] + grow[(size_t)q * ld + (I - c0[q])];
 }
-// global coarse vector from the padded all-gather (stride ld per rank)
-__global__ void k_unpad(int NC, int nranks, const int *__restrict__ c0, const double *__restrict__ all, int ld,
-                        double *__restrict__ out, const int *done)
-{
-    if (done && *done) return;
-    const int I = blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= NC) return;
-    int q = 0;
-    while (c0[q + 1] <= I) ++q;
-    out[I] = all[(size_t)q * ld + (I - c0[q])];
-}
 
 }  // namespace
 
@@ -2646,15 +968,6 @@ Amg::~Amg()
     delete trace;
 }
 
-#define AMG_CHECK(call)                                                          \
-    do {                                                                         \
-        hipError_t _e = (call);                                                  \
-        if (_e != hipSuccess) {                                                  \
-            ::xfk::set_error(std::string(#call) + ": " + hipGetErrorString(_e)); \
-            return XFK_ERR_HIP;                                                  \
-        }                                                                        \
-    } while (0)
-
 namespace {
 
 // out[0..n] = exclusive scan of in[0..n-1], out[n] = total; returns total
@@ -2664,9 +977,6 @@ namespace {
 // registers, a workgroup scan of the thread sums gives the offsets, and the
 // prefixes are stored -- one memory round trip each way.
 constexpr int kScanLds = 16384;
-
-// levels / transfer operators with at least this many rows use the tile kernels
-constexpr int kTileMinRows = 16384;
 
 __global__ void __launch_bounds__(1024) k_scan_lds(int n, const int *__restrict__ in, int *__restrict__ out)
 {
@@ -2710,6 +1020,9 @@ __global__ void __launch_bounds__(1024) k_scan_lds(int n, const int *__restrict_
     if (threadIdx.x == 0) out[0] = 0;
 }
 
+}  // namespace
+
+// (declared in xfk_amg_impl.h: the SpGEMM driver scans its row lengths too)
 int scan_total(Amg &A, hipStream_t s, const int *in, int *out, int n, long long &total)
 {
     if (n <= kScanLds) {
@@ -2755,264 +1068,12 @@ int read_flag(Amg &A, hipStream_t s, int idx, int &v)
     return XFK_OK;
 }
 
-// C = X Y (rowptr/col/val allocated here); XFK_ERR_UNSUPPORTED on LDS overflow
-// XFK_SPGEMM_SLAB=0: the sub-wave SpGEMM writes padded rows (row * cap) and the
-// compaction moves them row by row (the layout before the dense slabs)
-static bool spgemm_slab_on()
-{
-    return env_int("XFK_SPGEMM_SLAB", 1) != 0;
-}
 // XFK_SPGEMM_PACK=0: the Galerkin products sort (column, value) pairs like the
 // prolongator's (read per setup: tests toggle it)
 static bool spgemm_pack_on()
 {
     return env_int("XFK_SPGEMM_PACK", 1) != 0;
 }
-
-// rows per k_spgemm_sort wavefront (64 / G of the instance launch_sort takes for `cap`)
-static int sort_rows_per_wave(int cap) { return cap == 16 ? 16 : cap <= 64 ? 8 : cap == 128 ? 4 : 2; }
-
-// slab_n: the slab lengths (null: padded rows)
-void launch_compact(hipStream_t s, int nrows, int cap, const int *crow, const int *slab_n, const int *pc,
-                    const double *pv, int *ccol, double *cval, int *nnz_out)
-{
-    if (slab_n) {
-        const int W = sort_rows_per_wave(cap), nslab = (nrows + W - 1) / W;
-        k_spgemm_compact_slab<<<(unsigned)(((long long)nslab * kSlabLanes + kB - 1) / kB), kB, 0, s>>>(
-            nrows, nslab, W, W * cap, crow, slab_n, pc, pv, ccol, cval, nnz_out);
-    } else if (cap <= 16)
-        k_spgemm_compact<4><<<(unsigned)(((long long)nrows * 4 + kB - 1) / kB), kB, 0, s>>>(nrows, cap, crow, pc, pv,
-                                                                                             ccol, cval, nnz_out);
-    else if (cap <= 32)
-        k_spgemm_compact<8><<<(unsigned)(((long long)nrows * 8 + kB - 1) / kB), kB, 0, s>>>(nrows, cap, crow, pc, pv,
-                                                                                             ccol, cval, nnz_out);
-    else
-        k_spgemm_compact<16><<<(unsigned)(((long long)nrows * 16 + kB - 1) / kB), kB, 0, s>>>(nrows, cap, crow, pc,
-                                                                                               pv, ccol, cval, nnz_out);
-}
-
-template <bool PMODE>
-int spgemm(Amg &M, hipStream_t s, int nrows, const SgX &X, const SgY &Y, DBuf<int> &crow, DBuf<int> &ccol,
-           DBuf<double> &cval, long long &cnnz, int key = -1, bool defer = true)
-{
-    // (behind the row lengths: the slab lengths, at most one per two rows)
-    AMG_CHECK(M.cnt.alloc((size_t)nrows + 1 + ((size_t)nrows + 1) / 2));
-    AMG_CHECK(crow.alloc((size_t)nrows + 1));
-    int *slab_n = spgemm_slab_on() ? M.cnt.p + nrows + 1 : nullptr;
-    // the sort kernel of the capacity class (rows of at most `cap` slots,
-    // nrows * cap slots in pad_col / pad_val in either layout)
-    int *sovf = M.dev_int.p + 6;
-    auto launch_sort = [&](int cap, int *ovf, int *need = nullptr) {
-        int *pc = M.pad_col.p;
-        double *pv = M.pad_val.p;
-        if (nrows > 0) {
-            // few lanes per row, 4-8 sorted slots per lane: many rows per
-            // wavefront to overlap their dependent gathers
-#define XFK_SORT(GG, CC, WW)                                                                                  \
-    do {                                                                                                      \
-        bool packed = false;                                                                                  \
-        if constexpr (!PMODE) {                                                                               \
-            if (X.pack) {                                                                                     \
-                k_spgemm_sort<PMODE, GG, CC, true><<<(nrows + WW - 1) / WW, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, \
-                                                                                         ovf, need, slab_n); \
-                packed = true;                                                                                \
-            }                                                                                                 \
-        }                                                                                                     \
-        if (!packed)                                                                                          \
-            k_spgemm_sort<PMODE, GG, CC><<<(nrows + WW - 1) / WW, 64, 0, s>>>(nrows, X, Y, M.cnt.p, pc, pv, ovf, need, \
-                                                                               slab_n);                       \
-    } while (0)
-            if (cap == 16) XFK_SORT(4, 16, 16);
-            else if (cap == 32) XFK_SORT(8, 32, 8);
-            else if (cap == 64) XFK_SORT(8, 64, 8);
-            else if (cap == 128) XFK_SORT(16, 128, 4);
-            else XFK_SORT(32, 256, 2);
-#undef XFK_SORT
-        }
-    };
-    // single pass into padded rows of `cap` slots (sort-based), then scan +
-    // compaction; returns the overflow flag (rows with more products than
-    // slots), read back with the scan's own synchronisation
-    auto sort_pass = [&](int cap, bool &overflow) -> int {
-        AMG_CHECK(M.pad_col.alloc((size_t)nrows * cap));
-        AMG_CHECK(M.pad_val.alloc((size_t)nrows * cap));
-        AMG_CHECK(hipMemsetAsync(sovf, 0, sizeof(int), s));
-        launch_sort(cap, sovf);
-        AMG_CHECK(hipMemcpyAsync(M.host_int + 4, sovf, sizeof(int), hipMemcpyDeviceToHost, s));
-        int rc = scan_total(M, s, M.cnt.p, crow.p, nrows, cnnz);   // synchronises
-        if (rc != XFK_OK) return rc;
-        overflow = M.host_int[4] != 0;
-        if (overflow) return XFK_OK;
-        AMG_CHECK(ccol.alloc((size_t)std::max(1LL, cnnz)));
-        AMG_CHECK(cval.alloc((size_t)std::max(1LL, cnnz)));
-        if (nrows > 0)
-            launch_compact(s, nrows, cap, crow.p, slab_n, M.pad_col.p, M.pad_val.p, ccol.p, cval.p, nullptr);
-        return XFK_OK;
-    };
-    // the slot capacity this product needed in the previous setup (same
-    // call site): taken without measuring the longest product list first,
-    // and without any host synchronisation -- the output is sized for
-    // nrows x cap, its length and the kernel's overflow flag land in a
-    // deferred slot that the setup reads once at its end (an overflow there
-    // rebuilds the hierarchy with measured capacities)
-    auto deferred_pass = [&](int cap, bool verify = false) -> int {
-        int *slot = M.def_dev.p + M.def_n;
-        // (a capacity from another problem: its class is checked on the device)
-        int *need = (verify && cap > 16) ? M.def_dev.p + kAmgDeferSlots + M.def_n / 2 : nullptr;
-        M.def_verify[M.def_n / 2] = need ? cap : 0;
-        AMG_CHECK(M.pad_col.alloc((size_t)nrows * cap));
-        AMG_CHECK(M.pad_val.alloc((size_t)nrows * cap));
-        AMG_CHECK(ccol.alloc((size_t)std::max(1LL, (long long)nrows * cap)));
-        AMG_CHECK(cval.alloc((size_t)std::max(1LL, (long long)nrows * cap)));
-        launch_sort(cap, slot, need);
-        int rc = scan_only(M, s, M.cnt.p, crow.p, nrows);
-        if (rc != XFK_OK) return rc;
-        if (nrows > 0)
-            launch_compact(s, nrows, cap, crow.p, slab_n, M.pad_col.p, M.pad_val.p, ccol.p, cval.p, slot + 1);
-        else
-            AMG_CHECK(hipMemsetAsync(slot + 1, 0, sizeof(int), s));
-        M.def_target[M.def_n / 2] = &cnnz;
-        M.def_n += 2;
-        cnnz = (long long)nrows * cap;   // an upper bound until the deferred read
-        return XFK_OK;
-    };
-    if (key >= 0) {
-        auto hint = M.cap_hint.find(key);
-        if (hint != M.cap_hint.end()) {
-            if (defer && M.def_n + 2 <= kAmgDeferSlots) return deferred_pass(hint->second, M.foreign);
-            if (M.foreign) {   // (no slot to check another problem's capacity in: measure)
-                M.cap_hint.erase(hint);
-                hint = M.cap_hint.end();
-            }
-        }
-        if (hint != M.cap_hint.end()) {
-            bool overflow = false;
-            int rc = sort_pass(hint->second, overflow);
-            if (rc != XFK_OK || !overflow) return rc;
-            M.cap_hint.erase(hint);
-        }
-    }
-    // longest product list -> sub-wave (<= 64 products per row) or wave-per-row kernels
-    int maxprod = 0;
-    if (nrows > 0) {
-        k_spgemm_nprod<PMODE><<<nb(nrows), kB, 0, s>>>(nrows, X, Y, M.cnt.p);
-        size_t bytes = 0;
-        AMG_CHECK(hipcub::DeviceReduce::Max(nullptr, bytes, M.cnt.p, M.dev_int.p + 3, nrows, s));
-        AMG_CHECK(M.cub_tmp.alloc(bytes ? bytes : 1));
-        AMG_CHECK(hipcub::DeviceReduce::Max(M.cub_tmp.p, bytes, M.cnt.p, M.dev_int.p + 3, nrows, s));
-        int rc = read_flag(M, s, 3, maxprod);
-        if (rc != XFK_OK) return rc;
-    }
-    if (maxprod <= kSortCap) {
-        const int cap = maxprod <= 16 ? 16 : maxprod <= 32 ? 32 : maxprod <= 64 ? 64 : maxprod <= 128 ? 128 : 256;
-        int rc = XFK_OK;
-        if (defer && key >= 0 && M.def_n + 2 <= kAmgDeferSlots) {
-            // the measured capacity (no overflow possible) through the
-            // deferred slot as a hinted one: the same kernels, so the same
-            // bits, without the host check for the length (~20 us per call
-            // site of a first setup)
-            rc = deferred_pass(cap);
-        } else {
-            bool overflow = false;
-            rc = sort_pass(cap, overflow);
-            if (rc == XFK_OK && overflow) {
-                set_error("AMG: internal SpGEMM capacity error");
-                return XFK_ERR_HIP;
-            }
-        }
-        if (rc != XFK_OK) return rc;
-        if (key >= 0) {
-            // XFK_AMG_TEST_SMALL_HINT=1 (tests only): store a too-small capacity so
-            // the next setup takes the overflow-and-rebuild path
-            const bool small = env_set("XFK_AMG_TEST_SMALL_HINT");
-            M.cap_hint[key] = small ? 16 : cap;   // (16: the smallest capacity the kernels have)
-        }
-        return XFK_OK;
-    }
-    AMG_CHECK(hipMemsetAsync(M.dev_int.p + 2, 0, 2 * sizeof(int), s));
-    if (nrows > 0)
-        k_spgemm<false, PMODE, kSgMax><<<nrows, 64, 0, s>>>(nrows, X, Y, M.cnt.p, nullptr, nullptr, nullptr,
-                                                            M.dev_int.p + 2);
-    if (nrows > 0) {   // longest row -> LDS capacity of the FILL pass
-        size_t bytes = 0;
-        AMG_CHECK(hipcub::DeviceReduce::Max(nullptr, bytes, M.cnt.p, M.dev_int.p + 3, nrows, s));
-        AMG_CHECK(M.cub_tmp.alloc(bytes ? bytes : 1));
-        AMG_CHECK(hipcub::DeviceReduce::Max(M.cub_tmp.p, bytes, M.cnt.p, M.dev_int.p + 3, nrows, s));
-    }
-    AMG_CHECK(hipMemcpyAsync(M.host_int + 2, M.dev_int.p + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    int rc = scan_total(M, s, M.cnt.p, crow.p, nrows, cnnz);   // synchronises
-    if (rc != XFK_OK) return rc;
-    const int ovf = M.host_int[2], maxrow = M.host_int[3];
-    if (ovf) {
-        set_error("AMG: a SpGEMM row exceeds the LDS hash capacity");
-        return XFK_ERR_UNSUPPORTED;
-    }
-    AMG_CHECK(ccol.alloc((size_t)std::max(1LL, cnnz)));
-    AMG_CHECK(cval.alloc((size_t)std::max(1LL, cnnz)));
-    if (nrows > 0) {
-        int *of = M.dev_int.p + 2;
-        if (maxrow <= 32)
-            k_spgemm<true, PMODE, 32><<<nrows, 64, 0, s>>>(nrows, X, Y, nullptr, crow.p, ccol.p, cval.p, of);
-        else if (maxrow <= 128)
-            k_spgemm<true, PMODE, 128><<<nrows, 64, 0, s>>>(nrows, X, Y, nullptr, crow.p, ccol.p, cval.p, of);
-        else
-            k_spgemm<true, PMODE, kSgMax><<<nrows, 64, 0, s>>>(nrows, X, Y, nullptr, crow.p, ccol.p, cval.p, of);
-    }
-    return XFK_OK;
-}
-
-// lanes per row for a CSR with this many nonzeros per row on average
-int lanes_for(double per_row)
-{
-    return per_row <= 6.0 ? 4 : (per_row <= 20.0 ? 8 : 16);
-}
-
-// level 0 with f32 values: the 256-row tile kernels (level 0 always has >= kTileMinRows rows)
-// (128- and 64-row tiles for R's ~25-entry rows were measured slower: 14.4 -> 15.0 / 15.6 us,
-// profiles/r04_experiments/r04h_XFK_R0_TILE_*.json)
-// staging slots per lane for the long rows: 6 = 6144 products per pass (R's
-// ~27-entry rows fill 256-row tiles with ~6900); 8 / 7 (one pass, 64 / 56 KiB
-// of LDS) measured 20.3 / 20.2 us vs 14.7 us
-void launch_mv32(hipStream_t s, int n, const int *rowptr, const int *col, const float *val, const double *x,
-                 double *y, bool acc, int G, const int *done, const unsigned short *c16, const int *cbase)
-{
-    if (n <= 0) return;
-    const int g = (n + 255) / 256;
-    if (G <= 4) {
-        if (acc) k_csr_mv_tile<256, true, 2><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-        else k_csr_mv_tile<256, false, 2><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-    } else {
-        if (acc) k_csr_mv_tile<256, true, 6><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-        else k_csr_mv_tile<256, false, 6><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-    }
-}
-
-// c16 / cbase: 16-bit column offsets in 256-row tiles (used by the 256-row tile kernels only)
-void launch_mv(hipStream_t s, int n, const int *rowptr, const int *col, const double *val, const double *x, double *y,
-               bool acc, int G, const int *done, const unsigned short *c16 = nullptr, const int *cbase = nullptr)
-{
-    if (n <= 0) return;
-    if (n >= kTileMinRows && G <= 8) {
-        // G = 8: 7..20 entries per row -> 6 slots per lane, one staging pass per tile
-        const int g = (n + 255) / 256;
-        if (G <= 4) {
-            if (acc) k_csr_mv_tile<256, true, 2><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-            else k_csr_mv_tile<256, false, 2><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-        } else {
-            if (acc) k_csr_mv_tile<256, true, 6><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-            else k_csr_mv_tile<256, false, 6><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done, c16, cbase);
-        }
-        return;
-    }
-    const int g = (int)(((long long)n * G + 255) / 256);
-#define XFK_MV(GG)                                                                                        \
-    if (acc) k_csr_mv_g<GG, true><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done);                    \
-    else k_csr_mv_g<GG, false><<<g, 256, 0, s>>>(n, rowptr, col, val, x, y, done);
-    if (G == 4) { XFK_MV(4) } else if (G == 8) { XFK_MV(8) } else { XFK_MV(16) }
-#undef XFK_MV
-}
-
-}  // namespace
 
 // tile t reads a halo column (>= n) in one of its rows
 __global__ void k_tile_halo_flags(int n, int B, const int *__restrict__ rowptr, const int *__restrict__ col,
@@ -3305,7 +1366,6 @@ HintStore &hint_store()
     static HintStore *h = new HintStore();   // (never destroyed, like the device caches)
     return *h;
 }
-bool foreign_on() { return !env_set("XFK_AMG_NO_FOREIGN"); }
 }  // namespace
 
 }  // namespace xfk
@@ -3628,342 +1688,6 @@ int Amg::joins_and_p_impl(hipStream_t s, int l)
     // (a sharded level needs P's length on the host at once -- the halo rows'
     // plan -- so it takes its capacity hint without deferring the length)
     return spgemm<true>(*this, s, n, XS, YT, A.prow, A.pcol, A.pval, A.pnnz, 4 * l, !A.dist);
-}
-
-// Nested-dissection order of the coarsest level for the dense inverse: a
-// recursive bisection -- left = the first half of the rows (the levels are
-// numbered along the fine level's Cuthill-McKee order, so the halves are
-// banded slabs), right = the other rows without an entry in the left half,
-// separator = those with one (about one grid line).  Two tree levels give
-// four leaves (four pivot chains per launch), then their two separators,
-// then the top separator; one level two leaves.  Groups are padded with
-// identity rows to whole blocks, the groups of one phase to equal block
-// counts.  Falls back to one level, then to the plain order, when a
-// separator would be empty or hold more than a quarter of the rows.
-// Host-synchronising (the coarsest level has <= dense_max rows).
-namespace {
-void nd_split_at(const std::vector<int> &rp, const std::vector<int> &cl, const std::vector<int> &rows, size_t h,
-                 std::vector<char> &inl, std::vector<int> &L, std::vector<int> &R, std::vector<int> &S)
-{
-    L.assign(rows.begin(), rows.begin() + h);
-    R.clear();
-    S.clear();
-    for (int r : L) inl[r] = 1;
-    for (size_t t = h; t < rows.size(); ++t) {
-        const int r = rows[t];
-        bool cross = false;
-        for (int k = rp[r]; k < rp[r + 1] && !cross; ++k) cross = inl[cl[k]] != 0;
-        (cross ? S : R).push_back(r);
-    }
-    for (int r : L) inl[r] = 0;
-}
-// split position chosen so that the two parts (not counting the separator)
-// come out about equal: the chain length of a phase is its largest part
-void nd_bisect(const std::vector<int> &rp, const std::vector<int> &cl, const std::vector<int> &rows,
-               std::vector<char> &inl, std::vector<int> &L, std::vector<int> &R, std::vector<int> &S)
-{
-    nd_split_at(rp, cl, rows, rows.size() / 2, inl, L, R, S);
-    const size_t h = (rows.size() - S.size()) / 2;
-    if (h > 0 && h != rows.size() / 2) nd_split_at(rp, cl, rows, h, inl, L, R, S);
-}
-}  // namespace
-
-int Amg::nd_order(hipStream_t s, const AmgLevel &C, int &ld)
-{
-    const int n = C.n;
-    nd_phases.clear();
-    ld = ((n + kBj - 1) / kBj) * kBj;
-    if (n < 8 * kBj || env_set("XFK_NO_ND")) {
-        nd_key_n = -1;
-        return XFK_OK;
-    }
-    // the pattern through pinned memory; an unchanged pattern (the next setup
-    // of the same matrix family) keeps the plan and its device arrays
-    const size_t npat = (size_t)n + 1 + (size_t)C.nnz;
-    {
-        int rc = host_ints((int)npat);
-        if (rc != XFK_OK) return rc;
-        AMG_CHECK(hipMemcpyAsync(host_big, C.rowptr, sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s));
-        AMG_CHECK(hipMemcpyAsync(host_big + n + 1, C.col, sizeof(int) * C.nnz, hipMemcpyDeviceToHost, s));
-        AMG_CHECK(hipStreamSynchronize(s));
-    }
-    if (nd_key.size() == npat && std::equal(nd_key.begin(), nd_key.end(), host_big)) {
-        nd_phases = nd_phases_key;
-        ld = nd_ld;
-        return XFK_OK;
-    }
-    nd_key.assign(host_big, host_big + npat);
-    // the device copy of the key: the next setup compares its coarsest
-    // pattern on the device and applies this plan without a host read
-    AMG_CHECK(nd_key_dev.alloc(npat));
-    AMG_CHECK(hipMemcpyAsync(nd_key_dev.p, C.rowptr, sizeof(int) * (n + 1), hipMemcpyDeviceToDevice, s));
-    AMG_CHECK(hipMemcpyAsync(nd_key_dev.p + n + 1, C.col, sizeof(int) * C.nnz, hipMemcpyDeviceToDevice, s));
-    nd_key_n = n;
-    nd_key_nnz = C.nnz;
-    nd_phases_key.clear();
-    nd_ld = ld;
-    std::vector<int> rp(host_big, host_big + n + 1), cl(host_big + n + 1, host_big + npat);
-    for (int r = 0; r < n; ++r)   // columns >= n (none on a level built here) are dropped by the scatter
-        for (int k = rp[r]; k < rp[r + 1]; ++k) cl[k] = std::min(cl[k], n);
-    std::vector<char> inl(n + 1, 0);
-    std::vector<int> all(n);
-    for (int r = 0; r < n; ++r) all[r] = r;
-    // groups: rows, phase, slot in the phase, parent separator group, subtree groups
-    struct G {
-        std::vector<int> rows;
-        int phase, slot, parent;
-        std::vector<int> sub;
-    };
-    std::vector<G> g;
-    // the deepest bisection (3, 2, then 1 level) whose groups are all non-empty,
-    // whose separators hold at most a quarter of the rows, and whose leaves
-    // keep >= 1 block; leaves are phase 0 (slots = leaf index), the
-    // separators of bisection level lev are phase D - lev
-    // The bisection levels are computed once: nd_bisect is a function of its
-    // set, so the first D levels of a deeper bisection are the D-level one and
-    // every depth reads the same splits (no recomputation per depth tried)
-    const int Dmax = n >= 24 * kBj ? 3 : (n >= 16 * kBj ? 2 : 1);
-    std::vector<std::vector<std::vector<int>>> lev_sets(Dmax + 1), lev_seps(Dmax);
-    std::vector<size_t> lev_nsep(Dmax, 0);
-    int lev_done = 0;   // levels computed, each with all its groups non-empty
-    lev_sets[0].push_back(all);
-    for (int lev = 0; lev < Dmax; ++lev) {
-        bool okl = true;
-        for (const auto &x : lev_sets[lev]) {
-            std::vector<int> L, R, S;
-            nd_bisect(rp, cl, x, inl, L, R, S);
-            okl = okl && !L.empty() && !R.empty() && !S.empty();
-            lev_nsep[lev] += S.size();
-            lev_sets[lev + 1].push_back(std::move(L));
-            lev_sets[lev + 1].push_back(std::move(R));
-            lev_seps[lev].push_back(std::move(S));
-        }
-        if (!okl) break;
-        lev_done = lev + 1;
-    }
-    for (int D = Dmax; D >= 1 && g.empty(); --D) {
-        bool ok = lev_done >= D;
-        size_t nsep = 0;
-        for (int lev = 0; lev < D && lev < Dmax; ++lev) nsep += lev_nsep[lev];
-        const std::vector<std::vector<int>> &sets = lev_sets[std::min(D, lev_done + 1)];
-        const std::vector<std::vector<std::vector<int>>> &seps = lev_seps;
-        if (env_set("XFK_AMG_DEBUG")) {
-            std::fprintf(stderr, "[amg] nested dissection depth %d: ok %d separators %zu, sets", D, (int)ok, nsep);
-            for (const auto &x : sets) std::fprintf(stderr, " %zu", x.size());
-            std::fprintf(stderr, "\n");
-        }
-        if (!ok || 3 * nsep > (size_t)n) continue;
-        if (D > 1)
-            for (const auto &x : sets) ok = ok && x.size() >= (size_t)kBj;
-        if (!ok) continue;
-        // group indices: leaves 0 .. 2^D - 1, then separators by level, deepest first
-        const int nl = 1 << D;
-        std::vector<int> sep_at(D);   // first group index of level lev's separators
-        int q = nl;
-        for (int lev = D - 1; lev >= 0; --lev) {
-            sep_at[lev] = q;
-            q += 1 << lev;
-        }
-        g.resize(q);
-        for (int k = 0; k < nl; ++k)
-            g[k] = {sets[k], 0, k, sep_at[D - 1] + (k >> 1), {k}};
-        for (int lev = D - 1; lev >= 0; --lev)
-            for (int m = 0; m < (1 << lev); ++m) {
-                G &x = g[sep_at[lev] + m];
-                x.rows = seps[lev][m];
-                x.phase = D - lev;
-                x.slot = m;
-                x.parent = lev > 0 ? sep_at[lev - 1] + (m >> 1) : -1;
-                // subtree: leaves and deeper separators under this one, and itself
-                for (int k = 0; k < nl; ++k)
-                    if ((k >> (D - lev)) == m) x.sub.push_back(k);
-                for (int l2 = lev + 1; l2 < D; ++l2)
-                    for (int m2 = 0; m2 < (1 << l2); ++m2)
-                        if ((m2 >> (l2 - lev)) == m) x.sub.push_back(sep_at[l2] + m2);
-                x.sub.push_back(sep_at[lev] + m);
-            }
-    }
-    if (g.empty()) return XFK_OK;
-    if (env_set("XFK_AMG_DEBUG")) {
-        std::fprintf(stderr, "[amg] coarsest %d rows: nested dissection, %d groups:", n, (int)g.size());
-        for (const G &x : g) std::fprintf(stderr, " %d/%d", (int)x.rows.size(), x.phase);
-        std::fprintf(stderr, "\n");
-    }
-    const int nph = g.back().phase + 1;
-    // blocks: each phase's groups padded to the phase's largest group
-    std::vector<int> pblk(nph, 0), b0(g.size());
-    for (const G &x : g) pblk[x.phase] = std::max(pblk[x.phase], (int)((x.rows.size() + kBj - 1) / kBj));
-    int nbk = 0;
-    for (size_t q = 0; q < g.size(); ++q) {
-        b0[q] = nbk;
-        nbk += pblk[g[q].phase];
-    }
-    ld = nbk * kBj;
-    std::vector<int> perm(n), iperm(ld, -1);
-    for (size_t q = 0; q < g.size(); ++q)
-        for (size_t t = 0; t < g[q].rows.size(); ++t) {
-            perm[g[q].rows[t]] = b0[q] * kBj + (int)t;
-            iperm[b0[q] * kBj + (int)t] = g[q].rows[t];
-        }
-    // per phase: region masks (bit = slot) and the tiles some chain holds
-    std::vector<unsigned char> mask((size_t)nph * nbk, 0);
-    std::vector<int> tl;
-    for (int ph = 0; ph < nph; ++ph) {
-        unsigned char *m = mask.data() + (size_t)ph * nbk;
-        NdPhase P{};
-        P.steps = pblk[ph];
-        for (size_t q = 0; q < g.size(); ++q) {
-            if (g[q].phase != ph) continue;
-            P.base[g[q].slot] = b0[q];
-            P.nch = std::max(P.nch, g[q].slot + 1);
-            P.next_slot[g[q].slot] = g[q].parent >= 0 ? g[g[q].parent].slot : -1;
-            std::vector<int> reg = g[q].sub;
-            for (int a = g[q].parent; a >= 0; a = g[a].parent) reg.push_back(a);
-            for (int x : reg)
-                for (int bb = 0; bb < pblk[g[x].phase]; ++bb) m[b0[x] + bb] |= (unsigned char)(1u << g[q].slot);
-        }
-        P.tiles_off = (int)tl.size();
-        for (int i = 0; i < nbk; ++i)
-            for (int j = 0; j < nbk; ++j)
-                if (m[i] & m[j]) tl.push_back(i * nbk + j);
-        P.ntiles = (int)tl.size() - P.tiles_off;
-        nd_phases.push_back(P);
-    }
-    AMG_CHECK(cinv_perm.alloc(n));
-    AMG_CHECK(cinv_iperm.alloc(ld));
-    AMG_CHECK(nd_mask.alloc(mask.size()));
-    AMG_CHECK(nd_tiles.alloc(tl.size()));
-    // uploads from a pinned staging copy (no host check: the staging buffer
-    // is rewritten only after the next setup's synchronising pattern read)
-    const size_t bytes = sizeof(int) * ((size_t)n + ld + tl.size()) + mask.size();
-    if (nd_stage_n < bytes) {
-        pinned_free(nd_stage);   // (outside a destroy: hipHostFree)
-        nd_stage = nullptr;
-        nd_stage_n = 0;
-        AMG_CHECK(pinned_malloc((void **)&nd_stage, bytes));
-        nd_stage_n = bytes;
-    }
-    char *h = nd_stage;
-    std::memcpy(h, perm.data(), sizeof(int) * n);
-    std::memcpy(h + sizeof(int) * n, iperm.data(), sizeof(int) * ld);
-    std::memcpy(h + sizeof(int) * ((size_t)n + ld), tl.data(), sizeof(int) * tl.size());
-    std::memcpy(h + sizeof(int) * ((size_t)n + ld + tl.size()), mask.data(), mask.size());
-    if (foreign_on()) {   // (the plan's device arrays for the next fresh problem of this size)
-        nd_plan.assign(h, h + bytes);
-        nd_tl_n = tl.size();
-        nd_mask_n = mask.size();
-    }
-    AMG_CHECK(hipMemcpyAsync(cinv_perm.p, h, sizeof(int) * n, hipMemcpyHostToDevice, s));
-    AMG_CHECK(hipMemcpyAsync(cinv_iperm.p, h + sizeof(int) * n, sizeof(int) * ld, hipMemcpyHostToDevice, s));
-    AMG_CHECK(hipMemcpyAsync(nd_tiles.p, h + sizeof(int) * ((size_t)n + ld), sizeof(int) * tl.size(),
-                             hipMemcpyHostToDevice, s));
-    AMG_CHECK(hipMemcpyAsync(nd_mask.p, h + sizeof(int) * ((size_t)n + ld + tl.size()), mask.size(),
-                             hipMemcpyHostToDevice, s));
-    nd_phases_key = nd_phases;
-    nd_ld = ld;
-    return XFK_OK;
-}
-
-// the dense coarsest inverse of C in the order nd_phases / cinv_perm give
-// (ld: the padded size of that order)
-int Amg::dense_inverse(hipStream_t s, const AmgLevel &C, int ld)
-{
-    const bool nd = !nd_phases.empty();
-    const int nbk = ld / kBj;
-    cinv_ld = ld;
-    AMG_CHECK(cinv.alloc((size_t)ld * ld));
-    const size_t T2 = (size_t)kBj * kBj;
-    // per chain slot and parity: row / column snapshots and the pivot inverse
-    const size_t per = 2 * (size_t)nbk * T2 + T2;
-    AMG_CHECK(bgj_tmp.alloc(2 * kNdChains * per + 1 + ld));
-    auto Rb = [&](int c, int q) { return bgj_tmp.p + (size_t)(2 * c + q) * per; };
-    auto Cb = [&](int c, int q) { return Rb(c, q) + (size_t)nbk * T2; };
-    auto Db = [&](int c, int q) { return Rb(c, q) + 2 * (size_t)nbk * T2; };
-    double *maxd = bgj_tmp.p + 2 * kNdChains * per, *sc = maxd + 1;
-    const int *pm = nd ? cinv_perm.p : nullptr, *ipm = nd ? cinv_iperm.p : nullptr;
-    AMG_CHECK(hipMemsetAsync(cinv.p, 0, sizeof(double) * (size_t)ld * ld, s));
-    k_dense_dscale<<<nb((long long)ld * kDsG), kB, 0, s>>>(C.n, ld, C.rowptr, C.col, C.val, ipm, sc);
-    k_dense_scatter<<<nb((long long)ld * kDsG), kB, 0, s>>>(C.n, ld, C.rowptr, C.col, C.val, pm, ipm, sc, cinv.p);
-    k_dense_maxdiag<<<1, 1024, 0, s>>>(ld, ld, cinv.p, maxd);
-    // (a lookahead variant -- block column k+1 first, its pivot block
-    // inverted on a second stream during the rest of the update -- was
-    // measured slower: the two cross-stream waits cost ~15 us per step,
-    // more than the 25 us pivot-block inversion it hides)
-    if (nd) {
-        int par = 0;
-        BgjStep st{};
-        st.nn = nd_phases[0].nch;
-        for (int c = 0; c < st.nn; ++c) {
-            st.nx[c] = nd_phases[0].base[c];
-            st.Dn[c] = Db(c, 0);
-            st.Rn[c] = Rb(c, 0);
-            st.Cn[c] = Cb(c, 0);
-        }
-        k_bgj_init<<<st.nn * (1 + 2 * nbk), 256, 0, s>>>(nbk, ld, cinv.p, st, maxd);
-        for (size_t ph = 0; ph < nd_phases.size(); ++ph) {
-            const NdPhase &P = nd_phases[ph];
-            for (int t = 0; t < P.steps; ++t) {
-                const int pp = par, qq = par ^ 1;
-                BgjStep x{};
-                x.n = P.nch;
-                for (int c = 0; c < P.nch; ++c) {
-                    x.k[c] = P.base[c] + t;
-                    x.D[c] = Db(c, pp);
-                    x.R[c] = Rb(c, pp);
-                    x.C[c] = Cb(c, pp);
-                }
-                if (t + 1 < P.steps) {
-                    x.nn = P.nch;
-                    for (int c = 0; c < P.nch; ++c) x.nx[c] = P.base[c] + t + 1;
-                } else if (ph + 1 < nd_phases.size()) {
-                    const NdPhase &Q = nd_phases[ph + 1];
-                    x.nn = Q.nch;
-                    for (int c = 0; c < Q.nch; ++c) x.nx[c] = Q.base[c];
-                }
-                for (int c = 0; c < x.nn; ++c) {
-                    x.Dn[c] = Db(c, qq);
-                    x.Rn[c] = Rb(c, qq);
-                    x.Cn[c] = Cb(c, qq);
-                }
-                k_bgj_multi<<<P.ntiles + x.nn, 256, 0, s>>>(nbk, ld, cinv.p, x, nd_mask.p + ph * (size_t)nbk,
-                                                            nd_tiles.p + P.tiles_off, maxd);
-                par = qq;
-            }
-        }
-    } else {
-        BgjStep st{};
-        st.nn = 1;
-        st.nx[0] = 0;
-        st.Dn[0] = Db(0, 0);
-        st.Rn[0] = Rb(0, 0);
-        st.Cn[0] = Cb(0, 0);
-        k_bgj_init<<<1 + 2 * nbk, 256, 0, s>>>(nbk, ld, cinv.p, st, maxd);
-        for (int k = 0; k < nbk; ++k) {
-            const int p = k & 1, q = (k + 1) & 1;
-            k_bgj_step<<<nbk * nbk, 256, 0, s>>>(k, nbk, ld, cinv.p, Db(0, p), Rb(0, p), Cb(0, p), Db(0, q),
-                                                 Rb(0, q), Cb(0, q), maxd);
-        }
-    }
-    {
-        const int ldo = ((C.n + kBj - 1) / kBj) * kBj;
-        const dim3 g(ld / 64, ld / 64);
-        AMG_CHECK(cinv_sc.alloc((size_t)ldo));
-        cinv_f64 = prec32 == 0;   // (f64 transfers: the f64 inverse too)
-        if (cinv_f64) {
-            AMG_CHECK(cinv_o64.alloc((size_t)ldo * ldo));
-            AMG_CHECK(hipMemsetAsync(cinv_o64.p, 0, sizeof(double) * (size_t)ldo * ldo, s));   // (padding columns)
-            k_dense_unperm<double><<<g, 256, 0, s>>>(C.n, ld, ldo, cinv.p, sc, nd ? cinv_iperm.p : nullptr,
-                                                     cinv_o64.p, cinv_sc.p);
-        } else {
-            AMG_CHECK(cinv_o.alloc((size_t)ldo * ldo));
-            AMG_CHECK(hipMemsetAsync(cinv_o.p, 0, sizeof(float) * (size_t)ldo * ldo, s));
-            k_dense_unperm<float><<<g, 256, 0, s>>>(C.n, ld, ldo, cinv.p, sc, nd ? cinv_iperm.p : nullptr, cinv_o.p,
-                                                    cinv_sc.p);
-        }
-        cinv_apply = cinv_o.p;
-        cinv_ld = ldo;
-    }
-    return XFK_OK;
 }
 
 // the V-cycle's per-level vectors
@@ -4665,407 +2389,6 @@ int Amg::galerkin_dist(hipStream_t s, int l, int st, bool &rep)
     return XFK_OK;
 }
 
-namespace {
-
-// which: 0 every row; 1 / 2 the interior / boundary tiles of A.ts (tile levels)
-template <int MODE>
-void launch_smooth_t(hipStream_t s, int l, const AmgLevel &A, const unsigned long long *rho, const double *b,
-                     const double *x, double *out, double *rout, const int *done, double *part_gam, int which)
-{
-    const int *tl = nullptr;
-    int nt = 0;
-    if (which) {
-        tl = A.ts.tiles.p + (which == 2 ? A.ts.n_in : 0);
-        nt = which == 1 ? A.ts.n_in : A.ts.n_bd;
-        if (nt == 0) return;
-    }
-    if (l == 0) {
-        const int g = tl ? nt : (A.n + kCgBlock - 1) / kCgBlock;
-        k_amg_smooth<MODE, kCgBlock><<<g, kCgBlock, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.val, A.dinv.p, rho,
-                                                            b, x, out, rout, done, part_gam, tl,
-                                                            A.has16 ? A.a16.p : nullptr, A.has16 ? A.a16b.p : nullptr);
-        return;
-    }
-    if (A.n >= kTileMinRows) {
-        // coarse levels carry 10-16 entries per row: 4 slots per lane, one pass per tile
-        const int g = tl ? nt : (A.n + 255) / 256;
-        if ((double)A.nnz <= 8.0 * A.n)
-            k_amg_smooth<MODE, 256, 2><<<g, 256, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.val, A.dinv.p, rho, b,
-                                                         x, out, rout, done, nullptr, tl);
-        else
-            k_amg_smooth<MODE, 256, 4><<<g, 256, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.val, A.dinv.p, rho, b,
-                                                         x, out, rout, done, nullptr, tl);
-        return;
-    }
-    const int G = lanes_for(A.n > 0 ? (double)A.nnz / A.n : 1.0);
-    const int g = (int)(((long long)A.n * G + 255) / 256);
-    if (G == 4)
-        k_amg_smooth_g<MODE, 4><<<g, 256, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.val, A.dinv.p, rho, b, x, out,
-                                                 rout, done);
-    else if (G == 8)
-        k_amg_smooth_g<MODE, 8><<<g, 256, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.val, A.dinv.p, rho, b, x, out,
-                                                 rout, done);
-    else
-        k_amg_smooth_g<MODE, 16><<<g, 256, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.val, A.dinv.p, rho, b, x,
-                                                  out, rout, done);
-}
-
-void launch_smooth(hipStream_t s, int mode, int l, const AmgLevel &A, const unsigned long long *rho, const double *b,
-                   const double *x, double *out, double *rout, const int *done, double *part_gam = nullptr,
-                   int which = 0)
-{
-    switch (mode) {
-    case kSweepFromZero: launch_smooth_t<kSweepFromZero>(s, l, A, rho, b, x, out, rout, done, nullptr, which); break;
-    case kSweep: launch_smooth_t<kSweep>(s, l, A, rho, b, x, out, rout, done, part_gam, which); break;
-    case kResid: launch_smooth_t<kResid>(s, l, A, rho, b, x, out, rout, done, nullptr, which); break;
-    default: launch_smooth_t<kResidFromZero>(s, l, A, rho, b, x, out, rout, done, nullptr, which); break;
-    }
-}
-
-// lanes per row of the long R~ rows (up to one wavefront)
-int lanes_wide(double per_row)
-{
-    return per_row <= 6.0 ? 4 : (per_row <= 20.0 ? 8 : (per_row <= 40.0 ? 16 : (per_row <= 80.0 ? 32 : 64)));
-}
-
-template <int GA>
-void launch_fold_pre_a(hipStream_t s, const AmgLevel &A, const unsigned long long *rho, const double *b, double *y,
-                       double *bc, const int *done, const double *yadd)
-{
-    const int GB = lanes_wide(A.nc > 0 ? (double)A.fnnz / A.nc : 1.0);
-    // (the first range padded to whole rounds of the 8 XCDs, so both ranges
-    // take the XCD-contiguous block order)
-    const int ga = (int)(((((long long)A.n * GA + 255) / 256) + 7) & ~7LL);
-    const int gb = (int)(((long long)A.nc * GB + 255) / 256);
-#define XFK_FOLD(GG)                                                                                               \
-    k_fold_pre<GA, GG><<<ga + gb, 256, 0, s>>>(A.n, A.ncol_smooth, A.rowptr, A.col, A.val, A.dinv.p, rho, b, y,   \
-                                               A.nc, A.frrow.p, A.frcol.p, A.frval.p, bc, ga, done, yadd)
-    switch (GB) {
-    case 4: XFK_FOLD(4); break;
-    case 8: XFK_FOLD(8); break;
-    case 16: XFK_FOLD(16); break;
-    case 32: XFK_FOLD(32); break;
-    default: XFK_FOLD(64); break;
-    }
-#undef XFK_FOLD
-}
-
-void launch_fold_pre(hipStream_t s, const AmgLevel &A, const unsigned long long *rho, const double *b, double *y,
-                     double *bc, const int *done, const double *yadd = nullptr)
-{
-    if (A.n <= 0) return;
-    const int GA = lanes_for((double)A.nnz / A.n);
-    if (GA == 4) launch_fold_pre_a<4>(s, A, rho, b, y, bc, done, yadd);
-    else if (GA == 8) launch_fold_pre_a<8>(s, A, rho, b, y, bc, done, yadd);
-    else launch_fold_pre_a<16>(s, A, rho, b, y, bc, done, yadd);
-}
-
-// tile size of the level's smoother launches (0: sub-wave kernels, no split)
-int smooth_tile(int l, const AmgLevel &A) { return l == 0 ? kCgBlock : (A.n >= kTileMinRows ? 256 : 0); }
-
-}  // namespace
-
-// algorithmic bytes of one smoother launch (mode as launch_smooth): the
-// matrix stream, the gathered operand once, b / D^-1, the written vectors
-static double smooth_bytes(const AmgLevel &A, int mode)
-{
-    const double n = A.n, base = ((A.has16 ? 2.0 : 4.0) + 8.0) * (double)A.nnz + 4.0 * (n + 1);
-    const bool implicit = mode == kSweepFromZero || mode == kResidFromZero;
-    const double rd = (implicit ? 2.0 : 3.0) * 8.0 * n;
-    const double wr = (mode == kResidFromZero && !A.fold ? 2.0 : 1.0) * 8.0 * n;
-    return base + rd + wr;
-}
-
-static const char *smooth_name(int mode)
-{
-    switch (mode) {
-    case kResidFromZero: return "sweep from 0 + residual";
-    case kSweepFromZero: return "sweep from 0";
-    case kResid: return "residual";
-    default: return "sweep";
-    }
-}
-
-static void smooth_ph(hipStream_t s, int mode, int l, const AmgLevel &A, const unsigned long long *rho,
-                      const double *b, const double *x, double *out, double *rout, const int *done,
-                      double *part_gam = nullptr)
-{
-    if (g_prof)
-        XFK_PHASE("L" + std::to_string(l) + " " + smooth_name(mode) + (part_gam ? " (+ r.u partials)" : ""),
-                  smooth_bytes(A, mode), launch_smooth(s, mode, l, A, rho, b, x, out, rout, done, part_gam));
-    else
-        launch_smooth(s, mode, l, A, rho, b, x, out, rout, done, part_gam);
-}
-
-// Symmetric V-cycle; returns the buffer holding the level's result.  Level 0
-// writes its result to `out0`.
-// (coarse folded / dense levels: yout = the result buffer instead of xa,
-// yadd = a vector the result is added onto -- the W-cycle's second correction)
-static double *vcycle_level(Amg &M, hipStream_t s, int l, const double *b, double *out0, const int *done,
-                            double *part_gam = nullptr, double *yout = nullptr, const double *yadd = nullptr)
-{
-    AmgLevel &A = *M.L[l];
-    const unsigned long long *rho = M.rho.p + 2 * l;
-    const int nu = M.sweeps;
-    auto other = [&](double *c) { return c == A.xa.p ? A.xb.p : A.xa.p; };
-    const std::string lv = g_prof ? "L" + std::to_string(l) + " " : std::string();
-    if (l == M.nlev - 1) {
-        double *dst = (l == 0) ? out0 : (yout ? yout : A.xa.p);
-        if (M.dense_coarse) {
-            if (M.cinv_f64)
-                XFK_PHASE(lv + "dense inverse x b", 8.0 * A.n * M.cinv_ld + 8.0 * (2 * M.cinv_ld + A.n),
-                          (k_dense_mv<double><<<A.n, 256, 0, s>>>(A.n, M.cinv_ld, M.cinv_o64.p, M.cinv_sc.p, b, dst,
-                                                                  done)));
-            else
-                XFK_PHASE(lv + "dense inverse x b", 4.0 * A.n * M.cinv_ld + 8.0 * (2 * M.cinv_ld + A.n),
-                          (k_dense_mv<float><<<A.n, 256, 0, s>>>(A.n, M.cinv_ld, M.cinv_apply, M.cinv_sc.p, b, dst,
-                                                                 done)));
-            return dst;
-        }
-        // smoother-only coarsest level: 2 nu sweeps from zero
-        double *cur = A.xa.p;
-        smooth_ph(s, kSweepFromZero, l, A, rho, b, nullptr, cur, nullptr, done);
-        for (int k = 2; k < 2 * nu; ++k) {
-            double *nx = (k == 2 * nu - 1 && l == 0) ? out0 : other(cur);
-            smooth_ph(s, kSweep, l, A, rho, b, cur, nx, nullptr, done);
-            cur = nx;
-        }
-        if (l == 0 && cur != out0)
-            (void)hipMemcpyAsync(out0, cur, sizeof(double) * A.n, hipMemcpyDeviceToDevice, s);
-        return cur;
-    }
-    if (A.fold && l > 0) {
-        // two launches: y and the coarse right-hand side, then x = y + P~ x_c
-        AmgLevel &C = *M.L[l + 1];
-        double *y = yout ? yout : A.xa.p;
-        const double n = A.n, nc = A.nc, f = (double)A.fnnz;
-        XFK_PHASE(lv + "folded pre: y, R~ r", 12.0 * A.nnz + 4.0 * (n + 1) + 24.0 * n + 12.0 * f + 4.0 * (nc + 1) +
-                                                   8.0 * nc + (yadd ? 8.0 * n : 0.0),
-                  launch_fold_pre(s, A, rho, b, y, C.b.p, done, yadd));
-        const double *xc;
-        if (M.w_at(l)) {
-            // W-cycle at this level: a second coarse correction from the
-            // coarse residual after the first, b_c' = b_c - A_c x_c (Galerkin:
-            // R (b - A (x_pre + P x_c)) = b_c - A_c x_c), x_c += V(b_c'); the
-            // second visit adds its result onto the first (its folded
-            // pre-step starts from x_c), so the post-step prolongs the sum.
-            // Symmetric like the V-cycle; three launches more than it.
-            const double *x1 = vcycle_level(M, s, l + 1, C.b.p, nullptr, done, nullptr, C.xb.p);
-            smooth_ph(s, kResid, l + 1, C, M.rho.p + 2 * (l + 1), C.b.p, x1, nullptr, C.r.p, done);
-            xc = vcycle_level(M, s, l + 1, C.r.p, nullptr, done, nullptr, C.xa.p, x1);
-        } else {
-            xc = vcycle_level(M, s, l + 1, C.b.p, nullptr, done);
-        }
-        XFK_PHASE(lv + "folded post: x = y + P~ xc", 12.0 * f + 4.0 * (n + 1) + 8.0 * nc + 16.0 * n,
-                  launch_mv(s, A.n, A.ftrow.p, A.ftcol.p, A.ftval.p, xc, y, true, lanes_for(f / n), done));
-        return y;
-    }
-    // pre-smoothing (nu sweeps from zero) and residual
-    double *cur = A.xa.p;
-    if (nu == 1) {
-        // (a folded level 0 recomputes x_pre = w D^-1 b in its post-step)
-        smooth_ph(s, kResidFromZero, l, A, rho, b, nullptr, (A.fold && l == 0) ? nullptr : cur, A.r.p, done);
-    } else {
-        smooth_ph(s, kSweepFromZero, l, A, rho, b, nullptr, cur, nullptr, done);
-        for (int k = 2; k < nu; ++k) {
-            double *nx = other(cur);
-            smooth_ph(s, kSweep, l, A, rho, b, cur, nx, nullptr, done);
-            cur = nx;
-        }
-        smooth_ph(s, kResid, l, A, rho, b, cur, nullptr, A.r.p, done);
-    }
-    AmgLevel &C = *M.L[l + 1];
-    const long long rnnz = A.pnnz;
-    XFK_PHASE(lv + "restriction R r", A.nz_bytes() * rnnz + 4.0 * (A.nc + 1) + 8.0 * A.n + 8.0 * A.nc,
-              (A.has32 ? launch_mv32(s, A.nc, A.rrow.p, A.rcol.p, A.r32.p, A.r.p, C.b.p, false,
-                                     lanes_for((double)rnnz / A.nc), done, A.r16.p, A.r16b.p)
-                       : launch_mv(s, A.nc, A.rrow.p, A.rcol.p, A.rval.p, A.r.p, C.b.p, false,
-                                   lanes_for((double)rnnz / A.nc), done, A.has16 ? A.r16.p : nullptr,
-                                   A.has16 ? A.r16b.p : nullptr)));
-    const double *xc = vcycle_level(M, s, l + 1, C.b.p, nullptr, done);
-    if (A.fold && l == 0 && nu == 1) {
-        const double n = A.n, f = (double)A.fnnz;
-        XFK_PHASE(lv + "folded post: u = x + w D^-1 r + P~ xc" + (part_gam ? " (+ r.u partials)" : ""),
-                  A.nz_bytes() * f + 4.0 * (n + 1) + 8.0 * A.nc + 32.0 * n,
-                  (A.has32 ? k_fold_post0<kCgBlock, 2><<<(A.n + kCgBlock - 1) / kCgBlock, kCgBlock, 0, s>>>(
-                                 A.n, A.ftrow.p, A.ftcol.p, A.f32v.p, xc, A.dinv.p, rho, A.r.p, b, out0, done,
-                                 part_gam, A.f16.p, A.f16b.p)
-                           : k_fold_post0<kCgBlock, 2><<<(A.n + kCgBlock - 1) / kCgBlock, kCgBlock, 0, s>>>(
-                                 A.n, A.ftrow.p, A.ftcol.p, A.ftval.p, xc, A.dinv.p, rho, A.r.p, b, out0, done,
-                                 part_gam, A.has16 ? A.f16.p : nullptr, A.has16 ? A.f16b.p : nullptr)));
-        if (part_gam) M.gamma_done = true;
-        return out0;
-    }
-    XFK_PHASE(lv + "prolongation x += P xc", 12.0 * rnnz + 4.0 * (A.n + 1) + 8.0 * A.nc + 16.0 * A.n,
-              launch_mv(s, A.n, A.prow.p, A.pcol.p, A.pval.p, xc, cur, true, lanes_for((double)rnnz / A.n), done));
-    for (int k = 0; k < nu; ++k) {
-        const bool last0 = k == nu - 1 && l == 0;
-        double *nx = last0 ? out0 : other(cur);
-        smooth_ph(s, kSweep, l, A, rho, b, cur, nx, nullptr, done, last0 ? part_gam : nullptr);
-        if (last0 && part_gam) M.gamma_done = true;
-        cur = nx;
-    }
-    return cur;
-}
-
-// sharded level l: every sweep reads the peers' halo values of the iterate;
-// the restriction / prolongation stay rank-local (P rows reference the own
-// aggregates only).  Returns the buffer holding the result (`out` if given).
-double *Amg::vc_dist(hipStream_t s, int l, const double *b, double *out, const int *done, int &rc)
-{
-    AmgLevel &A = *L[l];
-    const unsigned long long *rh = rho.p + 2 * l;
-    double *cur = A.xa.p, *oth = A.xb.p;
-    rc = XFK_OK;
-    // tile levels: the halo exchange of the iterate overlaps the interior tiles
-    const int B = smooth_tile(l, A);
-    const bool ov = B > 0 && overlap;
-    if (ov && !A.ts.ready()) {
-        if ((rc = side.init()) != XFK_OK) return nullptr;
-        if ((rc = build_tile_split(s, A.n, B, A.rowptr, A.col, A.ts)) != XFK_OK) return nullptr;
-    }
-    // halo of x, then mode over the level's rows (interior tiles during the exchange)
-    auto smooth_after_exchange = [&](int mode, double *x, double *o, double *ro, double *pg) -> int {
-        if (!ov) {
-            const int r = comm->exchange(A.plan, x, s);
-            if (r != XFK_OK) return r;
-            launch_smooth(s, mode, l, A, rh, b, x, o, ro, done, pg);
-            return XFK_OK;
-        }
-        return exchange_overlapped(
-            s, side, [&](hipStream_t cs) { return comm->exchange(A.plan, x, cs); },
-            [&] { launch_smooth(s, mode, l, A, rh, b, x, o, ro, done, pg, 1); },
-            [&] { launch_smooth(s, mode, l, A, rh, b, x, o, ro, done, pg, 2); });
-    };
-    if (A.n > 0) k_jacobi_first<<<nb(A.n), kB, 0, s>>>(A.n, rh, A.dinv.p, b, cur, done);
-    for (int k = 1; k < sweeps; ++k) {
-        if ((rc = smooth_after_exchange(kSweep, cur, oth, nullptr, nullptr)) != XFK_OK) return nullptr;
-        std::swap(cur, oth);
-    }
-    if ((rc = smooth_after_exchange(kResid, cur, nullptr, A.r.p, nullptr)) != XFK_OK) return nullptr;
-    AmgLevel &C = *L[l + 1];
-    const int GR = lanes_for(A.nc > 0 ? (double)A.pnnz / A.nc : 1.0);
-    const double *xc;
-    // level 0 with f32 transfers: R and P in f32 with 16-bit tile columns
-    auto restrict_to = [&](double *dst) {
-        if (A.has32)
-            launch_mv32(s, A.nc, A.rrow.p, A.rcol.p, A.r32.p, A.r.p, dst, false, GR, done, A.r16.p, A.r16b.p);
-        else
-            launch_mv(s, A.nc, A.rrow.p, A.rcol.p, A.rval.p, A.r.p, dst, false, GR, done);
-    };
-    const bool fold = A.fold && sweeps == 1;
-    const double *xfull = nullptr;   // folded: x_c with the columns P~ reads (coarse halo / global)
-    if (C.dist) {
-        restrict_to(C.b.p);
-        xc = vc_dist(s, l + 1, C.b.p, nullptr, done, rc);
-        if (rc != XFK_OK) return nullptr;
-        if (fold) {   // the coarse halo P~ reads (the next level's plan covers P~'s columns)
-            double *xh = const_cast<double *>(xc);
-            if ((rc = comm->exchange(C.plan, xh, s)) != XFK_OK) return nullptr;
-            xfull = xh;
-        }
-    } else {
-        // the replicated levels: gather the global right-hand side, solve the
-        // same coarse problem on every rank, read the own aggregates back
-        restrict_to(cb_loc.p);
-        const int te = tail_begin(s, 0);
-        if ((rc = comm->allgather(cb_loc.p, cb_all.p, (size_t)ncmax, s)) != XFK_OK) return nullptr;
-        k_unpad<<<nb(C.n), kB, 0, s>>>(C.n, nranks, c0_dev.p, cb_all.p, ncmax, C.b.p, done);
-        xfull = vcycle_level(*this, s, l + 1, C.b.p, nullptr, done);
-        xc = xfull + c0[rank];
-        tail_end(s, te);
-    }
-    if (fold) {
-        // u = w D^-1 b + w D^-1 r' + P~ x_c over the own rows: the prolongation
-        // and the post-sweep (whose halo exchange it replaces) in one pass
-        double *o = out ? out : oth;
-        if (A.n > 0) {
-            double *pg = (l == 0 && out) ? part_gam_ : nullptr;
-            if (l == 0) {
-                const int g = (A.n + kCgBlock - 1) / kCgBlock;
-                if (A.has32)
-                    k_fold_post0<kCgBlock, 2><<<g, kCgBlock, 0, s>>>(A.n, A.ftrow.p, A.ftcol.p, A.f32v.p, xfull,
-                                                                     A.dinv.p, rh, A.r.p, b, o, done, pg,
-                                                                     A.has16 ? A.f16.p : nullptr,
-                                                                     A.has16 ? A.f16b.p : nullptr);
-                else
-                    k_fold_post0<kCgBlock, 2><<<g, kCgBlock, 0, s>>>(A.n, A.ftrow.p, A.ftcol.p, A.ftval.p, xfull,
-                                                                     A.dinv.p, rh, A.r.p, b, o, done, pg,
-                                                                     A.has16 ? A.f16.p : nullptr,
-                                                                     A.has16 ? A.f16b.p : nullptr);
-            } else {
-                const int g = (A.n + 255) / 256;
-                const unsigned short *no16 = nullptr;
-                const int *nob = nullptr;
-                if ((double)A.fnnz <= 8.0 * A.n)
-                    k_fold_post0<256, 2><<<g, 256, 0, s>>>(A.n, A.ftrow.p, A.ftcol.p, A.ftval.p, xfull, A.dinv.p, rh,
-                                                           A.r.p, b, o, done, pg, no16, nob);
-                else
-                    k_fold_post0<256, 4><<<g, 256, 0, s>>>(A.n, A.ftrow.p, A.ftcol.p, A.ftval.p, xfull, A.dinv.p, rh,
-                                                           A.r.p, b, o, done, pg, no16, nob);
-            }
-        }
-        if (l == 0 && out && part_gam_) gamma_done = true;
-        return o;
-    }
-    if (A.n > 0) {
-        const int GP = lanes_for((double)A.pnnz / A.n);
-        if (A.has32)
-            launch_mv32(s, A.n, A.prow.p, A.pcol.p, A.p32.p, xc, cur, true, GP, done, A.p16.p, A.p16b.p);
-        else
-            launch_mv(s, A.n, A.prow.p, A.pcol.p, A.pval.p, xc, cur, true, GP, done);
-    }
-    for (int k = 0; k < sweeps; ++k) {
-        const bool last0 = k == sweeps - 1 && out && l == 0;
-        double *nx = (k == sweeps - 1 && out) ? out : oth;
-        if ((rc = smooth_after_exchange(kSweep, cur, nx, nullptr, last0 ? part_gam_ : nullptr)) != XFK_OK)
-            return nullptr;
-        if (last0 && part_gam_) gamma_done = true;
-        oth = cur;
-        cur = nx;
-    }
-    return cur;
-}
-
-int Amg::tail_begin(hipStream_t s, int kind)
-{
-    if (!time_tail) return -1;
-    const int at = tail_used;
-    while ((int)tail_ev.size() < at + 2) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return -1;
-        tail_ev.push_back(e);
-    }
-    if (hipEventRecord(tail_ev[at], s) != hipSuccess) return -1;
-    tail_kind.resize(at / 2 + 1);
-    tail_kind[at / 2] = (char)kind;
-    tail_used = at + 2;
-    return at;
-}
-
-void Amg::tail_end(hipStream_t s, int at)
-{
-    if (at >= 0) (void)hipEventRecord(tail_ev[at + 1], s);
-}
-
-int Amg::tail_read(double &ms_cycle, int &cycles, double &ms_setup)
-{
-    ms_cycle = ms_setup = 0;
-    cycles = 0;
-    for (int k = 0; k + 1 < tail_used; k += 2) {
-        float m = 0;
-        AMG_CHECK(hipEventElapsedTime(&m, tail_ev[k], tail_ev[k + 1]));
-        if (tail_kind[k / 2] == 0) {
-            ms_cycle += m;
-            ++cycles;
-        } else {
-            ms_setup += m;
-        }
-    }
-    tail_used = 0;
-    return XFK_OK;
-}
-
 // XFK_AMG_REFOLD=0: a Newton refresh runs level 0 unfolded (the former way)
 static bool refold_on()
 {
@@ -5100,22 +2423,6 @@ int Amg::refresh(hipStream_t s, bool fold)
                                                                 A.pcol.p, A.pval.p, A.ftrow.p, A.ftcol.p, A.ftval.p,
                                                                 A.has32 ? A.f32v.p : nullptr, refold_stage());
     }
-    AMG_CHECK(hipGetLastError());
-    return XFK_OK;
-}
-
-int Amg::vcycle(hipStream_t s, const double *r, double *u, const int *done, double *part_gam)
-{
-    gamma_done = false;
-    if (!dist) {
-        vcycle_level(*this, s, 0, r, u, done, part_gam);
-        return XFK_OK;
-    }
-    int rc = XFK_OK;
-    part_gam_ = part_gam;
-    vc_dist(s, 0, r, u, done, rc);
-    part_gam_ = nullptr;
-    if (rc != XFK_OK) return rc;
     AMG_CHECK(hipGetLastError());
     return XFK_OK;
 }

@@ -324,6 +324,10 @@ hipError_t stream_acquire(hipStream_t *s);
 // one kernel of each translation unit queried, so its code object is loaded
 // (xfk_device_init)
 hipError_t warm_module_amg();
+// (the AMG's other translation units: library-internal, no dynamic symbol)
+__attribute__((visibility("hidden"))) hipError_t warm_module_amg_cycle();
+__attribute__((visibility("hidden"))) hipError_t warm_module_amg_dense();
+__attribute__((visibility("hidden"))) hipError_t warm_module_amg_spgemm();
 hipError_t warm_module_comm();
 hipError_t warm_module_device();
 hipError_t warm_module_electro();

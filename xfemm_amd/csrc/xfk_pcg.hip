@@ -1,6 +1,6 @@
 // Preconditioned conjugate gradient of the fsolver hot path: two launches per
 // iteration with the Jacobi preconditioner, update + V-cycle + SpMV with the
-// default smoothed-aggregation AMG (xfk_amg.hip).
+// default smoothed-aggregation AMG (xfk_amg*.hip).
 //
 // Reference: CBigLinProb::PCGSolve (cfemm/libfemm/spars.cpp:238-316) -- same
 // PCG, same stopping test sqrt(z.r / z0.b) <= Precision, same initial guess

@@ -1,5 +1,5 @@
 // Device helpers shared by the PCG (xfk_pcg.hip) and the AMG V-cycle
-// (xfk_amg.hip): wavefront/workgroup sums and the CSR-stream tile SpMV.
+// (xfk_amg_cycle.hip): wavefront/workgroup sums and the CSR-stream tile SpMV.
 #pragma once
 
 #include <hip/hip_runtime.h>
