@@ -650,8 +650,8 @@ int xfk_hf_conductor_flow(xfk_problem *prob, int conductor, double *q);
 /* ---------------------------------------------------------------------------
  * Post-processing of a solved electrostatic or heat-flow problem on the
  * device: what the reference's epproc and hpproc compute (getElementD,
- * getNodalD, blockIntegral types 0-6 with makeMask, getPointValues), in the reference's
- * operation order.  Lengths are the problem's own length units, as the
+ * getNodalD, blockIntegral types 0-6 with makeMask, getPointValues,
+ * lineIntegral), in the reference's operation order.  Lengths are the problem's own length units, as the
  * reference's post-processors read them.
  *
  * Every function returns XFK_ERR_ARG with a message naming the cause on a
@@ -717,6 +717,37 @@ int xfk_pot_get_mask(xfk_problem *prob, double *W, double *msk);
  * corner values instead of taking the element's D (F). */
 int xfk_pot_point_values(xfk_problem *prob, int n, const double *x, const double *y, int smooth, int *elem,
                          double *out);
+/* Contour (line) integrals, the reference's lineIntegral, for a batch of
+ * contours: contour c is the polyline through the vertices ptr[c] .. ptr[c+1]
+ * of (x, y), in the problem's length units; ptr has n_contours + 1 entries.
+ * Every segment is sampled at npts midpoints (npts <= 0: the reference's 400),
+ * each shifted by 1e-6 length units to the segment's left (n = i t) except for
+ * the heat-flow average temperature; the samples are made on the device.  A
+ * sample takes the lowest-numbered element that contains it, as
+ * xfk_pot_point_values does; a sample no element contains adds nothing and is
+ * counted in missed[c] (may be NULL).  smooth != 0 blends the smoothed corner
+ * values, the reference's default.  out holds 2 doubles per contour, type in
+ * the reference's numbering --
+ *   electrostatics                         heat flow
+ *   0  V(first) - V(last), 0               0  T(first) - T(last), 0
+ *   1  flux of D (C), its average (C/m^2)  1  flux of F (W), its average (W/m^2)
+ *   2  length (m), swept area (m^2)        2  length (m), swept area (m^2)
+ *   3  stress tensor force (N): x, y;      3  average T (K), the weight sum (m^2)
+ *      0, z on an axisymmetric problem
+ *   4  stress tensor torque about the
+ *      origin (N m), 0; 0 on an
+ *      axisymmetric problem
+ * Type 0 is NaN when an end lies outside the mesh (missed: the ends outside);
+ * an average over a contour wholly outside is 0/0 = NaN.  The sums run in a
+ * fixed order per contour: two runs give the same bits, and a contour gives
+ * the same bits alone or inside any batch.  XFK_ERR_ARG also for a type the
+ * physics does not have, a contour with fewer than 2 points, a zero-length
+ * segment, a NaN or infinite vertex and a negative count.
+ * xfk_pot_line_integral: one contour of n points. */
+int xfk_pot_line_integrals(xfk_problem *prob, int n_contours, const int *ptr, const double *x, const double *y,
+                           int type, int smooth, int npts, double *out, int *missed);
+int xfk_pot_line_integral(xfk_problem *prob, int n, const double *x, const double *y, int type, int smooth, int npts,
+                          double *out2, int *missed);
 
 /* Diagnostics of the post-processor, for tests and the lab probe; not part of
  * the interface a caller should build on.
@@ -751,6 +782,18 @@ int xfk_pot_time(xfk_problem *prob, int n, const double *x, const double *y, int
 int xfk_pot_mask_info(xfk_problem *prob, double *out9);
 int xfk_pot_mask_problem(xfk_problem *prob, xfk_problem **aux);
 int xfk_pot_stress_time(xfk_problem *prob, int repeats, double *ms);
+/* ... and of the contour integrals.
+ * xfk_pot_contour_samples: the samples of one contour of n points for a
+ * sampled type (1, 3, 4; heat flow 1, 3) as the kernel makes them: xy, 2
+ * doubles per sample, and elem, the element each took (-1: none),
+ * (n - 1) npts of each (npts <= 0: 400).
+ * xfk_pot_contour_time: HIP-event ms of the sample launch and its
+ * per-contour sum for a batch of a sampled type, the median of `repeats` runs
+ * after a warm-up. */
+int xfk_pot_contour_samples(xfk_problem *prob, int n, const double *x, const double *y, int type, int npts,
+                            double *xy, int *elem);
+int xfk_pot_contour_time(xfk_problem *prob, int n_contours, const int *ptr, const double *x, const double *y,
+                         int type, int smooth, int npts, int repeats, double *ms);
 
 /* Diagnostics of the AMG hierarchy (single device), for tests; not part of the
  * interface a caller should build on.  A probe holds one hierarchy built from

@@ -15,6 +15,8 @@
 //   point values      InTriangleTest (PostProcessor.cpp:359-398), getPointD
 //                     (1153-1188), getPointValues (epproc.cpp:434-469,
 //                     hpproc.cpp:332-366) over a uniform cell grid
+//   contour integrals lineIntegral (epproc.cpp:489-724, hpproc.cpp:648-800)
+//                     over batches of contours, a thread per sample
 //
 // The post-processors work in the problem's own length units with
 // LengthConv[] to metres; the solvers in mm (esolver) or m (hsolver).  The
@@ -725,46 +727,41 @@ __device__ __forceinline__ bool pp_in_triangle(const double *__restrict__ xs, co
     return in;
 }
 
-// getPointValues of n points: the lowest-numbered element containing each
-// (-1: none, its values NaN), then 8 values per point --
-//   electrostatics: V, Dx, Dy, Ex, Ey, ex, ey, nrg
-//   heat flow:      T, Fx, Fy, Kx, Ky, Gx, Gy, 0
-template <bool HEAT>
-__global__ void __launch_bounds__(kBlock) k_pp_points(int n, PpArgs A, PpGrid G, const int *__restrict__ ptr,
-                                                      const int *__restrict__ cell_el, int nbig,
-                                                      const int *__restrict__ big, const double *__restrict__ px,
-                                                      const double *__restrict__ py, int smooth,
-                                                      const double *__restrict__ D, const double *__restrict__ dc,
-                                                      int *__restrict__ elem, double *__restrict__ out,
-                                                      int *__restrict__ ntests)
+// The cell grid and the oversize list as the search reads them
+struct PpLists {
+    const int *ptr, *cell_el, *big;
+    int nbig;
+};
+
+// The lowest-numbered element containing (x, y), or -1 when none does (or a
+// coordinate is NaN); ntests: the elements the point was tested against
+__device__ __forceinline__ int pp_find(const PpArgs &A, const PpGrid &G, const PpLists &L, double x, double y,
+                                       int &ntests)
 {
-    const int t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n) return;
-    const double x = px[t], y = py[t];
     int k = 0x7fffffff;
+    ntests = 0;
     if (x == x && y == y) {
         const int c = pp_cell1(y, G.y0, G.ihy, G.ny) * G.nx + pp_cell1(x, G.x0, G.ihx, G.nx);
-        // (diagnostics: the elements this point is tested against)
-        if (ntests) ntests[t] = ptr[c + 1] - ptr[c] + nbig;
-        for (int m = ptr[c]; m < ptr[c + 1]; ++m) {
-            const int e = cell_el[m];
+        ntests = L.ptr[c + 1] - L.ptr[c] + L.nbig;
+        for (int m = L.ptr[c]; m < L.ptr[c + 1]; ++m) {
+            const int e = L.cell_el[m];
             if (e < k && pp_in_triangle(A.x, A.y, A.p, e, x, y)) k = e;
         }
-        for (int m = 0; m < nbig; ++m) {
-            const int e = big[m];
+        for (int m = 0; m < L.nbig; ++m) {
+            const int e = L.big[m];
             if (e < k && pp_in_triangle(A.x, A.y, A.p, e, x, y)) k = e;
         }
     }
-    double *o = out + 8 * (size_t)t;
-    if (ntests && !(x == x && y == y)) ntests[t] = 0;
-    if (k == 0x7fffffff) {
-        elem[t] = -1;
-        const double nan = __longlong_as_double(0x7ff8000000000000LL);
-#pragma unroll
-        for (int v = 0; v < 8; ++v) o[v] = nan;
-        return;
-    }
-    elem[t] = k;
+    return k == 0x7fffffff ? -1 : k;
+}
+
+// getPointValues(x, y, k) (epproc.cpp:434-469, hpproc.cpp:332-366) with
+// getPointD (PostProcessor.cpp:1153-1188): the 8 values of k_pp_points
+template <bool HEAT>
+__device__ __forceinline__ void pp_values_at(const PpArgs &A, int k, double x, double y, int smooth,
+                                             const double *__restrict__ D, const double *__restrict__ dc,
+                                             double (&o)[8])
+{
     PpElem E;
     pp_load(A, k, E);
     double a[3], b[3], c[3];
@@ -817,6 +814,164 @@ __global__ void __launch_bounds__(kBlock) k_pp_points(int n, PpArgs A, PpGrid G,
         o[6] = ey;
         o[7] = (Dr * Er - Di * (-Ei)) / 2.;
     }
+}
+
+// getPointValues of n points: the lowest-numbered element containing each
+// (-1: none, its values NaN), then 8 values per point --
+//   electrostatics: V, Dx, Dy, Ex, Ey, ex, ey, nrg
+//   heat flow:      T, Fx, Fy, Kx, Ky, Gx, Gy, 0
+template <bool HEAT>
+__global__ void __launch_bounds__(kBlock) k_pp_points(int n, PpArgs A, PpGrid G, PpLists L,
+                                                      const double *__restrict__ px,
+                                                      const double *__restrict__ py, int smooth,
+                                                      const double *__restrict__ D, const double *__restrict__ dc,
+                                                      int *__restrict__ elem, double *__restrict__ out,
+                                                      int *__restrict__ ntests)
+{
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const double x = px[t], y = py[t];
+    int nt;
+    const int k = pp_find(A, G, L, x, y, nt);
+    // (diagnostics: the elements this point is tested against)
+    if (ntests) ntests[t] = nt;
+    double *o = out + 8 * (size_t)t;
+    elem[t] = k;
+    double v[8];
+    if (k < 0) {
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v[c] = nan;
+    } else {
+        pp_values_at<HEAT>(A, k, x, y, smooth, D, dc, v);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[c] = v[c];
+}
+
+// lineIntegral types 1, 3 and 4 (epproc.cpp:508-572, 597-723) and 1 and 3
+// of heat flow (hpproc.cpp:668-725, 746-797): one thread per sample of a batch
+// of contours, the samples made here from the contours' vertices.  Contour c
+// holds the vertices cptr[c] .. cptr[c + 1) of (cx, cy) and owns the workgroups
+// bptr[c] .. bptr[c + 1), so a workgroup never straddles two contours and a
+// contour's partials do not depend on its place in the batch.  Per workgroup
+// three sums into part: the integral's two, and the samples no element holds
+// (which add nothing to the other two, the reference's flag == false).  The
+// element of a sample is the lowest-numbered containing one, as k_pp_points
+// takes it; the reference walks from the previous sample's element.
+// dbg_xy, dbg_el (may be null; one contour only): every sample's point and
+// element.
+template <bool HEAT>
+__global__ void __launch_bounds__(kPotQBlock) k_pp_contour(int nc, PpArgs A, PpGrid G, PpLists L,
+                                                           const int *__restrict__ cptr,
+                                                           const int *__restrict__ bptr,
+                                                           const double *__restrict__ cx,
+                                                           const double *__restrict__ cy, int npts, int type,
+                                                           int smooth, const double *__restrict__ D,
+                                                           const double *__restrict__ dc,
+                                                           double *__restrict__ part, double *__restrict__ dbg_xy,
+                                                           int *__restrict__ dbg_el)
+{
+    // the contour of this workgroup: bptr[c] <= blockIdx.x < bptr[c + 1]
+    int c = 0, hi = nc;
+    while (hi - c > 1) {
+        const int mid = (c + hi) >> 1;
+        if (bptr[mid] <= (int)blockIdx.x) c = mid;
+        else hi = mid;
+    }
+    const int v0 = cptr[c], nseg = cptr[c + 1] - v0 - 1;
+    const int j = ((int)blockIdx.x - bptr[c]) * kPotQBlock + threadIdx.x;
+    double v[3] = {0., 0., 0.};
+    if (j < nseg * npts) {
+        const int k = j / npts, i = j - k * npts;
+        const double x0 = cx[v0 + k], y0 = cy[v0 + k], x1 = cx[v0 + k + 1], y1 = cy[v0 + k + 1];
+        const double dx = x1 - x0, dy = y1 - y0;
+        const double len = pp_cabs(dx, dy);
+        const double dz = len / ((double)npts);
+        const double u = (((double)i) + 0.5) / ((double)npts);
+        double ptx = x0 + u * dx, pty = y0 + u * dy;
+        const double tr = dx / len, ti = dy / len;
+        // n = I * t, the complex product as the reference forms it
+        const double nr = 0. * tr - 1. * ti, ni = 0. * ti + 1. * tr;
+        if (!(HEAT && type == 3)) {
+            ptx += nr * 1.e-06;
+            pty += ni * 1.e-06;
+        }
+        int nt;
+        const int el = pp_find(A, G, L, ptx, pty, nt);
+        if (dbg_xy) {
+            dbg_xy[2 * (size_t)j] = ptx;
+            dbg_xy[2 * (size_t)j + 1] = pty;
+        }
+        if (dbg_el) dbg_el[j] = el;
+        if (el < 0) {
+            v[2] = 1.;
+        } else {
+            double o[8];
+            pp_values_at<HEAT>(A, el, ptx, pty, smooth, D, dc, o);
+            // 1 / n (femmcomplex.cpp:362-380)
+            double q, yr, yi;
+            if (fabs(nr) > fabs(ni)) {
+                q = ni / nr;
+                yr = 1. / (nr * (1. + q * q));
+                yi = (-q) * yr;
+            } else {
+                q = nr / ni;
+                yi = (-1.) / (ni * (1. + q * q));
+                yr = (-q) * yi;
+            }
+            if (type == 1 || (HEAT && type == 3)) {
+                double d;
+                if (A.axi) d = 2. * kPI * ptx * (A.lc * A.lc);
+                else d = A.depth * A.lc;
+                if (type == 1) {
+                    const double Dn = o[1] * yr - o[2] * yi;
+                    v[0] = (Dn * dz * d);
+                } else {
+                    v[0] = (o[0] * dz * d);
+                }
+                v[1] = dz * d;
+            } else if (!HEAT) {
+                const double Dr = o[1], Di = o[2], Er = o[3], Ei = o[4];
+                const double Hn = Er * yr - Ei * yi;
+                const double Bn = Dr * yr - Di * yi;
+                const double BH = Dr * Er - Di * (-Ei);
+                double dF1 = Er * Bn + Dr * Hn - nr * BH;
+                const double dF2 = Ei * Bn + Di * Hn - ni * BH;
+                if (type == 3) {
+                    double dza = dz * A.lc;
+                    if (A.axi) {
+                        dza *= 2. * kPI * ptx * A.lc;
+                        dF1 = 0;
+                    } else {
+                        dza *= A.depth;
+                    }
+                    v[0] = (dF1 * dza / 2.);
+                    v[1] = (dF2 * dza / 2.);
+                } else if (!A.axi) {   // (type 4; on an axisymmetric problem 0, as block integral 6)
+                    const double dT = ptx * dF2 - dF1 * pty;
+                    const double dza = dz * (A.lc * A.lc);
+                    v[0] = (dT * dza * A.depth / 2.);
+                }
+            }
+        }
+    }
+    block_sums<3>(v, part);
+}
+
+// one workgroup per contour: its workgroups' partials strided per thread in a
+// fixed order, then the workgroup's sums, into out[3 c .. 3 c + 3)
+__global__ void __launch_bounds__(kPotQBlock) k_pp_contour_sum(const int *__restrict__ bptr,
+                                                               const double *__restrict__ part,
+                                                               double *__restrict__ out)
+{
+    const int b0 = bptr[blockIdx.x], g = bptr[blockIdx.x + 1] - b0;
+    double s[3] = {0., 0., 0.};
+    for (int i = threadIdx.x; i < g; i += kPotQBlock) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] += part[3 * (size_t)(b0 + i) + c];
+    }
+    block_sums<3>(s, out);
 }
 
 // --- host side ---------------------------------------------------------------
@@ -1136,19 +1291,25 @@ static int pp_entry(xfk_problem *P, bool need_solution, F &&body)
     }
 }
 
+static PpLists pp_lists(const xfk_problem *P)
+{
+    return PpLists{P->pp_cell_ptr.p, P->pp_cell_el.p, P->pp_big.p, P->pp_nbig};
+}
+
 static int pp_launch_points(xfk_problem *P, int n, const double *px, const double *py, int smooth, double *o,
                             int *ntests)
 {
     const PpArgs A = pp_args(P);
     const PpGrid G = pp_grid_args(P);
+    const PpLists L = pp_lists(P);
     const int g = (n + kBlock - 1) / kBlock;
     hipStream_t s = P->stream;
     if (P->heat)
-        k_pp_points<true><<<g, kBlock, 0, s>>>(n, A, G, P->pp_cell_ptr.p, P->pp_cell_el.p, P->pp_nbig, P->pp_big.p, px,
-                                               py, smooth ? 1 : 0, P->pp_D.p, P->pp_d.p, P->pp_pel.p, o, ntests);
+        k_pp_points<true><<<g, kBlock, 0, s>>>(n, A, G, L, px, py, smooth ? 1 : 0, P->pp_D.p, P->pp_d.p, P->pp_pel.p, o,
+                                               ntests);
     else
-        k_pp_points<false><<<g, kBlock, 0, s>>>(n, A, G, P->pp_cell_ptr.p, P->pp_cell_el.p, P->pp_nbig, P->pp_big.p, px,
-                                                py, smooth ? 1 : 0, P->pp_D.p, P->pp_d.p, P->pp_pel.p, o, ntests);
+        k_pp_points<false><<<g, kBlock, 0, s>>>(n, A, G, L, px, py, smooth ? 1 : 0, P->pp_D.p, P->pp_d.p, P->pp_pel.p, o,
+                                                ntests);
     XFK_CHECK(hipGetLastError());
     return XFK_OK;
 }
@@ -1361,7 +1522,254 @@ static int pp_stress_integrals(xfk_problem *P, double *out3)
     return XFK_OK;
 }
 
+// --- contour integrals: host side ---------------------------------------------
+
+constexpr int kPpLineIntegralPoints = 400;   // d_LineIntegralPoints (PostProcessor.cpp:76)
+
+// A batch of contours checked and laid out for k_pp_contour
+struct PpContours {
+    int nc = 0, type = 0, smooth = 0, npts = 0;
+    std::vector<int> cptr, bptr;   // vertices and workgroups of each contour
+    DBuf<int> d_cptr, d_bptr;
+    DBuf<double> d_xy;             // the vertices: all x, then all y
+    DBuf<double> part;             // 3 per workgroup, then 3 per contour
+    int groups() const { return bptr.empty() ? 0 : bptr.back(); }
+    double *sums() { return part.p + 3 * (size_t)groups(); }
+};
+
+static int pp_contour_check(const xfk_problem *P, int nc, const int *ptr, const double *x, const double *y,
+                            int type)
+{
+    XFK_REQUIRE(nc >= 0, XFK_ERR_ARG, "negative number of contours");
+    XFK_REQUIRE(type >= 0, XFK_ERR_ARG, "line integral type out of range (negative)");
+    XFK_REQUIRE(!P->heat || type <= 3, XFK_ERR_ARG,
+                "line integral type out of range: a heat-flow problem has types 0-3 (the stress tensor force and "
+                "torque, 3 and 4, are electrostatic)");
+    XFK_REQUIRE(!P->electro || type <= 4, XFK_ERR_ARG, "line integral type out of range: an electrostatic problem has types 0-4");
+    if (nc == 0) return XFK_OK;
+    XFK_REQUIRE(ptr && x && y, XFK_ERR_ARG, "null contour arrays");
+    XFK_REQUIRE(ptr[0] >= 0, XFK_ERR_ARG, "contour offsets must start at 0 or above and not decrease");
+    for (int c = 0; c < nc; ++c) {
+        XFK_REQUIRE(ptr[c + 1] >= ptr[c], XFK_ERR_ARG, "contour offsets must start at 0 or above and not decrease");
+        XFK_REQUIRE(ptr[c + 1] - ptr[c] >= 2, XFK_ERR_ARG, "a contour needs at least 2 points");
+        for (int k = ptr[c]; k < ptr[c + 1]; ++k) {
+            XFK_REQUIRE(x[k] == x[k] && y[k] == y[k], XFK_ERR_ARG, "a contour vertex is NaN");
+            XFK_REQUIRE(std::isfinite(x[k]) && std::isfinite(y[k]), XFK_ERR_ARG, "a contour vertex is infinite");
+            if (k > ptr[c]) {
+                const double len = pp_cabs(x[k] - x[k - 1], y[k] - y[k - 1]);
+                XFK_REQUIRE(len > 0, XFK_ERR_ARG, "a contour has a zero-length segment (two equal consecutive points)");
+                XFK_REQUIRE(std::isfinite(len), XFK_ERR_ARG, "a contour segment's length overflows");
+            }
+        }
+    }
+    return XFK_OK;
+}
+
+// types 1, 3, 4 (heat flow: 1, 3): the batch on the device, the fields and the grid ready
+static int pp_contour_prepare(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, int type,
+                              int smooth, int npts, PpContours &J)
+{
+    hipStream_t s = P->stream;
+    J.nc = nc;
+    J.type = type;
+    J.smooth = smooth ? 1 : 0;
+    J.npts = npts <= 0 ? kPpLineIntegralPoints : npts;
+    J.cptr.assign(nc + 1, 0);
+    J.bptr.assign(nc + 1, 0);
+    long long groups = 0;
+    for (int c = 0; c < nc; ++c) {
+        const long long samples = (long long)(ptr[c + 1] - ptr[c] - 1) * J.npts;
+        XFK_REQUIRE(samples < (1LL << 31) - kPotQBlock, XFK_ERR_ARG, "a contour has too many samples (segments x points >= 2^31)");
+        groups += (samples + kPotQBlock - 1) / kPotQBlock;
+        XFK_REQUIRE(groups < (1LL << 31), XFK_ERR_ARG, "the batch has too many samples (2^31 workgroups)");
+        J.cptr[c + 1] = ptr[c + 1] - ptr[0];
+        J.bptr[c + 1] = (int)groups;
+    }
+    int rc = J.smooth ? pp_corners(P, nullptr) : pp_fields(P);
+    if (rc == XFK_OK) rc = pp_grid(P);
+    if (rc != XFK_OK) return rc;
+    const size_t nv = (size_t)J.cptr[nc];
+    XFK_CHECK(J.d_xy.alloc(2 * nv));
+    XFK_CHECK(hipMemcpyAsync(J.d_xy.p, x + ptr[0], sizeof(double) * nv, hipMemcpyHostToDevice, s));
+    XFK_CHECK(hipMemcpyAsync(J.d_xy.p + nv, y + ptr[0], sizeof(double) * nv, hipMemcpyHostToDevice, s));
+    XFK_CHECK(upload(J.d_cptr, J.cptr.data(), J.cptr.size(), s));
+    XFK_CHECK(upload(J.d_bptr, J.bptr.data(), J.bptr.size(), s));
+    XFK_CHECK(J.part.alloc(3 * ((size_t)groups + nc)));
+    return XFK_OK;
+}
+
+// the sample kernel and the per-contour sums; dbg_xy, dbg_el: one contour's samples (may be null)
+static int pp_contour_launch(xfk_problem *P, PpContours &J, double *dbg_xy, int *dbg_el)
+{
+    const PpArgs A = pp_args(P);
+    const PpGrid G = pp_grid_args(P);
+    const PpLists L = pp_lists(P);
+    hipStream_t s = P->stream;
+    const double *cx = J.d_xy.p, *cy = cx + J.cptr[J.nc];
+    if (P->heat)
+        k_pp_contour<true><<<J.groups(), kPotQBlock, 0, s>>>(J.nc, A, G, L, J.d_cptr.p, J.d_bptr.p, cx, cy, J.npts,
+                                                             J.type, J.smooth, P->pp_D.p, P->pp_d.p, J.part.p, dbg_xy,
+                                                             dbg_el);
+    else
+        k_pp_contour<false><<<J.groups(), kPotQBlock, 0, s>>>(J.nc, A, G, L, J.d_cptr.p, J.d_bptr.p, cx, cy, J.npts,
+                                                              J.type, J.smooth, P->pp_D.p, P->pp_d.p, J.part.p, dbg_xy,
+                                                              dbg_el);
+    k_pp_contour_sum<<<J.nc, kPotQBlock, 0, s>>>(J.d_bptr.p, J.part.p, J.sums());
+    XFK_CHECK(hipGetLastError());
+    return XFK_OK;
+}
+
+// lineIntegral type 0: V (T) at the first point minus at the last, through the point kernel
+static int pp_contour_ends(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, double *out,
+                           int *missed)
+{
+    int rc = pp_fields(P);
+    if (rc == XFK_OK) rc = pp_grid(P);
+    if (rc != XFK_OK) return rc;
+    const int n = 2 * nc;
+    std::vector<double> ex(n), ey(n), val(8 * (size_t)n);
+    for (int c = 0; c < nc; ++c) {
+        ex[2 * c] = x[ptr[c]];
+        ey[2 * c] = y[ptr[c]];
+        ex[2 * c + 1] = x[ptr[c + 1] - 1];
+        ey[2 * c + 1] = y[ptr[c + 1] - 1];
+    }
+    if ((rc = pp_upload_points(P, n, ex.data(), ey.data())) != XFK_OK) return rc;
+    double *px = P->pp_pts.p, *o = px + 2 * (size_t)n;
+    if ((rc = pp_launch_points(P, n, px, px + n, 0, o, nullptr)) != XFK_OK) return rc;
+    std::vector<int> el(n);
+    XFK_CHECK(d2h(el.data(), P->pp_pel.p, sizeof(int) * (size_t)n, P->stream));
+    XFK_CHECK(d2h(val.data(), o, sizeof(double) * 8 * (size_t)n, P->stream));
+    for (int c = 0; c < nc; ++c) {
+        double r = val[8 * (size_t)(2 * c)];
+        r -= val[8 * (size_t)(2 * c + 1)];
+        out[2 * c] = r;
+        out[2 * c + 1] = 0.;
+        if (missed) missed[c] = (el[2 * c] < 0) + (el[2 * c + 1] < 0);
+    }
+    return XFK_OK;
+}
+
+// lineIntegral type 2 (epproc.cpp:574-595, hpproc.cpp:727-744): length and swept area, on the host
+static void pp_contour_length(const xfk_problem *P, int n, const double *x, const double *y, double *out2)
+{
+    const double lc = kPpLengthConv[P->pot_length_units];
+    const double depth = P->pot_depth_user == -1 ? 1 : P->pot_depth_user * lc;
+    out2[0] = 0;
+    out2[1] = 0;
+    for (int i = 0; i < n - 1; ++i) out2[0] += pp_cabs(x[i + 1] - x[i], y[i + 1] - y[i]);
+    out2[0] *= lc;
+    if (P->axi) {
+        for (int i = 0; i < n - 1; ++i) out2[1] += (kPI * (x[i] + x[i + 1]) * pp_cabs(x[i + 1] - x[i], y[i + 1] - y[i]));
+        out2[1] *= P->heat ? std::pow(lc, 2.) : lc * lc;
+    } else {
+        out2[1] = out2[0] * depth;
+    }
+}
+
+static int pp_line_integrals(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, int type,
+                             int smooth, int npts, double *out, int *missed)
+{
+    int rc = pp_contour_check(P, nc, ptr, x, y, type);
+    if (rc != XFK_OK || nc == 0) return rc;
+    XFK_REQUIRE(out, XFK_ERR_ARG, "null output");
+    if (type == 0) return pp_contour_ends(P, nc, ptr, x, y, out, missed);
+    if (type == 2) {
+        for (int c = 0; c < nc; ++c) {
+            pp_contour_length(P, ptr[c + 1] - ptr[c], x + ptr[c], y + ptr[c], out + 2 * c);
+            if (missed) missed[c] = 0;
+        }
+        return XFK_OK;
+    }
+    PpContours J;
+    if ((rc = pp_contour_prepare(P, nc, ptr, x, y, type, smooth, npts, J)) != XFK_OK) return rc;
+    if ((rc = pp_contour_launch(P, J, nullptr, nullptr)) != XFK_OK) return rc;
+    std::vector<double> sums(3 * (size_t)nc);
+    XFK_CHECK(d2h(sums.data(), J.sums(), sizeof(double) * sums.size(), P->stream));
+    for (int c = 0; c < nc; ++c) {
+        double r0 = sums[3 * (size_t)c], r1 = sums[3 * (size_t)c + 1];
+        // the averages, divided after the loop as the reference does
+        if (type == 1) r1 = r0 / r1;
+        else if (P->heat) r0 = r0 / r1;   // (type 3: the weight sum stays in r1)
+        out[2 * c] = r0;
+        out[2 * c + 1] = r1;
+        if (missed) missed[c] = (int)sums[3 * (size_t)c + 2];
+    }
+    return XFK_OK;
+}
+
 extern "C" {
+
+int xfk_pot_line_integrals(xfk_problem *P, int n_contours, const int *ptr, const double *x, const double *y,
+                           int type, int smooth, int npts, double *out, int *missed)
+{
+    return pp_entry(P, true, [&]() -> int {
+        return pp_line_integrals(P, n_contours, ptr, x, y, type, smooth, npts, out, missed);
+    });
+}
+
+int xfk_pot_line_integral(xfk_problem *P, int n, const double *x, const double *y, int type, int smooth, int npts,
+                          double *out2, int *missed)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of contour points");
+        const int ptr[2] = {0, n};
+        return pp_line_integrals(P, 1, ptr, x, y, type, smooth, npts, out2, missed);
+    });
+}
+
+int xfk_pot_contour_samples(xfk_problem *P, int n, const double *x, const double *y, int type, int npts, double *xy,
+                            int *elem)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of contour points");
+        const int ptr[2] = {0, n};
+        int rc = pp_contour_check(P, 1, ptr, x, y, type);
+        if (rc != XFK_OK) return rc;
+        XFK_REQUIRE(type != 0 && type != 2, XFK_ERR_ARG, "line integral types 0 and 2 take no samples");
+        XFK_REQUIRE(xy && elem, XFK_ERR_ARG, "null output");
+        PpContours J;
+        if ((rc = pp_contour_prepare(P, 1, ptr, x, y, type, 0, npts, J)) != XFK_OK) return rc;
+        const size_t ns = (size_t)(n - 1) * J.npts;
+        DBuf<double> dxy;
+        DBuf<int> del;
+        XFK_CHECK(dxy.alloc(2 * ns));
+        XFK_CHECK(del.alloc(ns));
+        if ((rc = pp_contour_launch(P, J, dxy.p, del.p)) != XFK_OK) return rc;
+        XFK_CHECK(d2h(xy, dxy.p, sizeof(double) * 2 * ns, P->stream));
+        XFK_CHECK(d2h(elem, del.p, sizeof(int) * ns, P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_contour_time(xfk_problem *P, int n_contours, const int *ptr, const double *x, const double *y, int type,
+                         int smooth, int npts, int repeats, double *ms)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(repeats > 0 && ms && n_contours > 0, XFK_ERR_ARG,
+                    "xfk_pot_contour_time needs contours, repeats > 0 and its output");
+        int rc = pp_contour_check(P, n_contours, ptr, x, y, type);
+        if (rc != XFK_OK) return rc;
+        XFK_REQUIRE(type != 0 && type != 2, XFK_ERR_ARG, "line integral types 0 and 2 launch no contour kernel");
+        PpContours J;
+        if ((rc = pp_contour_prepare(P, n_contours, ptr, x, y, type, smooth, npts, J)) != XFK_OK) return rc;
+        ScopedEvents<2> ev;
+        XFK_CHECK(ev.create());
+        std::vector<double> t;
+        for (int k = 0; k <= repeats; ++k) {   // (the first a warm-up)
+            XFK_CHECK(hipEventRecord(ev[0], P->stream));
+            if ((rc = pp_contour_launch(P, J, nullptr, nullptr)) != XFK_OK) return rc;
+            XFK_CHECK(hipEventRecord(ev[1], P->stream));
+            XFK_CHECK(hipEventSynchronize(ev[1]));
+            float m = 0;
+            XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
+            if (k) t.push_back(m);
+        }
+        std::sort(t.begin(), t.end());
+        *ms = t[t.size() / 2];
+        return XFK_OK;
+    });
+}
 
 int xfk_pot_set_solution(xfk_problem *P, const double *V)
 {

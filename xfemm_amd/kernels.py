@@ -7,6 +7,7 @@ is present, every solve raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Sequence
 
@@ -62,6 +63,7 @@ EXPORTED = (
     "xfk_pot_set_solution", "xfk_pot_element_fields", "xfk_pot_corner_fields", "xfk_pot_corner_branches",
     "xfk_pot_block_integrals", "xfk_pot_block_integral", "xfk_pot_point_values", "xfk_pot_grid_info", "xfk_pot_time",
     "xfk_pot_make_mask", "xfk_pot_get_mask", "xfk_pot_mask_info", "xfk_pot_mask_problem", "xfk_pot_stress_time",
+    "xfk_pot_line_integrals", "xfk_pot_line_integral", "xfk_pot_contour_samples", "xfk_pot_contour_time",
     "xfk_amg_probe_create", "xfk_amg_probe_info", "xfk_amg_probe_level_size", "xfk_amg_probe_level_csr",
     "xfk_amg_probe_tiles", "xfk_amg_probe_vector", "xfk_amg_probe_trace", "xfk_amg_probe_apply",
     "xfk_amg_probe_refresh", "xfk_amg_probe_destroy",
@@ -331,6 +333,10 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_pot_grid_info.argtypes = [C.c_void_p, dptr]
     L.xfk_pot_time.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, dptr, dptr]
     L.xfk_pot_point_values.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, iptr, dptr]
+    L.xfk_pot_line_integrals.argtypes = [C.c_void_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_int, C.c_int, dptr, iptr]
+    L.xfk_pot_line_integral.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, C.c_int, C.c_int, dptr, iptr]
+    L.xfk_pot_contour_samples.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, C.c_int, dptr, iptr]
+    L.xfk_pot_contour_time.argtypes = [C.c_void_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_int, C.c_int, C.c_int, dptr]
     L.xfk_sort_elements.argtypes = [C.c_int, C.POINTER(C.c_uint), C.c_int, iptr]
     L.xfk_magdir_eval.argtypes = [C.c_char_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_double, dptr]
     L.xfk_lua_run.argtypes = [C.c_char_p, C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong)]
@@ -698,6 +704,68 @@ class Static2DProblem:
         return out
 
 
+class Contour:
+    """The contour of the reference's post-processors, built on the host as
+    PostProcessor builds it: a list of (x, y) in the problem's length units."""
+
+    def __init__(self, points=()):
+        self.points = []
+        for x, y in points:
+            self.add(x, y)
+
+    def __len__(self):
+        return len(self.points)
+
+    def add(self, x, y):
+        """addContourPoint (PostProcessor.cpp:167-171): a point equal to the last is dropped."""
+        z = (float(x), float(y))
+        if not self.points or z != self.points[-1]:
+            self.points.append(z)
+        return self
+
+    def clear(self):
+        """clearContour."""
+        self.points = []
+        return self
+
+    def bend(self, angle, step=1.0):
+        """bendContour (PostProcessor.cpp:772-820): the last segment becomes an
+        arc of `angle` degrees in steps of `step` (0: 1).  An angle of 0 or
+        outside +-180, or a contour of fewer than two points, changes nothing."""
+        pi = 3.141592653589793238462643383
+        if angle == 0:
+            return self
+        if step == 0:
+            step = 1
+        k = len(self.points) - 1
+        if k < 1:
+            return self
+        if angle < -180. or angle > 180.:
+            return self
+        n = int(math.ceil(abs(angle / step)))
+        tta = angle * pi / 180.
+        dtta = tta / float(n)
+        a1 = self.points.pop(k)
+        a0 = self.points[k - 1]
+        dr, di = a1[0] - a0[0], a1[1] - a0[1]
+        if dr == 0 and di == 0:
+            d = 0.
+        elif abs(dr) > abs(di):
+            d = abs(dr) * math.sqrt(1. + (di / dr) * (di / dr))
+        else:
+            d = abs(di) * math.sqrt(1. + (dr / di) * (dr / di))
+        R = d / (2. * math.sin(abs(tta / 2.)))
+        ph = (pi - tta) / 2. if tta > 0 else (-1. * (pi + tta)) / 2.
+        er, ei = math.cos(ph), math.sin(ph)
+        sr, si = (R / d) * dr, (R / d) * di
+        cr, ci = a0[0] + (sr * er - si * ei), a0[1] + (sr * ei + si * er)
+        vr, vi = a0[0] - cr, a0[1] - ci
+        for k in range(1, n + 1):
+            er, ei = math.cos(float(k) * dtta), math.sin(float(k) * dtta)
+            self.points.append((cr + (vr * er - vi * ei), ci + (vr * ei + vi * er)))
+        return self
+
+
 class _PotentialPostProc:
     """Post-processing shared by ElectrostaticProblem and HeatFlowProblem (the
     reference's epproc / hpproc on the device, xfk_pot_*).  _POINT_NAMES: the
@@ -802,6 +870,69 @@ class _PotentialPostProc:
         for name, cols in self._POINT_NAMES:
             r[name] = o[:, cols].copy()
         return r
+
+    @staticmethod
+    def _contour_xy(contour):
+        pts = contour.points if isinstance(contour, Contour) else contour
+        a = np.asarray(pts)
+        if a.ndim == 1 and np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=1)
+        a = np.asarray(a, dtype=np.float64).reshape(-1, 2)
+        return np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1])
+
+    def line_integrals(self, contours, kind: int, smooth: bool = True, points: int = 400) -> dict:
+        """The reference's lineIntegral of type `kind` (its numbering) over a
+        batch of contours: each a Contour, a sequence of (x, y) or of complex
+        points, in the problem's length units.  raw: (n, 2), the two results
+        per contour; missed: per contour the samples no element contains
+        (they add nothing).  Every contour's result has the bits it has when
+        integrated alone."""
+        xy = [self._contour_xy(c) for c in contours]
+        n = len(xy)
+        ptr = np.zeros(n + 1, np.int32)
+        ptr[1:] = np.cumsum([len(x) for x, _ in xy])
+        x = np.ascontiguousarray(np.concatenate([x for x, _ in xy] + [np.zeros(1)]))
+        y = np.ascontiguousarray(np.concatenate([y for _, y in xy] + [np.zeros(1)]))
+        o = np.zeros((max(1, n), 2))
+        missed = np.zeros(max(1, n), np.int32)
+        _check(_lib.xfk_pot_line_integrals(self._h, n, ptr.ctypes.data_as(iptr), x.ctypes.data_as(dptr),
+                                           y.ctypes.data_as(dptr), int(kind), int(bool(smooth)), int(points),
+                                           o.ctypes.data_as(dptr), missed.ctypes.data_as(iptr)))
+        return {"raw": o[:n], "missed": missed[:n]}
+
+    def line_integral(self, contour, kind: int, smooth: bool = True, points: int = 400) -> complex:
+        """One contour's lineIntegral of type `kind`: the two results as a
+        complex number (xfk_pot_line_integral)."""
+        x, y = self._contour_xy(contour)
+        o = np.zeros(2)
+        _check(_lib.xfk_pot_line_integral(self._h, len(x), x.ctypes.data_as(dptr), y.ctypes.data_as(dptr), int(kind),
+                                          int(bool(smooth)), int(points), o.ctypes.data_as(dptr), None))
+        return complex(o[0], o[1])
+
+    def contour_samples(self, contour, kind: int, points: int = 400) -> dict:
+        """Diagnostic: the samples of one contour as the kernel makes them, xy
+        (n, 2) and the element each took, -1 for none (xfk_pot_contour_samples)."""
+        x, y = self._contour_xy(contour)
+        ns = max(0, len(x) - 1) * (int(points) if points > 0 else 400)
+        xy = np.zeros((max(1, ns), 2))
+        el = np.zeros(max(1, ns), np.int32)
+        _check(_lib.xfk_pot_contour_samples(self._h, len(x), x.ctypes.data_as(dptr), y.ctypes.data_as(dptr), int(kind),
+                                            int(points), xy.ctypes.data_as(dptr), el.ctypes.data_as(iptr)))
+        return {"xy": xy[:ns], "elem": el[:ns]}
+
+    def time_contours(self, contours, kind: int, smooth: bool = True, points: int = 400, repeats: int = 5) -> float:
+        """Diagnostic: HIP-event ms (median) of the contour kernel and its sums
+        over the batch (xfk_pot_contour_time)."""
+        xy = [self._contour_xy(c) for c in contours]
+        ptr = np.zeros(len(xy) + 1, np.int32)
+        ptr[1:] = np.cumsum([len(x) for x, _ in xy])
+        x = np.ascontiguousarray(np.concatenate([x for x, _ in xy]))
+        y = np.ascontiguousarray(np.concatenate([y for _, y in xy]))
+        ms = C.c_double()
+        _check(_lib.xfk_pot_contour_time(self._h, len(xy), ptr.ctypes.data_as(iptr), x.ctypes.data_as(dptr),
+                                         y.ctypes.data_as(dptr), int(kind), int(bool(smooth)), int(points),
+                                         int(repeats), C.byref(ms)))
+        return ms.value
 
 
 class ElectrostaticProblem(_PotentialPostProc):
