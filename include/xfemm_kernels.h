@@ -668,6 +668,12 @@ int xfk_hf_conductor_flow(xfk_problem *prob, int conductor, double *q);
  * after a solve, so xfk_get_conductors / xfk_hf_get_conductors describe the
  * loaded solution. */
 int xfk_pot_set_solution(xfk_problem *prob, const double *V);
+/* The mark of every node as the reference's L.Q holds it and its .res / .anh
+ * node lines carry it (n_nodes ints): a conductor's index on its nodes, else
+ * -1 on a node with a point property or on a BdryFormat 0 edge, else -2.
+ * Derived from the descriptor at creation (the post-processor's smoothing
+ * reads the same marks); no solution needed.  Host data: no device work. */
+int xfk_pot_get_qmarks(xfk_problem *prob, int *Q);
 /* Per element D (C/m^2) and E (V/m), or F (W/m^2) and G (K/m): x and y
  * components interleaved, 2 n_elems each.  Either may be NULL. */
 int xfk_pot_element_fields(xfk_problem *prob, double *D, double *E);

@@ -1,5 +1,6 @@
 // .fem parser and B-H curve preprocessing (see femm_problem.h).
 #include "femm_problem.h"
+#include "pot_problem.h"
 
 #include <algorithm>
 #include <cctype>
@@ -715,6 +716,187 @@ bool ParseFemFile(const std::string &path, FemmProblemData &pr, std::string &err
             return false;
         }
     }
+    return true;
+}
+
+bool ParsePotentialFile(const std::string &path, PotentialKind kind, PotProblemData &pr, std::string &err)
+{
+    const bool heat = kind == POT_HEATFLOW;
+    std::ifstream f(path);
+    if (!f.is_open()) {
+        err = std::string("Couldn't read from specified ") + (heat ? ".feh" : ".fee") + " file: " + path;
+        return false;
+    }
+    LineReader in;
+    std::string line;
+    while (std::getline(f, line)) in.lines.push_back(line);
+    pr = PotProblemData();
+    while (in.good()) {
+        std::string ln = trim(in.next());
+        if (ln.empty()) continue;
+        std::string tok = first_token(ln), rest;
+        // the geometry matters for the block labels only
+        if (tok == "[numpoints]" || tok == "[numsegments]" || tok == "[numarcsegments]" || tok == "[numholes]") {
+            int n = 0;
+            if (!rest_after_eq(ln, rest) || !parse_int(rest, n)) {
+                err = "bad count: " + ln;
+                return false;
+            }
+            for (int k = 0; k < n && in.good(); ++k) in.next();
+            continue;
+        }
+        if (!rest_after_eq(ln, rest)) {
+            err = "Unknown token: " + tok;
+            return false;
+        }
+        bool ok = true;
+        if (tok == "[format]") ok = parse_double(rest, pr.FileFormat);
+        else if (tok == "[precision]") ok = parse_double(rest, pr.Precision);
+        else if (tok == "[minangle]") ok = parse_double(rest, pr.MinAngle);
+        else if (tok == "[depth]") ok = parse_double(rest, pr.Depth);
+        else if (tok == "[lengthunits]") {
+            std::string u = first_token(rest);
+            if (u == "inches") pr.LengthUnits = LengthInches;
+            else if (u == "millimeters") pr.LengthUnits = LengthMillimeters;
+            else if (u == "centimeters") pr.LengthUnits = LengthCentimeters;
+            else if (u == "mils") pr.LengthUnits = LengthMils;
+            else if (u == "microns") pr.LengthUnits = LengthMicrometers;
+            else if (u == "meters") pr.LengthUnits = LengthMeters;
+        } else if (tok == "[coordinates]") {
+            std::string u = first_token(rest);
+            if (u == "cartesian") pr.Coords = CART;
+            if (u == "polar") pr.Coords = POLAR;
+        } else if (tok == "[problemtype]") {
+            std::string u = first_token(rest);
+            if (u == "planar") pr.ProblemTypeV = PLANAR;
+            if (u == "axisymmetric") pr.ProblemTypeV = AXISYMMETRIC;
+        } else if (tok == "[extzo]") ok = parse_double(rest, pr.extZo);
+        else if (tok == "[extro]") ok = parse_double(rest, pr.extRo);
+        else if (tok == "[extri]") ok = parse_double(rest, pr.extRi);
+        else if (tok == "[forcemaxmesh]" || tok == "[dosmartmesh]") {
+            // meshing options, unused by the solver
+        } else if (tok == "[comment]") ok = parse_string(rest, pr.comment);
+        else if (heat && tok == "[dt]") ok = parse_double(rest, pr.dT);
+        else if (heat && tok == "[prevsoln]") ok = parse_string(rest, pr.previousSolutionFile) || trim(rest) == "\"\"";
+        else if (tok == "[pointprops]") {
+            int k = 0;
+            ok = parse_int(rest, k);
+            for (int i = 0; ok && i < k; ++i) {
+                CPPointProp p;
+                ok = read_block(in, "<beginpoint>", "<endpoint>", err, [&](const std::string &t, const std::string &r, LineReader &) {
+                    if (t == "<pointname>") return parse_string(r, p.PointName);
+                    if (t == (heat ? "<tp>" : "<vp>")) return parse_double(r, p.V);
+                    if (t == "<qp>") return parse_double(r, p.qp);
+                    return true;
+                });
+                pr.nodeproplist.push_back(p);
+            }
+        } else if (tok == "[bdryprops]") {
+            int k = 0;
+            ok = parse_int(rest, k);
+            for (int i = 0; ok && i < k; ++i) {
+                CPBoundaryProp b;
+                ok = read_block(in, "<beginbdry>", "<endbdry>", err, [&](const std::string &t, const std::string &r, LineReader &) {
+                    if (t == "<bdryname>") return parse_string(r, b.BdryName);
+                    if (t == "<bdrytype>") return parse_int(r, b.BdryFormat);
+                    if (t == (heat ? "<tset>" : "<vs>")) return parse_double(r, b.V);
+                    if (t == "<qs>") return parse_double(r, b.qs);
+                    if (!heat && t == "<c0>") return parse_double(r, b.c0);
+                    if (!heat && t == "<c1>") return parse_double(r, b.c1);
+                    if (heat && t == "<beta>") return parse_double(r, b.beta);
+                    if (heat && t == "<h>") return parse_double(r, b.h);
+                    if (heat && t == "<tinf>") return parse_double(r, b.Tinf);
+                    return true;
+                });
+                pr.lineproplist.push_back(b);
+            }
+        } else if (tok == "[blockprops]") {
+            int k = 0;
+            ok = parse_int(rest, k);
+            for (int i = 0; ok && i < k; ++i) {
+                CPMaterialProp m;
+                ok = read_block(in, "<beginblock>", "<endblock>", err, [&](const std::string &t, const std::string &r, LineReader &ls) {
+                    if (t == "<blockname>") return parse_string(r, m.BlockName);
+                    if (t == (heat ? "<kx>" : "<ex>")) return parse_double(r, m.kx);
+                    if (t == (heat ? "<ky>" : "<ey>")) return parse_double(r, m.ky);
+                    if (heat && t == "<kt>") return parse_double(r, m.Kt);
+                    if (t == "<qv>") return parse_double(r, m.qv);
+                    if (heat && t == "<tkpoints>") {
+                        // CHMaterialProp::fromStream (CMaterialProp.cpp:1458-1475): at most 128 knots
+                        int npts = 0;
+                        if (!parse_int(r, npts) || npts < 0 || npts > 128) return false;
+                        std::vector<double> vals;
+                        while ((int)vals.size() < 2 * npts && ls.good()) {
+                            std::istringstream is(ls.next());
+                            double v;
+                            while (is >> v) vals.push_back(v);
+                        }
+                        if ((int)vals.size() != 2 * npts) return false;
+                        for (int q = 0; q < npts; ++q) {
+                            m.T.push_back(vals[2 * q]);
+                            m.K.push_back(vals[2 * q + 1]);
+                        }
+                        return true;
+                    }
+                    return true;
+                });
+                pr.blockproplist.push_back(m);
+            }
+        } else if (tok == "[conductorprops]") {
+            int k = 0;
+            ok = parse_int(rest, k);
+            for (int i = 0; ok && i < k; ++i) {
+                CPConductor c;
+                ok = read_block(in, "<beginconductor>", "<endconductor>", err, [&](const std::string &t, const std::string &r, LineReader &) {
+                    if (t == "<conductorname>") return parse_string(r, c.CircName);
+                    if (t == (heat ? "<tc>" : "<vc>")) return parse_double(r, c.V);
+                    if (t == "<qc>") return parse_double(r, c.q);
+                    if (t == "<conductortype>") return parse_int(r, c.CircType);
+                    return true;
+                });
+                pr.circproplist.push_back(c);
+            }
+        } else if (tok == "[numblocklabels]") {
+            int k = 0;
+            ok = parse_int(rest, k);
+            for (int i = 0; ok && i < k; ++i) {
+                // CSBlockLabel / CHBlockLabel::fromStream (CBlockLabel.cpp:194-290)
+                if (!in.good()) {
+                    ok = false;
+                    err = "block label list ends early";
+                    break;
+                }
+                std::istringstream is(trim(in.next()));
+                CPBlockLabel lb;
+                double maxarea = 0;
+                int extDefault = 0;
+                if (!(is >> lb.x >> lb.y >> lb.BlockType)) {
+                    ok = false;
+                    err = "bad block label";
+                    break;
+                }
+                lb.BlockType--;
+                if (is >> maxarea) lb.MaxArea = (maxarea <= 0) ? 0 : kPi * maxarea * maxarea / 4.;
+                is >> lb.InGroup >> extDefault;
+                lb.IsDefault = extDefault & 2;
+                lb.IsExternal = extDefault & 1;
+                pr.labellist.push_back(lb);
+            }
+        } else {
+            err = "Unknown token: " + tok + "\nContext line:\n" + ln;
+            return false;
+        }
+        if (!ok) {
+            if (err.empty()) err = "Parse error in line: " + ln;
+            err = "Parse error while reading input file " + path + "!\n" + err;
+            return false;
+        }
+    }
+    for (const auto &lb : pr.labellist)
+        if (lb.BlockType >= (int)pr.blockproplist.size()) {
+            err = "block label refers to an undefined block property\n";
+            return false;
+        }
     return true;
 }
 

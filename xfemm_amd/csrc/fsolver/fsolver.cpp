@@ -28,49 +28,17 @@
 #include "fastnum.h"
 #include "hostmem.h"
 #include "hostpool.h"
+#include "meshhost_impl.h"
 
 namespace xfemm {
 
-int PrintWarningMsg(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    int r = vfprintf(stderr, fmt, ap);
-    va_end(ap);
-    return r;
-}
+using namespace meshio;
 
-FSolver::FSolver() : WarnMessage(&PrintWarningMsg), PrintMessage(&PrintWarningMsg) {}
+FSolver::FSolver() {}
 
 FSolver::~FSolver()
 {
     if (ele_fmt_.joinable()) ele_fmt_.join();
-    join_hip_warmup();
-    join_removals();
-}
-
-void FSolver::start_hip_warmup()
-{
-    // a sharded FSolver's communicator has brought the device up already;
-    // XFEMM_NO_HIP_WARMUP=1 leaves the bring-up to the first device call
-    if (comm || hip_warm_.joinable() || std::getenv("XFEMM_NO_HIP_WARMUP")) return;
-    const int dev = device;
-    hip_warm_ = std::thread([dev] { (void)xfk_device_init(dev); });
-}
-
-void FSolver::join_hip_warmup()
-{
-    if (hip_warm_.joinable()) hip_warm_.join();
-}
-
-// The mesh files the reference deletes once read (fsolver.cpp:711-716,
-// cuthill.cpp:140): unlinking ~170 MB of page cache costs tens of ms, so it
-// runs beside the rest of runSolver and is joined before runSolver returns.
-void FSolver::remove_async(std::vector<std::string> paths)
-{
-    removers_.emplace_back([paths = std::move(paths)] {
-        for (const auto &p : paths) remove(p.c_str());
-    });
 }
 
 bool FSolver::writes_output() const { return !comm || xfk_comm_rank(comm) == 0; }
@@ -85,18 +53,6 @@ void FSolver::remove_mesh_files_after_collective_solve()
     for (const char *ext : {".ele", ".node", ".pbc", ".poly"}) v.push_back(PathName + ext);
     if (previousSolutionFile.empty()) v.push_back(PathName + ".edge");
     remove_async(std::move(v));
-}
-
-void FSolver::join_removals()
-{
-    for (auto &t : removers_) t.join();
-    removers_.clear();
-}
-
-void FSolver::warn(const std::string &msg)
-{
-    lastError = msg;
-    WarnMessage("%s", msg.c_str());
 }
 
 std::string FSolver::getErrorString(LoadMeshErr err)
@@ -118,7 +74,7 @@ std::string FSolver::getErrorString(LoadMeshErr err)
 
 bool FSolver::LoadProblemFile()
 {
-    start_hip_warmup();
+    if (!comm) start_hip_warmup();   // (a sharded FSolver's communicator has brought the device up already)
     Relax = 1.;
     std::string err;
     FemmProblemData &base = *this;
@@ -323,271 +279,27 @@ bool FSolver::loadPreviousSolution(bool loadAprev)
     return true;
 }
 
-namespace {
-// XFEMM_TRACE_LOAD=1: host milliseconds of the mesh-loading / renumbering stages on stderr
-struct LoadTrace {
-    bool on = std::getenv("XFEMM_TRACE_LOAD") != nullptr;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void mark(const char *what)
-    {
-        if (!on) return;
-        const auto n = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[load] %-24s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
-        t = n;
-    }
-};
-
-// Token readers with fscanf's semantics: "%i" (strtol base 0: decimal, 0x..,
-// leading-0 octal) and "%lf" (strtod).  Digit strings take a direct decimal
-// path (the value strtol gives); everything else goes through strtol /
-// strtod, so every value is the reference's fscanf value to the bit.  `nl`:
-// the token must lie on the current line (line-parallel parsing).
-inline bool ws(char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n' || c == '\v' || c == '\f'; }
-inline bool skip_ws(const char *&p, bool nl)
-{
-    if (nl) {
-        while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\v' || *p == '\f') ++p;
-        return *p && *p != '\n';
-    }
-    while (ws(*p)) ++p;
-    return *p != 0;
-}
-inline bool read_int(const char *&p, int &v, bool nl)
-{
-    if (!skip_ws(p, nl)) return false;
-    const char *q = p + (*p == '-' || *p == '+');
-    if (*q >= '1' && *q <= '9') {   // plain decimal (no octal / hex prefix)
-        long long a = 0;
-        const char *r = q;
-        while (*r >= '0' && *r <= '9' && r - q < 18) a = 10 * a + (*r++ - '0');
-        if (!(*r >= '0' && *r <= '9') && a <= 2147483648LL) {
-            v = (int)(*p == '-' ? -a : a);
-            p = r;
-            return true;
-        }
-    }
-    char *end = nullptr;
-    const long x = std::strtol(p, &end, 0);
-    if (end == p) return false;
-    v = (int)x;
-    p = end;
-    return true;
-}
-inline bool read_double(const char *&p, double &v, bool nl)
-{
-    if (!skip_ws(p, nl)) return false;
-    const char *end = nullptr;   // (strtod's value and extent, exact fast path: fastnum.h)
-    if (!fastnum::parse_double(p, v, &end)) return false;
-    p = end;
-    return true;
-}
-
-// [0, n) split over the host's cores (at most 16), f(begin, end) per part,
-// on the persistent pool (hostpool.h)
-template <class F>
-void par_for(long long n, long long min_per_thread, F f)
-{
-    HostPool &pool = HostPool::get();
-    const int T = (int)std::max<long long>(1, std::min<long long>((long long)pool.size(), n / std::max(1LL, min_per_thread)));
-    if (T <= 1) {
-        f(0LL, n);
-        return;
-    }
-    pool.run(T, [&](int t) { f(n * t / T, n * (t + 1) / T); });
-}
-
-// v = n copies of val, the storage first-touched by the pool's threads
-template <class T>
-void par_assign(BigVec<T> &v, size_t n, const T &val)
-{
-    huge_reserve(v, n);
-    v.clear();
-    v.resize(n);   // (NoInitAlloc: nothing written)
-    par_for((long long)n, 1 << 16, [&](long long a, long long b) {
-        for (long long k = a; k < b; k++) ::new (&v[k]) T(val);
-    });
-}
-
-// A whole mesh file in memory, read as the token stream fscanf sees.
-struct TextBuf {
-    // the file's bytes + a terminating NUL; not value-initialised (the
-    // parallel reads below fill it, each thread faulting in its own pages),
-    // on huge pages, kept for the next file of the mesh
-    struct Bytes {
-        HugeBuf<char> b;
-        size_t n = 0;   // bytes incl. the NUL
-        char *data() { return b.data(); }
-        const char *data() const { return b.data(); }
-        size_t size() const { return n; }
-        char &operator[](size_t i) { return b[i]; }
-    } d;
-    size_t pos = 0;
-    size_t hint = 0;      // bytes to allocate at least (the largest file to come)
-    double ms_count = 0;  // (trace: the record-count pass of the last records())
-    bool load(const std::string &path)
-    {
-        const int fd = ::open(path.c_str(), O_RDONLY);
-        if (fd < 0) return false;
-        struct stat st;
-        if (::fstat(fd, &st) != 0) {
-            ::close(fd);
-            return false;
-        }
-        const size_t n = (size_t)std::max<off_t>(0, st.st_size);
-        // (sized for the largest mesh file at the first load: .edge > .ele > .node for fmesher output)
-        if (!d.b.allocate(std::max<size_t>(n + 1, hint))) {
-            ::close(fd);
-            return false;
-        }
-        // chunks of >= 4 MiB read side by side (pread: no shared file offset)
-        const int T = (int)std::max<size_t>(1, std::min<size_t>(16, n >> 22));
-        std::vector<size_t> got(T, 0);
-        par_for(T, 1, [&](long long a, long long b) {
-            for (long long t = a; t < b; ++t) {
-                size_t o = n * t / T;
-                const size_t e = n * (t + 1) / T;
-                while (o < e) {
-                    const ssize_t r = ::pread(fd, d.b.data() + o, e - o, (off_t)o);
-                    if (r <= 0) break;
-                    o += (size_t)r;
-                    got[t] += (size_t)r;
-                }
-            }
-        });
-        ::close(fd);
-        size_t tot = 0;
-        for (size_t g : got) tot += g;
-        if (tot != n) return false;
-        d.b[n] = '\0';
-        d.n = n + 1;
-        pos = 0;
-        return true;
-    }
-    bool next_int(int &v)
-    {
-        const char *p = d.data() + pos;
-        if (!read_int(p, v, false)) return false;
-        pos = (size_t)(p - d.data());
-        return true;
-    }
-    // the first line's leading integer (fgets + sscanf "%i"), then the stream after that line
-    bool header_int(int &v)
-    {
-        const char *nl = std::strchr(d.data(), '\n');
-        std::string line(d.data(), nl ? (size_t)(nl - d.data()) : std::strlen(d.data()));
-        pos = nl ? (size_t)(nl - d.data()) + 1 : d.size() - 1;
-        return std::sscanf(line.c_str(), "%i", &v) == 1;
-    }
-    // `count` records from pos on, rec(p, index, nl) reading one record.
-    // When every record sits on a line of its own (fmesher's layout) the lines
-    // are parsed in parallel chunks -- the same values as the token stream;
-    // any other layout (a record over several lines, extra tokens on a line)
-    // is parsed as one sequential token stream, as fscanf reads it.
-    template <class Rec>
-    bool records(int count, Rec rec)
-    {
-        const char *base = d.data() + pos, *end = d.data() + d.size() - 1;
-        const long long len = end - base;
-        const int T = (int)std::max<long long>(1, std::min<long long>(HostPool::get().size(), len / (1 << 20)));
-        bool ok = T > 1;
-        const auto tc = std::chrono::steady_clock::now();
-        ms_count = 0;
-        if (ok) {
-            // chunk starts at line starts; records (non-blank lines) per chunk
-            std::vector<const char *> cs(T + 1);
-            cs[0] = base;
-            cs[T] = end;
-            for (int t = 1; t < T; ++t) {
-                const char *q = base + len * t / T;
-                while (q < end && q[-1] != '\n') ++q;
-                cs[t] = std::max(q, cs[t - 1]);
-            }
-            std::vector<long long> cnt(T + 1, 0);
-            par_for(T, 1, [&](long long a, long long b) {
-                for (long long t = a; t < b; ++t) {
-                    // lines found by memchr; a line counts when a non-blank
-                    // character precedes its end (leading blanks are few)
-                    long long c = 0;
-                    const char *q = cs[t], *const e = cs[t + 1];
-                    while (q < e) {
-                        const char *nl = static_cast<const char *>(std::memchr(q, '\n', (size_t)(e - q)));
-                        const char *le = nl ? nl : e;
-                        while (q < le && ws(*q)) ++q;
-                        c += q < le;
-                        q = nl ? nl + 1 : e;
-                    }
-                    cnt[t + 1] = c;
-                }
-            });
-            for (int t = 0; t < T; ++t) cnt[t + 1] += cnt[t];
-            ms_count = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc).count();
-            ok = cnt[T] >= count;
-            std::vector<char> good(T, 1);
-            if (ok)
-                par_for(T, 1, [&](long long a, long long b) {
-                    for (long long t = a; t < b; ++t) {
-                        long long k = cnt[t];
-                        const char *q = cs[t];
-                        while (q < cs[t + 1] && k < count) {
-                            const char *p = q;
-                            if (!skip_ws(p, true)) {   // blank line
-                                q = p + (*p == '\n');
-                                continue;
-                            }
-                            if (!rec(p, (int)k, true) || skip_ws(p, true)) {   // short record or extra tokens
-                                good[t] = 0;
-                                return;
-                            }
-                            ++k;
-                            q = p + (*p == '\n');
-                        }
-                    }
-                });
-            for (char g : good) ok = ok && g;
-        }
-        if (!ok) {   // the token stream, sequentially
-            const char *p = base;
-            for (int k = 0; k < count; ++k)
-                if (!rec(p, k, false)) return false;
-        }
-        return true;
-    }
-};
-}  // namespace
 
 LoadMeshErr FSolver::LoadMesh(bool deleteFiles)
 {
     if (meshLoadedFromPrevSolution) return NOERROR;   // fsolver.cpp:357-360
     LoadTrace tr;
     char s[1024];
-    std::string infile = PathName + ".node";
+    std::string infile;
     TextBuf tb;
     {   // one buffer for the three mesh files: the largest one's size
         struct stat st;
         for (const char *ext : {".node", ".ele", ".edge"})
             if (::stat((PathName + ext).c_str(), &st) == 0) tb.hint = std::max(tb.hint, (size_t)st.st_size + 1);
     }
-    if (!tb.load(infile)) return BADNODEFILE;
-    tr.mark("  .node read");
-    int k = 0, j = 0;
-    if (!tb.header_int(k)) return BADNODEFILE;
-    NumNodes = k;
-    par_assign(meshnode, (size_t)std::max(0, k), CNode());
+    int j = 0;
     const double conv = 100 * kLengthConvMeters[LengthUnits];
-    if (!tb.records(k, [&](const char *&p, int i, bool nl) {
-            int a, m;
-            CNode &node = meshnode[i];
-            if (!read_int(p, a, nl) || !read_double(p, node.x, nl) || !read_double(p, node.y, nl) ||
-                !read_int(p, m, nl))
-                return false;
+    if (!read_node_file(tb, meshnode, [conv](CNode &node, double x, double y, int m) {
             node.BoundaryMarker = (m > 1) ? m - 2 : -1;
-            node.x *= conv;   // lengths in cm (fsolver.cpp:386-388)
-            node.y *= conv;
-            return true;
+            node.x = x * conv;   // lengths in cm (fsolver.cpp:386-388)
+            node.y = y * conv;
         }))
         return BADNODEFILE;
-    if (tr.on) std::fprintf(stderr, "[load]   (record count pass %.1f ms)\n", tb.ms_count);
-    tr.mark("nodes");
 
     infile = PathName + ".pbc";
     FILE *fp = fopen(infile.c_str(), "rt");
@@ -634,90 +346,33 @@ LoadMeshErr FSolver::LoadMesh(bool deleteFiles)
     }
     fclose(fp);
 
-    infile = PathName + ".ele";
-    if (!tb.load(infile)) return BADELEMENTFILE;
-    tr.mark("  .ele read");
-    if (!tb.header_int(k)) return BADELEMENTFILE;
-    NumEls = k;
-    par_assign(meshele, (size_t)std::max(0, k), CMElement());
-    tr.mark("  element array");
+    if (!read_element_file(tb, meshele)) return BADELEMENTFILE;
     int defaultLabel = -1;
     for (int i = 0; i < (int)labellist.size(); i++)
         if (labellist[i].IsDefault) defaultLabel = i;
     auto remove_files = [&]() {
         for (const char *ext : {".ele", ".node", ".pbc", ".poly", ".edge"}) remove((PathName + ext).c_str());
     };
-    if (!tb.records(k, [&](const char *&p, int i, bool nl) {
-            int a;
-            CMElement &elm = meshele[i];
-            return read_int(p, a, nl) && read_int(p, elm.p[0], nl) && read_int(p, elm.p[1], nl) &&
-                   read_int(p, elm.p[2], nl) && read_int(p, elm.lbl, nl);
-        }))
-        return BADELEMENTFILE;
-    if (tr.on) std::fprintf(stderr, "[load]   (record count pass %.1f ms)\n", tb.ms_count);
-    tr.mark("  element records");
     {
-        // labels and node ids checked per element, in parallel; the first
-        // failing element (in file order) decides the error, as the
-        // reference's sequential loop does (fsolver.cpp:593-626)
-        const int nl = (int)labellist.size();
-        const int T = 64;
-        std::vector<int> bad_at(T, -1), bad_code(T, 0);
-        par_for(T, 1, [&](long long t0, long long t1) {
-            for (long long t = t0; t < t1; ++t) {
-                const int a = (int)((long long)k * t / T), b = (int)((long long)k * (t + 1) / T);
-                for (int i = a; i < b; i++) {
-                    CMElement &elm = meshele[i];
-                    elm.lbl--;
-                    if (elm.lbl < 0) elm.lbl = defaultLabel;
-                    int code = 0;
-                    if (elm.lbl < 0) code = 1;
-                    else if (elm.lbl >= nl) code = 2;
-                    else
-                        for (int q = 0; q < 3; q++)
-                            if (elm.p[q] < 0 || elm.p[q] >= NumNodes) code = 3;
-                    if (code) {
-                        bad_at[t] = i;
-                        bad_code[t] = code;
-                        break;
-                    }
-                    elm.blk = labellist[elm.lbl].BlockType;
-                }
-            }
-        });
-        for (int t = 0; t < T; ++t) {
-            if (bad_at[t] < 0) continue;
-            const int i = bad_at[t];
-            if (bad_code[t] == 1) {
-                char buf[256];
-                snprintf(buf, sizeof buf, "The element number %i had label %i\n", i, meshele[i].lbl);
-                warn(std::string("Material properties have not been defined for all regions.\n") + buf);
-                if (deleteFiles) remove_files();
-                return MISSINGMATPROPS;
-            }
-            if (bad_code[t] == 2) {
-                if (deleteFiles) remove_files();
-                return ELMLABELTOOBIG;
-            }
-            return BADELEMENTFILE;
+        const ElementCheck bad = check_elements(meshele, (int)labellist.size(), defaultLabel,
+                                                [&](int lbl) { return labellist[lbl].BlockType; });
+        if (bad.code == 1) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "The element number %i had label %i\n", bad.index, meshele[bad.index].lbl);
+            warn(std::string("Material properties have not been defined for all regions.\n") + buf);
+            if (deleteFiles) remove_files();
+            return MISSINGMATPROPS;
         }
+        if (bad.code == 2) {
+            if (deleteFiles) remove_files();
+            return ELMLABELTOOBIG;
+        }
+        if (bad.code) return BADELEMENTFILE;
     }
     tr.mark("elements");
 
-    infile = PathName + ".edge";
-    if (!tb.load(infile)) return BADEDGEFILE;
-    tr.mark("  .edge read");
-    int nedge = 0, flag = 0;
-    if (!tb.next_int(nedge) || !tb.next_int(flag)) return BADEDGEFILE;
-    par_assign(edges_, (size_t)std::max(0, nedge), std::array<int, 3>{0, 0, 0});
-    if (nedge > 0 && !tb.records(nedge, [&](const char *&p, int i, bool nl) {
-            int a;
-            auto &e = edges_[i];
-            return read_int(p, a, nl) && read_int(p, e[0], nl) && read_int(p, e[1], nl) && read_int(p, e[2], nl);
-        }))
-        return BADEDGEFILE;
-    if (tr.on) std::fprintf(stderr, "[load]   (record count pass %.1f ms)\n", tb.ms_count);
-    tr.mark("edge records");
+    std::vector<int> marked;
+    if (!read_edge_file(tb, marked)) return BADEDGEFILE;
     // boundary-marked edges (marker < 0) set the boundary property of the
     // element sides they match (fsolver.cpp:660-704: per edge, every element
     // around its first node whose side k joins the two nodes).  The last such
@@ -726,35 +381,16 @@ LoadMeshErr FSolver::LoadMesh(bool deleteFiles)
     // filled in file order, looked up per element side in parallel -- no
     // node -> element membership lists
     {
-        const int T = 64;
-        std::vector<char> bad(T, 0);
-        std::vector<std::vector<int>> marked(T);
-        par_for(T, 1, [&](long long t0, long long t1) {
-            for (long long t = t0; t < t1; ++t) {
-                const int a = (int)((long long)nedge * t / T), b = (int)((long long)nedge * (t + 1) / T);
-                for (int i = a; i < b; i++) {
-                    const auto &e = edges_[i];
-                    if (e[0] < 0 || e[1] < 0 || e[0] >= NumNodes || e[1] >= NumNodes) {
-                        bad[t] = 1;
-                        break;
-                    }
-                    if (e[2] < 0) marked[t].push_back(i);
-                }
-            }
-        });
-        for (char c : bad)
-            if (c) return BADEDGEFILE;
         std::unordered_map<unsigned long long, int> side_bc;
         std::vector<char> on_marked(NumNodes, 0);
         auto pair_key = [](int a, int b) {
             return ((unsigned long long)(unsigned)std::min(a, b) << 32) | (unsigned)std::max(a, b);
         };
-        for (auto &m : marked)
-            for (int i : m) {
-                const auto &e = edges_[i];
-                side_bc[pair_key(e[0], e[1])] = -(e[2] + 2);
-                on_marked[e[0]] = on_marked[e[1]] = 1;
-            }
+        for (int i : marked) {
+            const auto &e = edges_[i];
+            side_bc[pair_key(e[0], e[1])] = -(e[2] + 2);
+            on_marked[e[0]] = on_marked[e[1]] = 1;
+        }
         if (!side_bc.empty())
             par_for(NumEls, 1 << 15, [&](long long a, long long b) {
                 for (long long i = a; i < b; i++) {
@@ -773,516 +409,15 @@ LoadMeshErr FSolver::LoadMesh(bool deleteFiles)
     return NOERROR;
 }
 
-namespace {
-// one run of comb-sort compare-swaps x[i] <-> y[i] (score = high 32 bits,
-// swap on a strict decrease); x and y do not overlap.  Branch-free: a wide
-// pass meets random data, whose swaps mispredict half the time.  Returns
-// nonzero when anything moved.
-__attribute__((target("avx2"))) unsigned long long comb_swap_run_avx2(unsigned long long *__restrict x,
-                                                                       unsigned long long *__restrict y, int n)
-{
-    __m256i anyv = _mm256_setzero_si256();
-    int i = 0;
-    for (; i + 4 <= n; i += 4) {
-        const __m256i a = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(x + i));
-        const __m256i b = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(y + i));
-        // (scores < 2^32: the signed 64-bit compare of the shifted keys is the unsigned one)
-        const __m256i m = _mm256_cmpgt_epi64(_mm256_srli_epi64(a, 32), _mm256_srli_epi64(b, 32));
-        _mm256_storeu_si256(reinterpret_cast<__m256i *>(x + i), _mm256_blendv_epi8(a, b, m));
-        _mm256_storeu_si256(reinterpret_cast<__m256i *>(y + i), _mm256_blendv_epi8(b, a, m));
-        anyv = _mm256_or_si256(anyv, m);
-    }
-    unsigned long long any = (unsigned long long)_mm256_movemask_epi8(anyv);
-    for (; i < n; ++i) {
-        const unsigned long long a = x[i], b = y[i];
-        const unsigned long long m = 0ULL - (unsigned long long)((a >> 32) > (b >> 32));
-        x[i] = (a & ~m) | (b & m);
-        y[i] = (b & ~m) | (a & m);
-        any |= m;
-    }
-    return any;
-}
-unsigned long long comb_swap_run_plain(unsigned long long *__restrict x, unsigned long long *__restrict y, int n)
-{
-    unsigned long long any = 0;
-    for (int i = 0; i < n; ++i) {
-        const unsigned long long a = x[i], b = y[i];
-        const unsigned long long m = 0ULL - (unsigned long long)((a >> 32) > (b >> 32));
-        x[i] = (a & ~m) | (b & m);
-        y[i] = (b & ~m) | (a & m);
-        any |= m;
-    }
-    return any;
-}
-unsigned long long comb_swap_run(unsigned long long *x, unsigned long long *y, int n)
-{
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    return avx2 ? comb_swap_run_avx2(x, y, n) : comb_swap_run_plain(x, y, n);
-}
 
-// Narrow comb passes as scans (see SortElements).  op(c, x): the carried
-// entry c stays only on a strictly greater score; the all-zero key (score 0)
-// is its identity from the left, so a class's first entry needs no special
-// case.  Rows of g positions: lane c of a row is class c.
-inline unsigned long long scan_op(unsigned long long c, unsigned long long x)
-{
-    const unsigned long long m = 0ULL - (unsigned long long)((c >> 32) > (x >> 32));
-    return (c & m) | (x & ~m);
-}
-// red[c] = op(red[c], key[r g + c]) over `rows` rows
-__attribute__((target("avx2"))) void scan_reduce_avx2(unsigned long long *red, const unsigned long long *key,
-                                                       long long rows, int g)
-{
-    int c = 0;
-    for (; c + 4 <= g; c += 4) {
-        __m256i r = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(red + c));
-        const unsigned long long *k = key + c;
-        for (long long i = 0; i < rows; ++i, k += g) {
-            const __m256i x = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(k));
-            const __m256i m = _mm256_cmpgt_epi64(_mm256_srli_epi64(r, 32), _mm256_srli_epi64(x, 32));
-            r = _mm256_blendv_epi8(x, r, m);
-        }
-        _mm256_storeu_si256(reinterpret_cast<__m256i *>(red + c), r);
-    }
-    for (; c < g; ++c) {
-        unsigned long long r = red[c];
-        const unsigned long long *k = key + c;
-        for (long long i = 0; i < rows; ++i, k += g) r = scan_op(r, *k);
-        red[c] = r;
-    }
-}
-// car[c] = op(car[c], key[r g + c]) = c_k; out[r g + c] = the smaller-score of
-// c_k and key[(r + 1) g + c] (c_k on ties) -- `rows` rows, each with its
-// next row present; returns nonzero when some position took the next entry
-__attribute__((target("avx2"))) unsigned long long scan_rows_avx2(unsigned long long *car,
-                                                                   const unsigned long long *key,
-                                                                   unsigned long long *out, long long rows, int g)
-{
-    unsigned long long any = 0;
-    int c = 0;
-    __m256i anyv = _mm256_setzero_si256();
-    for (; c + 4 <= g; c += 4) {
-        __m256i cv = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(car + c));
-        const unsigned long long *k = key + c;
-        unsigned long long *o = out + c;
-        for (long long i = 0; i < rows; ++i, k += g, o += g) {
-            const __m256i x = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(k));
-            const __m256i nx = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(k + g));
-            const __m256i m0 = _mm256_cmpgt_epi64(_mm256_srli_epi64(cv, 32), _mm256_srli_epi64(x, 32));
-            cv = _mm256_blendv_epi8(x, cv, m0);
-            const __m256i m = _mm256_cmpgt_epi64(_mm256_srli_epi64(cv, 32), _mm256_srli_epi64(nx, 32));
-            _mm256_storeu_si256(reinterpret_cast<__m256i *>(o), _mm256_blendv_epi8(cv, nx, m));
-            anyv = _mm256_or_si256(anyv, m);
-        }
-        _mm256_storeu_si256(reinterpret_cast<__m256i *>(car + c), cv);
-    }
-    any = (unsigned long long)_mm256_movemask_epi8(anyv);
-    for (; c < g; ++c) {
-        unsigned long long cc = car[c];
-        const unsigned long long *k = key + c;
-        unsigned long long *o = out + c;
-        for (long long i = 0; i < rows; ++i, k += g, o += g) {
-            cc = scan_op(cc, *k);
-            const unsigned long long nx = k[g];
-            const unsigned long long m = 0ULL - (unsigned long long)((cc >> 32) > (nx >> 32));
-            *o = (nx & m) | (cc & ~m);
-            any |= m;
-        }
-        car[c] = cc;
-    }
-    return any;
-}
-void scan_reduce_plain(unsigned long long *red, const unsigned long long *key, long long rows, int g)
-{
-    for (int c = 0; c < g; ++c) {
-        unsigned long long r = red[c];
-        const unsigned long long *k = key + c;
-        for (long long i = 0; i < rows; ++i, k += g) r = scan_op(r, *k);
-        red[c] = r;
-    }
-}
-unsigned long long scan_rows_plain(unsigned long long *car, const unsigned long long *key, unsigned long long *out,
-                                   long long rows, int g)
-{
-    unsigned long long any = 0;
-    for (int c = 0; c < g; ++c) {
-        unsigned long long cc = car[c];
-        const unsigned long long *k = key + c;
-        unsigned long long *o = out + c;
-        for (long long i = 0; i < rows; ++i, k += g, o += g) {
-            cc = scan_op(cc, *k);
-            const unsigned long long nx = k[g];
-            const unsigned long long m = 0ULL - (unsigned long long)((cc >> 32) > (nx >> 32));
-            *o = (nx & m) | (cc & ~m);
-            any |= m;
-        }
-        car[c] = cc;
-    }
-    return any;
-}
-void scan_reduce(unsigned long long *red, const unsigned long long *key, long long rows, int g)
-{
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    if (avx2 && g >= 4) scan_reduce_avx2(red, key, rows, g);
-    else scan_reduce_plain(red, key, rows, g);
-}
-unsigned long long scan_rows(unsigned long long *car, const unsigned long long *key, unsigned long long *out,
-                             long long rows, int g)
-{
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    return (avx2 && g >= 4) ? scan_rows_avx2(car, key, out, rows, g) : scan_rows_plain(car, key, out, rows, g);
-}
-}  // namespace
-
-// meshele[k] = the old meshele[src(k)]: a second element array copy-constructed
-// in parallel (no serial value-initialisation), then swapped in
-template <class Src>
-bool FSolver::permute_elements(Src src)
-{
-    BigVec<CMElement> out;
-    huge_reserve(out, (size_t)std::max(0, NumEls));
-    out.resize((size_t)std::max(0, NumEls));   // (NoInitAlloc: written below, in parallel)
-    par_for(NumEls, 1 << 16, [&](long long a, long long b) {
-        // (the sources are scattered: each 40-B record is a cache miss, so the
-        // one kPf ahead is requested while this one is copied)
-        constexpr long long kPf = 16;
-        for (long long k = a; k < b; k++) {
-            if (k + kPf < b) __builtin_prefetch(&meshele[src(k + kPf)], 0, 0);
-            ::new (&out[k]) CMElement(meshele[src(k)]);
-        }
-    });
-    meshele.swap(out);
-    static_assert(std::is_trivially_destructible<CMElement>::value, "uninitialised storage");
-    return true;
-}
-
-int FSolver::SortElements()
-{
-    // comb sort on p0+p1+p2 (cuthill.cpp:39-86); not stable, restated exactly:
-    // the same comparisons and swaps, on packed (score, element) keys instead
-    // of the element records, which are permuted once at the end.  With a
-    // GPU (the solve needs one anyway) every pass runs on the device
-    // (xfk_sort_elements: ~2 ms instead of ~45 on 16 host cores); without
-    // one, or with XFEMM_HOST_SORT set, on the host below.
-    LoadTrace tr;
-    join_hip_warmup();
-    if (NumEls > 1 && !std::getenv("XFEMM_HOST_SORT") && xfk_device_count() > 0) {
-        HugeBuf<unsigned> score;
-        HugeBuf<int> perm;
-        if (!score.allocate((size_t)NumEls) || !perm.allocate((size_t)NumEls)) return false;
-        par_for(NumEls, 1 << 16, [&](long long a, long long b) {
-            for (long long k = a; k < b; k++) {
-                const CMElement &e = meshele[k];
-                score[k] = (unsigned)((long long)e.p[0] + e.p[1] + e.p[2]);
-            }
-        });
-        if (xfk_sort_elements(NumEls, score.data(), device, perm.data()) != XFK_OK) {
-            warn(std::string("device element sort failed: ") + xfk_last_error() + "\n");
-            return false;
-        }
-        tr.mark("  device comb sort");
-        permute_elements([&](long long k) { return perm[k]; });
-        tr.mark("  permute");
-        return true;
-    }
-    std::vector<unsigned long long> key, tmp;
-    huge_reserve(key, (size_t)NumEls);
-    huge_reserve(tmp, (size_t)NumEls);
-    key.resize(NumEls);
-    par_for(NumEls, 1 << 16, [&](long long a, long long b) {
-        for (long long k = a; k < b; k++) {
-            const CMElement &e = meshele[k];
-            const unsigned long long sc = (unsigned long long)((long long)e.p[0] + e.p[1] + e.p[2]);
-            key[k] = (sc << 32) | (unsigned)k;
-        }
-    });
-    // A pass with gap g compares (j, j + g) for j ascending: the steps of one
-    // residue class j mod g touch only that class's entries, in ascending
-    // order, so classes are independent.  Wide passes split the classes over
-    // threads.  Narrow passes (few classes) use that a pass over one class is
-    // a bubble pass: the element carried to position k is the prefix
-    // "maximum" c_k = op(c_{k-1}, x_k), op(a, b) = score(a) > score(b) ? a : b
-    // (a swap happens exactly when the carried score exceeds the next one:
-    // ties keep their order), and position k receives
-    // score(c_k) > score(x_{k+1}) ? x_{k+1} : c_k -- an associative scan, so
-    // chunks of rows run in parallel from their classes' carries (computed
-    // from per-chunk reductions): out of place, the same result as the
-    // sequential pass
-    HostPool &pool = HostPool::get();
-    const int T = pool.size();
-    auto scan_pass = [&](int g) -> bool {
-        // chunks of whole rows (g positions each); every chunk but the last
-        // holds every class, so the carries need no presence flags
-        const long long n = NumEls;
-        const long long R = (n + g - 1) / g;
-        const int TT = (int)std::max<long long>(1, std::min<long long>(T, R / 64));
-        std::vector<long long> q0(TT + 1);
-        for (int t = 0; t <= TT; ++t) q0[t] = std::min(n, (R * t / TT) * g);
-        std::vector<unsigned long long> red((size_t)TT * g), cin((size_t)TT * g);
-        std::vector<char> sw(TT, 0);
-        auto run = [&](auto fn) { pool.run(TT, fn); };
-        run([&](int t) {   // per chunk and class: the op-reduction of its entries (from the identity 0)
-            if (t == TT - 1) return;   // (the last chunk feeds no carry; the others are whole rows)
-            unsigned long long *rd = red.data() + (size_t)t * g;
-            std::fill(rd, rd + g, 0ULL);
-            scan_reduce(rd, key.data() + q0[t], (q0[t + 1] - q0[t]) / g, g);
-        });
-        for (int t = 1; t < TT; ++t)   // carries into each chunk
-            for (int c = 0; c < g; ++c) {
-                const size_t i1 = (size_t)(t - 1) * g + c, i2 = (size_t)t * g + c;
-                cin[i2] = t == 1 ? red[i1] : scan_op(cin[i1], red[i1]);
-            }
-        tmp.resize(NumEls);
-        run([&](int t) {
-            const long long a = q0[t], e = q0[t + 1];
-            if (a >= e) return;
-            std::vector<unsigned long long> car(g, 0ULL);   // chunk 0: the identity
-            if (t > 0) std::copy(cin.begin() + (size_t)t * g, cin.begin() + (size_t)(t + 1) * g, car.begin());
-            // whole rows whose next row is complete, then position by position
-            const long long full = std::max(0LL, std::min((e - a) / g, (n - g - a) / g));
-            unsigned long long any = scan_rows(car.data(), key.data() + a, tmp.data() + a, full, g);
-            int c = 0;
-            long long q = a + full * g;
-            const long long lim = std::min(e, n - g);   // positions with a partner one gap on
-            for (; q < lim; ++q) {
-                const unsigned long long cc = scan_op(car[c], key[q]);   // c_k
-                car[c] = cc;
-                const unsigned long long nx = key[q + g];                 // x_{k+1}
-                const unsigned long long m = 0ULL - (unsigned long long)((cc >> 32) > (nx >> 32));
-                tmp[q] = (nx & m) | (cc & ~m);
-                any |= m;
-                if (++c == g) c = 0;
-            }
-            for (; q < e; ++q) {   // the last g positions: the carried entry lands
-                tmp[q] = scan_op(car[c], key[q]);
-                if (++c == g) c = 0;
-            }
-            sw[t] = any != 0;
-        });
-        key.swap(tmp);
-        bool any = false;
-        for (char c : sw) any |= c != 0;
-        return any;
-    };
-    int gap = NumEls, i = 0;
-    double ms_wide = 0, ms_narrow = 0;
-    int n_wide = 0, n_narrow = 0;
-    do {
-        const auto tp = std::chrono::steady_clock::now();
-        if (gap > 1) {
-            gap = (gap * 10) / 13;
-            if ((gap == 10) || (gap == 9)) gap = 11;
-        }
-        i = 0;
-        if (T > 1 && gap >= 8 * T && NumEls >= (1 << 16)) {
-            std::vector<char> sw(T, 0);
-            const int g = gap;
-            auto part = [&](int t) {
-                const int r0 = (int)((long long)g * t / T), r1 = (int)((long long)g * (t + 1) / T);
-                unsigned long long any = 0;
-                for (long long b = 0; b + g < NumEls; b += g) {
-                    // (the class range [r0, r1) of this block and its partners one gap on:
-                    // disjoint, so the compare-swaps are independent -- branch-free)
-                    const int re = (int)std::min<long long>(r1, NumEls - g - b);
-                    any |= comb_swap_run(key.data() + b + r0, key.data() + b + r0 + g, re - r0);
-                }
-                sw[t] = any != 0;
-            };
-            pool.run(T, part);
-            for (char c : sw) i |= c;
-        } else if (T > 1 && NumEls >= (1 << 16)) {   // (narrow passes: few classes)
-            i = scan_pass(gap) ? 1 : 0;
-        } else {
-            for (int j = 0; (j + gap) < NumEls; j++) {
-                if ((key[j] >> 32) > (key[j + gap] >> 32)) {
-                    std::swap(key[j], key[j + gap]);
-                    i = 1;
-                }
-            }
-        }
-        const double dt = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
-        if (T > 1 && gap >= 8 * T && NumEls >= (1 << 16)) ms_wide += dt, ++n_wide;
-        else ms_narrow += dt, ++n_narrow;
-    } while ((gap > 1) && (i > 0));
-    if (tr.on)
-        std::fprintf(stderr, "[load]   comb passes: %d wide %.1f ms, %d narrow %.1f ms\n", n_wide, ms_wide, n_narrow,
-                     ms_narrow);
-    tr.mark("  comb sort");
-    // the permutation applied through a second element array (permute_elements)
-    if (!permute_elements([&](long long k) { return (int)(key[k] & 0xffffffffu); })) return false;
-    tr.mark("  permute");
-    return true;
-}
+int FSolver::SortElements() { return sort_mesh_elements(meshele); }
 
 int FSolver::Cuthill(bool deleteFiles)
 {
-    // reverse-less Cuthill-McKee of cuthill.cpp:88-390, on the .edge connectivity
-    LoadTrace tr;
-    const int n_lines = (int)edges_.size();
-    BigVec<int> numcon, newnum, nxtnum;
-    par_assign(numcon, (size_t)NumNodes, 0);
-    par_assign(newnum, (size_t)NumNodes, -1);
-    par_assign(nxtnum, (size_t)NumNodes, -1);
-    // neighbour lists as CSR, each in the order the reference's lists get
-    // their entries (edge order).  Thread t takes the edges of its range and
-    // bins both ends by the node range that owns them (bucket (t, u)); owner u
-    // then reads its buckets in t order -- every list in edge order, as the
-    // sequential loop appends it -- counts, scans and fills its own nodes.
-    // The edge array is read twice in all (not once per thread).
-    BigVec<int> aptr, adj;
-    par_assign(aptr, (size_t)NumNodes + 1, 0);
-    huge_reserve(adj, 2 * edges_.size());
-    adj.resize(2 * edges_.size());   // (every slot written by the fill below)
-    {
-        const int T = (int)std::max<long long>(1, std::min<long long>(HostPool::get().size(), (long long)n_lines / 65536));
-        const int chunk = (int)std::max<long long>(1, ((long long)NumNodes + T - 1) / T);
-        auto lo = [&](int u) { return (int)std::min<long long>(NumNodes, (long long)chunk * u); };
-        auto elo = [&](int t) { return (long long)n_lines * t / T; };
-        std::vector<long long> bc((size_t)T * T + 1, 0);   // bucket (t, u) at t * T + u: ends counted, then offsets
-        par_for(T, 1, [&](long long t0, long long t1) {
-            for (long long t = t0; t < t1; ++t) {
-                long long *c = bc.data() + t * T;
-                for (long long i = elo((int)t); i < elo((int)t + 1); ++i) {
-                    c[edges_[i][0] / chunk]++;
-                    c[edges_[i][1] / chunk]++;
-                }
-            }
-        });
-        // layout: owner u's region holds its buckets t = 0 .. T-1 in order
-        std::vector<long long> off((size_t)T * T), ubase(T + 1, 0);
-        long long o = 0;
-        for (int u = 0; u < T; ++u) {
-            ubase[u] = o;
-            for (int t = 0; t < T; ++t) {
-                off[(size_t)t * T + u] = o;
-                o += bc[(size_t)t * T + u];
-            }
-        }
-        ubase[T] = o;
-        BigVec<std::array<int, 2>> ends;   // (owned end, other end)
-        huge_reserve(ends, (size_t)o);
-        ends.resize((size_t)o);
-        par_for(T, 1, [&](long long t0, long long t1) {
-            for (long long t = t0; t < t1; ++t) {
-                long long *w = off.data() + t * T;
-                for (long long i = elo((int)t); i < elo((int)t + 1); ++i) {
-                    const int e0 = edges_[i][0], e1 = edges_[i][1];
-                    ends[w[e0 / chunk]++] = {e0, e1};
-                    ends[w[e1 / chunk]++] = {e1, e0};
-                }
-            }
-        });
-        par_for(T, 1, [&](long long u0, long long u1) {
-            for (long long u = u0; u < u1; ++u) {
-                for (long long k = ubase[u]; k < ubase[u + 1]; ++k) numcon[ends[k][0]]++;
-                long long q = ubase[u];   // (= the ends owned by the ranges before u)
-                for (int v = lo((int)u); v < lo((int)u + 1); ++v) {
-                    aptr[v] = (int)q;
-                    q += numcon[v];
-                }
-                std::vector<int> cur(aptr.begin() + lo((int)u), aptr.begin() + lo((int)u + 1));
-                for (long long k = ubase[u]; k < ubase[u + 1]; ++k) adj[cur[ends[k][0] - lo((int)u)]++] = ends[k][1];
-            }
-        });
-        aptr[NumNodes] = (int)ubase[T];
-    }
-    if (deleteFiles) remove_async({PathName + ".edge"});
-    tr.mark("adjacency");
-    // bubble sort by increasing connectivity: swaps only on a strict decrease,
-    // so it is the stable sort of the list by numcon -- an insertion sort per
-    // list gives the same order; lists are independent
-    par_for(NumNodes, 1 << 14, [&](long long a, long long b) {
-        for (long long n0 = a; n0 < b; n0++) {
-            int *l = adj.data() + aptr[n0];
-            const int m = aptr[n0 + 1] - aptr[n0];
-            for (int q = 1; q < m; q++) {
-                const int v = l[q], kv = numcon[v];
-                int r = q;
-                for (; r > 0 && numcon[l[r - 1]] > kv; --r) l[r] = l[r - 1];
-                l[r] = v;
-            }
-        }
+    return cuthill_mesh(meshnode, meshele, deleteFiles, [&](const BigVec<int> &newnum) {
+        for (auto &g : agelist)   // cuthill.cpp:321-330
+            for (int &q : g.qn) q = newnum[q];
     });
-    tr.mark("neighbour sort");
-    long long j = numcon[0];
-    int n0 = 0;
-    for (long long i = 1; i < NumNodes; i++) {
-        if (numcon[i] < j) {
-            j = numcon[i];
-            n0 = (int)i;
-        }
-        if (j == 2) i = n_lines;
-    }
-    newnum[n0] = 0;
-    int n = 1;
-    nxtnum[0] = n0;
-    if (NumNodes > 1) {
-        do {
-            for (int t = aptr[n0]; t < aptr[n0 + 1]; ++t)
-                if (const int c = adj[t]; newnum[c] < 0) {
-                    newnum[c] = n;
-                    nxtnum[n] = c;
-                    n++;
-                }
-            const int nextpos = newnum[n0] + 1;
-            if (nextpos >= NumNodes || nxtnum[nextpos] < 0) {
-                if (n >= NumNodes) break;
-                for (int i = 0; i < NumNodes; i++)
-                    if (newnum[i] < 0) {
-                        j = numcon[i];
-                        n0 = i;
-                        break;
-                    }
-                for (int i = 0; i < NumNodes; i++) {
-                    if ((newnum[i] < 0) && (numcon[i] < j)) {
-                        j = numcon[i];
-                        n0 = i;
-                    }
-                    if (j == 2) break;
-                }
-                newnum[n0] = n;
-                nxtnum[n] = n0;
-                n++;
-            } else {
-                n0 = nxtnum[nextpos];
-            }
-        } while (n < NumNodes);
-    }
-    tr.mark("numbering");
-    for (auto &p : pbclist) {
-        p.x = newnum[p.x];
-        p.y = newnum[p.y];
-    }
-    for (auto &g : agelist)   // cuthill.cpp:321-330
-        for (int &q : g.qn) q = newnum[q];
-    int newwide = 0;
-    {
-        std::mutex mu;
-        par_for(NumNodes, 1 << 16, [&](long long a0, long long a1) {
-            int w = 0;
-            for (long long a = a0; a < a1; a++)
-                for (int t = aptr[a]; t < aptr[a + 1]; ++t) w = std::max(w, std::abs(newnum[a] - newnum[adj[t]]));
-            std::lock_guard<std::mutex> g(mu);
-            newwide = std::max(newwide, w);
-        });
-    }
-    BandWidth = newwide + 1;
-    par_for(NumEls, 1 << 16, [&](long long a, long long b) {
-        for (long long k = a; k < b; k++)
-            for (int q = 0; q < 3; q++) meshele[k].p[q] = newnum[meshele[k].p[q]];
-    });
-    // SortNodes (fsolver.cpp:1341-1353): node i moves to slot newnum[i]
-    BigVec<CNode> sorted;
-    huge_reserve(sorted, (size_t)NumNodes);
-    sorted.resize(NumNodes);   // (every slot written below: newnum is a permutation)
-    par_for(NumNodes, 1 << 16, [&](long long a, long long b) {
-        for (long long k = a; k < b; k++) ::new (&sorted[newnum[k]]) CNode(meshnode[k]);
-    });
-    meshnode.swap(sorted);
-    tr.mark("bandwidth + renumber");
-    SortElements();
-    tr.mark("SortElements");
-    return true;
 }
 
 void FSolver::GetFillFactor(int lbl)
@@ -1481,16 +616,6 @@ bool FSolver::make_desc(DescStore &ds)
     return true;
 }
 
-namespace {
-double ms_since(std::chrono::steady_clock::time_point &t)
-{
-    const auto n = std::chrono::steady_clock::now();
-    const double ms = std::chrono::duration<double, std::milli>(n - t).count();
-    t = n;
-    return ms;
-}
-}  // namespace
-
 int FSolver::Static2D()
 {
     join_hip_warmup();
@@ -1606,48 +731,6 @@ int FSolver::Harmonic2D()
     return rc == XFK_OK;
 }
 
-namespace {
-// "%.17g" and "%i" as printf writes them (std::to_chars: the same correctly
-// rounded digits and the same %g form), for the .ans's large sections
-inline char *put_g17(char *p, double v) { return fastnum::put_g17(p, v); }   // (exact: fastnum.h)
-inline char *put_i(char *p, int v) { return std::to_chars(p, p + 16, v).ptr; }
-// lines [0, n): line(i, buf) writes line i (at most max_line chars) and returns
-// its end; formatted in parallel chunks into huge-page buffers, then written
-// in order by fwrite (one write of ~10 GB/s on the box; a shared mapping of
-// the file was measured 5x slower, tools/lab/io_probe.cpp)
-int format_chunks(int n) { return (int)std::max(1, std::min<int>(HostPool::get().size(), n / 8192)); }
-template <class F>
-FSolver::Formatted format_lines(int n, int max_line, F line)
-{
-    const int T = format_chunks(n);
-    FSolver::Formatted f;
-    f.buf.resize(T);
-    f.len.assign(T, 0);
-    par_for(T, 1, [&](long long t0, long long t1) {
-        for (long long t = t0; t < t1; ++t) {
-            const int a = (int)((long long)n * t / T), b = (int)((long long)n * (t + 1) / T);
-            if (!f.buf[t].allocate((size_t)(b - a) * max_line + 1)) continue;   // (Formatted::ok() fails)
-            char *q = f.buf[t].data();
-            for (int i = a; i < b; ++i) q = line(i, q);
-            f.len[t] = (size_t)(q - f.buf[t].data());
-        }
-    });
-    return f;
-}
-bool write_formatted(FILE *fp, const FSolver::Formatted &f)
-{
-    if (!f.ok()) return false;   // (a chunk's buffer could not be allocated)
-    for (size_t t = 0; t < f.buf.size(); ++t)
-        if (f.len[t]) fwrite(f.buf[t].data(), 1, f.len[t], fp);
-    return true;
-}
-template <class F>
-bool write_lines(FILE *fp, int n, int max_line, F line)
-{
-    return write_formatted(fp, format_lines(n, max_line, line));
-}
-}  // namespace
-
 FSolver::Formatted FSolver::format_static_elements() const
 {
     return format_lines(NumEls, 64, [&](int i, char *q) {
@@ -1688,24 +771,6 @@ FSolver::NodeParts FSolver::format_static_node_parts() const
         return q;
     });
     return np;
-}
-
-// an existing .ans is moved aside and unlinked beside the write (truncating
-// ~130 MB of page cache in fopen costs ~7 ms); the new file is written whole.
-// A symlinked or hard-linked .ans keeps the reference's fopen("wt") behaviour
-// (truncated in place: the link target, inode and permissions stay); the
-// aside name is unique (mkstemp in the same directory, replaced by rename).
-void FSolver::clear_old_output(const std::string &path)
-{
-    struct stat st;
-    if (::lstat(path.c_str(), &st) != 0 || !S_ISREG(st.st_mode) || st.st_nlink > 1 || st.st_size < (1 << 20))
-        return;
-    std::string aside = path + ".xfemm-old-XXXXXX";
-    const int fd = ::mkstemp(&aside[0]);
-    if (fd < 0) return;
-    ::close(fd);
-    if (::rename(path.c_str(), aside.c_str()) == 0) remove_async({aside});
-    else ::unlink(aside.c_str());
 }
 
 int FSolver::WriteStatic2D()
@@ -1988,3 +1053,4 @@ bool FSolver::runSolver(bool verbose)
 }
 
 }  // namespace xfemm
+

@@ -17,15 +17,14 @@
 #include "../../../include/xfemm_kernels.h"
 #include "femm_problem.h"
 #include "hostmem.h"
+#include "meshhost.h"
 
 namespace xfemm {
 
-enum LoadMeshErr { NOERROR, BADFEMFILE, BADNODEFILE, BADPBCFILE, BADELEMENTFILE, BADEDGEFILE, MISSINGMATPROPS,
-                   ELMLABELTOOBIG, UNSUPPORTEDMESH };
-
-int PrintWarningMsg(const char *fmt, ...);
-
-class FSolver : public FemmProblemData {
+// (LoadMeshErr, the message hooks, PathName, the mesh counts, pbclist, device,
+// deleteMeshFiles, stats, ms_phase and lastError: MeshHost, shared with the
+// potential solvers)
+class FSolver : public FemmProblemData, public MeshHost {
 public:
     FSolver();
     ~FSolver();
@@ -33,12 +32,10 @@ public:
     FSolver &operator=(const FSolver &) = delete;
 
     // General problem attributes (fsolver.h / feasolver.h)
-    std::string PathName;
     double Relax = 0.0;
-    int NumNodes = 0, NumEls = 0, BandWidth = 0, NumPBCs = 0, NumAirGapElems = 0, NumCircPropsOrig = 0;
+    int NumAirGapElems = 0, NumCircPropsOrig = 0;
     BigVec<CNode> meshnode;      // (parallel first touch: hostmem.h)
     BigVec<CMElement> meshele;
-    std::vector<CCommonPoint> pbclist;
     // CAirGapElement as read from the .pbc file (fsolver.cpp:425-515)
     struct AirGap {
         std::string name;
@@ -50,12 +47,6 @@ public:
     };
     std::vector<AirGap> agelist;
 
-    int (*WarnMessage)(const char *, ...);
-    int (*PrintMessage)(const char *, ...);
-
-    // GPU selection and file handling
-    int device = 0;
-    bool deleteMeshFiles = true;
     // sharded solve over comm's ranks (xfk_problem_create_dist): every rank
     // runs its own FSolver on the same files; rank 0 writes the .ans and
     // deletes the mesh files.  nullptr: one device.
@@ -75,19 +66,6 @@ public:
     void WriteAirGapElements(FILE *fp) const;            // static2d.cpp:1161-1190, harmonic2d.cpp:1002-1030
     void GetFillFactor(int lbl);                         // fsolver.cpp:1083-1193 (incl. ProximityMu)
     static std::string getErrorString(LoadMeshErr err);
-    void join_removals();   // wait for the mesh-file deletions LoadMesh / Cuthill started
-    // .ans text formatted in parallel chunks (fsolver.cpp: format_lines)
-    struct Formatted {
-        std::vector<HugeBuf<char>> buf;
-        std::vector<size_t> len;
-        // every chunk's buffer was allocated (a failed chunk is left empty)
-        bool ok() const
-        {
-            for (const auto &b : buf)
-                if (!b.data()) return false;
-            return true;
-        }
-    };
 
     // result of the last Static2D: A (= V*c) per node, in meshnode order;
     // Harmonic2D: A holds the real parts and A_im the imaginary parts
@@ -96,27 +74,9 @@ public:
     // (PrevType != 0), and whether the mesh came from it (fsolver.h:149)
     std::vector<double> Aprev;
     bool meshLoadedFromPrevSolution = false;
-    xfk_result stats{};
-    // wall milliseconds of the last runSolver: LoadMesh, Cuthill, problem
-    // creation (descriptor + host -> HBM upload), solve (device + solution
-    // read-back), write (.ans)
-    double ms_phase[5] = {};
-    std::string lastError;
 
 private:
-    BigVec<std::array<int, 3>> edges_;        // .edge content: n0, n1, marker
-    std::vector<std::thread> removers_;       // mesh-file deletions in flight (joined by runSolver)
-    void remove_async(std::vector<std::string> paths);
-    template <class Src>
-    bool permute_elements(Src src);
     std::thread ele_fmt_;                     // the .ans element section, formatted beside the solve
-    // HIP runtime / device / code-object bring-up (xfk_device_init) started by
-    // LoadProblemFile on a thread of its own, so a fresh process pays it beside
-    // LoadMesh and Cuthill instead of inside the first device call; joined
-    // before the first device use (SortElements, Static2D, Harmonic2D)
-    std::thread hip_warm_;
-    void start_hip_warmup();
-    void join_hip_warmup();
     Formatted ele_text_;
     Formatted format_static_elements() const;
     // the .ans node lines without A (x, y before it; the marker and the
@@ -129,9 +89,7 @@ private:
     };
     NodeParts node_parts_;
     NodeParts format_static_node_parts() const;
-    void clear_old_output(const std::string &path);
     void remove_mesh_files_after_collective_solve();
-    void warn(const std::string &msg);
     struct DescStore;                         // property tables + mesh arrays behind an xfk_problem_desc
     bool make_desc(DescStore &ds);
 };

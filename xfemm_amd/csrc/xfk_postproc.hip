@@ -1883,6 +1883,15 @@ int xfk_pot_get_mask(xfk_problem *P, double *W, double *msk)
     });
 }
 
+int xfk_pot_get_qmarks(xfk_problem *P, int *Q)
+{
+    return pp_entry(P, false, [&]() -> int {
+        XFK_REQUIRE(Q, XFK_ERR_ARG, "null output");
+        std::copy(P->pot_qmark.begin(), P->pot_qmark.end(), Q);
+        return XFK_OK;
+    });
+}
+
 int xfk_pot_mask_info(xfk_problem *P, double *out9)
 {
     return pp_entry(P, false, [&]() -> int {

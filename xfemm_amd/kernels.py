@@ -60,7 +60,7 @@ EXPORTED = (
     "xfk_problem_create_electrostatic", "xfk_electrostatic", "xfk_get_conductors", "xfk_conductor_charge",
     "xfk_problem_create_heatflow", "xfk_heatflow", "xfk_heatflow_assemble", "xfk_heatflow_set_step",
     "xfk_heatflow_advance", "xfk_hf_get_conductors", "xfk_hf_conductor_flow",
-    "xfk_pot_set_solution", "xfk_pot_element_fields", "xfk_pot_corner_fields", "xfk_pot_corner_branches",
+    "xfk_pot_set_solution", "xfk_pot_get_qmarks", "xfk_pot_element_fields", "xfk_pot_corner_fields", "xfk_pot_corner_branches",
     "xfk_pot_block_integrals", "xfk_pot_block_integral", "xfk_pot_point_values", "xfk_pot_grid_info", "xfk_pot_time",
     "xfk_pot_make_mask", "xfk_pot_get_mask", "xfk_pot_mask_info", "xfk_pot_mask_problem", "xfk_pot_stress_time",
     "xfk_pot_line_integrals", "xfk_pot_line_integral", "xfk_pot_contour_samples", "xfk_pot_contour_time",
@@ -320,6 +320,7 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_hf_conductor_flow.argtypes = [C.c_void_p, C.c_int, dptr]
     ubptr = C.POINTER(C.c_ubyte)
     L.xfk_pot_set_solution.argtypes = [C.c_void_p, dptr]
+    L.xfk_pot_get_qmarks.argtypes = [C.c_void_p, iptr]
     L.xfk_pot_element_fields.argtypes = [C.c_void_p, dptr, dptr]
     L.xfk_pot_corner_fields.argtypes = [C.c_void_p, dptr]
     L.xfk_pot_corner_branches.argtypes = [C.c_void_p, ubptr]

@@ -613,3 +613,131 @@ def age_motor(n_theta: int = 48, n_r: int = 4, half: bool = False, rotor_angle: 
     return dict(x=x, y=y, p=p, lbl=np.array(lbl, np.int32), e=np.array(e, np.int32), marker=None, pbc=pbc,
                 blocks=blocks, labels=labels, lines=[dict(format=0)], points=[], circuits=[], precision=precision,
                 length_units=2, coords=0, relax=1.0, ages=[age])
+
+
+# ---- the potential solvers' files (ESolver / HSolver) ---------------------------
+
+UNIT_WORDS = ("inches", "millimeters", "centimeters", "meters", "mils", "microns")
+
+
+def potential_text(kind: str, kw: dict) -> str:
+    """A .fee (kind "e") or .feh (kind "h") header from the keyword dictionary
+    of kernels.ElectrostaticProblem / HeatFlowProblem (no geometry: meshes are
+    given).  Labels may carry is_default; heat flow: dt and prev_soln."""
+    heat = kind == "h"
+    g = "%.17g"
+    out = ["[Format]      =  1", "[Precision]   =  " + g % kw.get("precision", 1e-8), "[MinAngle]    =  30",
+           "[Depth]       =  " + g % kw.get("depth", 1.0),
+           "[LengthUnits] =  %s" % UNIT_WORDS[kw.get("length_units", 0)],
+           "[ProblemType] =  %s" % ("axisymmetric" if kw.get("problem_type", 0) == 1 else "planar"),
+           "[Coordinates] =  cartesian"]
+    if kw.get("ext_ro", 0.0) or kw.get("ext_ri", 0.0) or kw.get("ext_zo", 0.0):
+        out += ["[extZo] = " + g % kw.get("ext_zo", 0.0), "[extRo] = " + g % kw.get("ext_ro", 0.0),
+                "[extRi] = " + g % kw.get("ext_ri", 0.0)]
+    if heat:
+        out += ['[PrevSoln] = "%s"' % kw.get("prev_soln", ""), "[dT] = " + g % kw.get("dt", 0.0)]
+    out.append('[Comment]     =  "synthetic"')
+    points = kw.get("points", ())
+    out.append("[PointProps]   = %d" % len(points))
+    for k, q in enumerate(points):
+        out += ["  <BeginPoint>", '    <PointName> = "p%d"' % k,
+                ("    <Tp> = " if heat else "    <Vp> = ") + g % q.get("T" if heat else "V", 0.0),
+                "    <qp> = " + g % q.get("qp", 0.0), "  <EndPoint>"]
+    lines = kw.get("lines", ())
+    out.append("[BdryProps]   = %d" % len(lines))
+    for k, ln in enumerate(lines):
+        out += ["  <BeginBdry>", '    <BdryName> = "b%d"' % k, "    <BdryType> = %d" % ln.get("format", 0)]
+        if heat:
+            out += ["    <Tset> = " + g % ln.get("Tset", 0.0), "    <qs>   = " + g % ln.get("qs", 0.0),
+                    "    <beta> = " + g % ln.get("beta", 0.0), "    <h>    = " + g % ln.get("h", 0.0),
+                    "    <Tinf> = " + g % ln.get("Tinf", 0.0)]
+        else:
+            out += ["    <Vs> = " + g % ln.get("V", 0.0), "    <qs> = " + g % ln.get("qs", 0.0),
+                    "    <c0> = " + g % ln.get("c0", 0.0), "    <c1> = " + g % ln.get("c1", 0.0)]
+        out.append("  <EndBdry>")
+    blocks = kw["blocks"]
+    out.append("[BlockProps]  = %d" % len(blocks))
+    for k, b in enumerate(blocks):
+        out += ["  <BeginBlock>", '    <BlockName> = "m%d"' % k]
+        if heat:
+            out += ["    <Kx> = " + g % b.get("kx", 1.0), "    <Ky> = " + g % b.get("ky", 1.0),
+                    "    <Kt> = " + g % b.get("kt", 0.0), "    <qv> = " + g % b.get("qv", 0.0)]
+            T = b.get("T")
+            if T is not None and len(T):
+                out.append("    <TKPoints> = %d" % len(T))
+                out += ["      " + g % t + "\t" + g % kk for t, kk in zip(T, b["K"])]
+        else:
+            out += ["    <ex> = " + g % b.get("ex", 1.0), "    <ey> = " + g % b.get("ey", 1.0),
+                    "    <qv> = " + g % b.get("qv", 0.0)]
+        out.append("  <EndBlock>")
+    conductors = kw.get("conductors", ())
+    out.append("[ConductorProps]  = %d" % len(conductors))
+    for k, c in enumerate(conductors):
+        out += ["  <BeginConductor>", '    <ConductorName> = "c%d"' % k,
+                ("    <Tc> = " if heat else "    <Vc> = ") + g % c.get("T" if heat else "V", 0.0),
+                "    <qc> = " + g % c.get("q", 0.0), "    <ConductorType> = %d" % c.get("type", 1),
+                "  <EndConductor>"]
+    out += ["[NumPoints] = 0", "[NumSegments] = 0", "[NumArcSegments] = 0", "[NumHoles] = 0",
+            "[NumBlockLabels] = %d" % len(kw["labels"])]
+    for lb in kw["labels"]:
+        out.append("0\t0\t%d\t-1\t0\t%d" % (lb["block"] + 1,
+                                          int(lb.get("is_external", 0)) | (2 if lb.get("is_default") else 0)))
+    return "\n".join(out) + "\n"
+
+
+def side_edge_marks(p, e, conductor_of_prop=None) -> list:
+    """(n0, n1, property, conductor) for every element side carrying a boundary
+    property in e, one per node pair (the last side in element order wins)."""
+    p = np.asarray(p).reshape(-1, 3)
+    e = np.asarray(e).reshape(-1, 3)
+    marks = {}
+    for i, j in zip(*np.nonzero(e >= 0)):
+        a, b = int(p[i, j]), int(p[i, (j + 1) % 3])
+        prop = int(e[i, j])
+        marks[(min(a, b), max(a, b))] = (a, b, prop, -1 if conductor_of_prop is None else conductor_of_prop.get(prop, -1))
+    return list(marks.values())
+
+
+def write_potential_mesh(base: str, x, y, p, lbl, marker=None, conductor=None, edge_marks=(), pbc=None) -> None:
+    """Write <base>.node/.ele/.edge/.pbc with the marker encoding of the
+    potential solvers' mesher output (esolver.cpp:155-167, 311-319): a node
+    marker is (conductor + 1) * 0x10000 + (point property + 2), 0 when the node
+    has neither; an edge marker the negated same of (conductor, boundary
+    property).  x, y in the problem's length units; lbl 0-based (-1: no label,
+    written as 0).  Every element edge is written once, sorted by its node
+    pair (the renumbering reads the mesh's connectivity from this file);
+    edge_marks: (n0, n1, property, conductor) for the marked ones, written as
+    n0 n1 in that orientation."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    p = np.asarray(p).reshape(-1, 3)
+    lbl = np.asarray(lbl)
+    n = len(x)
+    mk = -np.ones(n, np.int64) if marker is None else np.asarray(marker, np.int64)
+    cd = -np.ones(n, np.int64) if conductor is None else np.asarray(conductor, np.int64)
+    code = np.where((mk < 0) & (cd < 0), 0, (cd + 1) * 0x10000 + np.where(mk >= 0, mk + 2, 0))
+    with open(base + ".node", "w") as fh:
+        fh.write("%d\t2\t0\t1\n" % n)
+        fh.write("".join("%d\t%.17g\t%.17g\t%d\n" % t for t in zip(range(n), x.tolist(), y.tolist(), code.tolist())))
+    with open(base + ".ele", "w") as fh:
+        fh.write("%d\t3\t1\n" % len(p))
+        fh.write("".join("%d\t%d\t%d\t%d\t%d\n" % t for t in zip(range(len(p)), p[:, 0].tolist(), p[:, 1].tolist(),
+                                                                    p[:, 2].tolist(), (lbl + 1).tolist())))
+    a = p.reshape(-1).astype(np.int64)
+    b = p[:, [1, 2, 0]].reshape(-1).astype(np.int64)
+    pairs = np.unique(np.stack([np.minimum(a, b), np.maximum(a, b)], axis=1), axis=0)
+    marked = {}
+    for n0, n1, prop, cond in edge_marks:
+        marked[(min(n0, n1), max(n0, n1))] = (int(n0), int(n1), -((int(cond) + 1) * 0x10000 + (int(prop) + 2 if prop >= 0 else 0)))
+    with open(base + ".edge", "w") as fh:
+        fh.write("%d\t1\n" % len(pairs))
+        rows = []
+        for k, (lo, hi) in enumerate(pairs.tolist()):
+            n0, n1, m = marked.get((lo, hi), (lo, hi, 0))
+            rows.append("%d\t%d\t%d\t%d\n" % (k, n0, n1, m))
+        fh.write("".join(rows))
+    pbc = np.zeros((0, 3), np.int32) if pbc is None else np.asarray(pbc).reshape(-1, 3)
+    with open(base + ".pbc", "w") as fh:
+        fh.write("%d\n" % len(pbc))
+        for k, (u, v, t) in enumerate(pbc.tolist()):
+            fh.write("%d\t%d\t%d\t%d\n" % (k, u, v, t))
