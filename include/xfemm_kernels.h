@@ -674,6 +674,22 @@ int xfk_pot_set_solution(xfk_problem *prob, const double *V);
  * Derived from the descriptor at creation (the post-processor's smoothing
  * reads the same marks); no solution needed.  Host data: no device work. */
 int xfk_pot_get_qmarks(xfk_problem *prob, int *Q);
+/* The marks of a solution file (n_nodes ints: the Q column of a .res / .anh)
+ * in place of the descriptor rule xfk_pot_get_qmarks restates; call it before
+ * xfk_pot_set_solution.  XFK_ERR_ARG on a mark that is neither -2, -1 nor a
+ * conductor's index.  A problem marked this way was opened from a file, which
+ * holds no boundary conditions: xfk_electrostatic, xfk_heatflow and
+ * xfk_heatflow_assemble return XFK_ERR_UNSUPPORTED on it from then on. */
+int xfk_pot_set_qmarks(xfk_problem *prob, const int *Q);
+/* d_PlotBounds of the reference's OpenDocument (epproc.cpp:184-225, and its
+ * twin in hpproc.cpp): out6 = min, max of the potential over the nodes, of
+ * |D| (|F|) and of |E| (|G|) over the elements whose label is not external.
+ * The reference's starting values are kept: |D| starts from the element whose
+ * index is the number of external elements (element 0 when every element is
+ * external, where the reference reads past its list), |E| from element 0,
+ * external or not.  One fixed-order min / max reduction without atomics: two
+ * runs give equal bits. */
+int xfk_pot_plot_bounds(xfk_problem *prob, double *out6);
 /* Per element D (C/m^2) and E (V/m), or F (W/m^2) and G (K/m): x and y
  * components interleaved, 2 n_elems each.  Either may be NULL. */
 int xfk_pot_element_fields(xfk_problem *prob, double *D, double *E);
@@ -698,6 +714,12 @@ int xfk_pot_corner_fields(xfk_problem *prob, double *d);
  * problem. */
 int xfk_pot_block_integrals(xfk_problem *prob, const unsigned char *label_selected, double *out7);
 int xfk_pot_block_integral(xfk_problem *prob, const unsigned char *label_selected, int type, double *out2);
+/* xfk_pot_block_integrals with the sums taken in the reference's order,
+ * element by element with one rounding per selected element, instead of the
+ * fixed tree: the value the reference's own loop leaves, so that a sum on a
+ * tie of its "%f" prints as the reference prints it.  One workgroup walks the
+ * elements (about 3 ns each); the file-based post-processors use it. */
+int xfk_pot_block_integrals_ordered(xfk_problem *prob, const unsigned char *label_selected, double *out7);
 /* The mask of the weighted stress tensor integrals (the reference's
  * PostProcessor::makeMask) for the selected labels (one byte per block label),
  * electrostatic problems only: a Laplace problem of its own on the mesh's
@@ -723,6 +745,12 @@ int xfk_pot_get_mask(xfk_problem *prob, double *W, double *msk);
  * corner values instead of taking the element's D (F). */
 int xfk_pot_point_values(xfk_problem *prob, int n, const double *x, const double *y, int smooth, int *elem,
                          double *out);
+/* The same values with the element of every point given (elem[i] in
+ * [0, n_elems), or -1: NaN), without the search: for a caller that locates
+ * points itself, as the file-based post-processors do with the reference's
+ * own walk from the element found last. */
+int xfk_pot_point_values_at(xfk_problem *prob, int n, const double *x, const double *y, const int *elem, int smooth,
+                            double *out);
 /* Contour (line) integrals, the reference's lineIntegral, for a batch of
  * contours: contour c is the polyline through the vertices ptr[c] .. ptr[c+1]
  * of (x, y), in the problem's length units; ptr has n_contours + 1 entries.

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cctype>
 #include <cmath>
+#include <cstring>
 #include <fstream>
 #include <sstream>
 #include <stdexcept>
@@ -719,6 +720,57 @@ bool ParseFemFile(const std::string &path, FemmProblemData &pr, std::string &err
     return true;
 }
 
+namespace {
+// one geometry line of a .fee / .feh: its numbers, as many as it has
+void geometry_line(const std::string &tok, const std::string &line, PotGeometry &g)
+{
+    std::istringstream is(line);
+    double v[8];
+    int n = 0;
+    while (n < 8 && (is >> v[n])) ++n;
+    auto at = [&](int k, double dflt) { return k < n ? v[k] : dflt; };
+    if (tok == "[numpoints]") {
+        PotGeometry::Point p;
+        p.x = at(0, 0);
+        p.y = at(1, 0);
+        p.prop = (int)at(2, 0) - 1;
+        p.group = (int)at(3, 0);
+        p.cond = (int)at(4, 0) - 1;
+        g.points.push_back(p);
+    } else if (tok == "[numsegments]") {
+        PotGeometry::Segment s;
+        s.n0 = (int)at(0, 0);
+        s.n1 = (int)at(1, 0);
+        s.MaxSideLength = at(2, -1);
+        s.prop = (int)at(3, 0) - 1;
+        s.hidden = (int)at(4, 0);
+        s.group = (int)at(5, 0);
+        s.cond = (int)at(6, 0) - 1;
+        g.segments.push_back(s);
+    } else if (tok == "[numarcsegments]") {
+        PotGeometry::Arc a;
+        a.n0 = (int)at(0, 0);
+        a.n1 = (int)at(1, 0);
+        a.ArcLength = at(2, 90);
+        a.MaxSideLength = at(3, 10);
+        a.prop = (int)at(4, 0) - 1;
+        a.hidden = (int)at(5, 0);
+        a.group = (int)at(6, 0);
+        a.cond = (int)at(7, 0) - 1;
+        g.arcs.push_back(a);
+    } else {
+        PotGeometry::Hole h;
+        h.x = at(0, 0);
+        h.y = at(1, 0);
+        h.group = (int)at(2, 0);
+        g.holes.push_back(h);
+    }
+}
+
+bool parse_potential_lines(LineReader &in, const std::string &path, PotentialKind kind, PotProblemData &pr,
+                           PotGeometry *geom, std::string &err);
+}  // namespace
+
 bool ParsePotentialFile(const std::string &path, PotentialKind kind, PotProblemData &pr, std::string &err)
 {
     const bool heat = kind == POT_HEATFLOW;
@@ -730,19 +782,45 @@ bool ParsePotentialFile(const std::string &path, PotentialKind kind, PotProblemD
     LineReader in;
     std::string line;
     while (std::getline(f, line)) in.lines.push_back(line);
+    return parse_potential_lines(in, path, kind, pr, nullptr, err);
+}
+
+bool ParsePotentialText(const char *text, size_t len, const std::string &path, PotentialKind kind, PotProblemData &pr,
+                        PotGeometry *geom, std::string &err)
+{
+    LineReader in;
+    const char *p = text, *const end = text + len;
+    while (p < end) {
+        const char *nl = static_cast<const char *>(std::memchr(p, '\n', (size_t)(end - p)));
+        const char *le = nl ? nl : end;
+        in.lines.emplace_back(p, (size_t)(le - p));
+        p = nl ? nl + 1 : end;
+    }
+    return parse_potential_lines(in, path, kind, pr, geom, err);
+}
+
+namespace {
+bool parse_potential_lines(LineReader &in, const std::string &path, PotentialKind kind, PotProblemData &pr,
+                           PotGeometry *geom, std::string &err)
+{
+    const bool heat = kind == POT_HEATFLOW;
     pr = PotProblemData();
+    if (geom) *geom = PotGeometry();
     while (in.good()) {
         std::string ln = trim(in.next());
         if (ln.empty()) continue;
         std::string tok = first_token(ln), rest;
-        // the geometry matters for the block labels only
+        // the geometry matters to the solvers for the block labels only
         if (tok == "[numpoints]" || tok == "[numsegments]" || tok == "[numarcsegments]" || tok == "[numholes]") {
             int n = 0;
             if (!rest_after_eq(ln, rest) || !parse_int(rest, n)) {
                 err = "bad count: " + ln;
                 return false;
             }
-            for (int k = 0; k < n && in.good(); ++k) in.next();
+            for (int k = 0; k < n && in.good(); ++k) {
+                const std::string gl = in.next();
+                if (geom) geometry_line(tok, gl, *geom);
+            }
             continue;
         }
         if (!rest_after_eq(ln, rest)) {
@@ -899,5 +977,6 @@ bool ParsePotentialFile(const std::string &path, PotentialKind kind, PotProblemD
         }
     return true;
 }
+}  // namespace
 
 }  // namespace xfemm

@@ -88,8 +88,43 @@ struct PotProblemData {
     std::vector<CPBlockLabel> labellist;
 };
 
+// The input geometry of a .fee / .feh, which the solvers skip and the
+// post-processors keep (contours along input segments and arcs): the lines
+// under [NumPoints], [NumSegments], [NumArcSegments] and [NumHoles].  Indices
+// are 0-based; `prop` is the file's 1-based property number less one (-1:
+// none), `cond` likewise.
+struct PotGeometry {
+    struct Point {
+        double x = 0, y = 0;
+        int prop = -1, group = 0, cond = -1;
+    };
+    struct Segment {
+        int n0 = 0, n1 = 0;
+        double MaxSideLength = -1;
+        int prop = -1, hidden = 0, group = 0, cond = -1;
+    };
+    struct Arc {
+        int n0 = 0, n1 = 0;
+        double ArcLength = 90, MaxSideLength = 10;   // degrees
+        int prop = -1, hidden = 0, group = 0, cond = -1;
+    };
+    struct Hole {
+        double x = 0, y = 0;
+        int group = 0;
+    };
+    std::vector<Point> points;
+    std::vector<Segment> segments;
+    std::vector<Arc> arcs;
+    std::vector<Hole> holes;
+};
+
 // FEASolver::LoadProblemFile on a .fee / .feh: returns false and fills `err`
 // on a parse error.
 bool ParsePotentialFile(const std::string &path, PotentialKind kind, PotProblemData &out, std::string &err);
+// The same on text already in memory (the header a .res / .anh echoes before
+// its [Solution]); `path` only names the file in messages.  geom (may be
+// null) receives the geometry lists.
+bool ParsePotentialText(const char *text, size_t len, const std::string &path, PotentialKind kind, PotProblemData &out,
+                        PotGeometry *geom, std::string &err);
 
 }  // namespace xfemm

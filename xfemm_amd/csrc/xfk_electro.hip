@@ -212,6 +212,8 @@ int xfk_problem_create_electrostatic(const xfk_es_problem_desc *d, int device, x
 int xfk_electrostatic(xfk_problem *P, int flags, xfk_result *res)
 {
     XFK_REQUIRE(P && P->electro, XFK_ERR_ARG, "not an electrostatic problem (xfk_problem_create_electrostatic)");
+    XFK_REQUIRE(!P->pot_from_file, XFK_ERR_UNSUPPORTED,
+                "the problem was opened from a solution file: it carries no boundary conditions to solve with");
     ArenaScope arena_scope(&P->arena);
     P->pot_solved = false;
     pp_invalidate(P);

@@ -447,6 +447,8 @@ int xfk_problem_create_heatflow(const xfk_hf_problem_desc *d, int device, xfk_pr
 int xfk_heatflow(xfk_problem *P, int flags, xfk_result *res)
 {
     XFK_REQUIRE(P && P->heat, XFK_ERR_ARG, "not a heat-flow problem (xfk_problem_create_heatflow)");
+    XFK_REQUIRE(!P->pot_from_file, XFK_ERR_UNSUPPORTED,
+                "the problem was opened from a solution file: it carries no boundary conditions to solve with");
     ArenaScope arena_scope(&P->arena);
     P->pot_solved = false;
     pp_invalidate(P);
@@ -466,6 +468,8 @@ int xfk_heatflow(xfk_problem *P, int flags, xfk_result *res)
 int xfk_heatflow_assemble(xfk_problem *P, const double *T)
 {
     XFK_REQUIRE(P && P->heat, XFK_ERR_ARG, "not a heat-flow problem (xfk_problem_create_heatflow)");
+    XFK_REQUIRE(!P->pot_from_file, XFK_ERR_UNSUPPORTED,
+                "the problem was opened from a solution file: it carries no boundary conditions to solve with");
     ArenaScope arena_scope(&P->arena);
     XFK_CHECK(hipSetDevice(P->device));
     hipStream_t s = P->stream;

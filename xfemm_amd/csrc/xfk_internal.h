@@ -603,6 +603,7 @@ struct xfk_problem {
     // mesh tables are built at the first post-processing call and kept; the
     // fields follow the solution (pp_invalidate: a new solve, xfk_pot_set_solution)
     std::vector<int> pot_qmark;                  // host, N: the reference's L.Q (-2 free, -1 fixed, else the conductor)
+    bool pot_from_file = false;                  // the marks came from a solution file (xfk_pot_set_qmarks): nothing to solve with
     int pot_length_units = 0;
     double pot_unit = 1;                         // user length unit -> the solver's
     double pot_depth_user = 0, pot_ext_user[3] = {0, 0, 0};   // [Depth], [extRo] [extRi] [extZo], user units

@@ -331,14 +331,14 @@ __global__ void __launch_bounds__(kBlock) k_pp_corner(int NE, PpArgs A, const in
 // blockIntegral types 0-4 at once: per selected element area, volume, the
 // energy (electrostatics) or volume-weighted T (heat flow), a D and a E(elem);
 // the workgroup's seven sums into part
+// the seven terms of element e (zeros when it is not selected or past the end)
 template <bool HEAT>
-__global__ void __launch_bounds__(kPotQBlock) k_pp_integrals(int NE, PpArgs A, const unsigned char *__restrict__ sel,
-                                                             const double *__restrict__ D,
-                                                             const double *__restrict__ Ef, double lc2,
-                                                             double *__restrict__ part)
+__device__ __forceinline__ void pp_integral_terms(int e, int NE, const PpArgs &A, const unsigned char *__restrict__ sel,
+                                                  const double *__restrict__ D, const double *__restrict__ Ef,
+                                                  double lc2, double (&v)[7])
 {
-    const int e = blockIdx.x * kPotQBlock + threadIdx.x;
-    double v[7] = {0., 0., 0., 0., 0., 0., 0.};
+#pragma unroll
+    for (int c = 0; c < 7; ++c) v[c] = 0.;
     if (e < NE && sel[A.lbl[e]]) {
         const int n[3] = {A.p[3 * e], A.p[3 * e + 1], A.p[3 * e + 2]};
         const double X[3] = {A.x[n[0]], A.x[n[1]], A.x[n[2]]}, Y[3] = {A.y[n[0]], A.y[n[1]], A.y[n[2]]};
@@ -368,7 +368,49 @@ __global__ void __launch_bounds__(kPotQBlock) k_pp_integrals(int NE, PpArgs A, c
         v[5] = av * Er;
         v[6] = av * Ei;
     }
+}
+
+template <bool HEAT>
+__global__ void __launch_bounds__(kPotQBlock) k_pp_integrals(int NE, PpArgs A, const unsigned char *__restrict__ sel,
+                                                             const double *__restrict__ D,
+                                                             const double *__restrict__ Ef, double lc2,
+                                                             double *__restrict__ part)
+{
+    const int e = blockIdx.x * kPotQBlock + threadIdx.x;
+    double v[7];
+    pp_integral_terms<HEAT>(e, NE, A, sel, D, Ef, lc2, v);
     block_sums<7>(v, part);
+}
+
+// The same seven sums in the reference's order: element by element, one
+// rounding per selected element (epproc.cpp:268-397, hpproc.cpp:584-646), so
+// that a value on a tie of the reference's "%f" prints as the reference
+// prints it.  One workgroup: tiles of kPotQBlock elements, each thread its
+// element's terms into LDS, then seven threads add their column in element
+// order (an unselected element adds an exact 0).  About 3 ns per element;
+// for the file-based post-processors, not the hot path.
+template <bool HEAT>
+__global__ void __launch_bounds__(kPotQBlock) k_pp_integrals_seq(int NE, PpArgs A,
+                                                                 const unsigned char *__restrict__ sel,
+                                                                 const double *__restrict__ D,
+                                                                 const double *__restrict__ Ef, double lc2,
+                                                                 double *__restrict__ out)
+{
+    __shared__ double term[7][kPotQBlock];
+    double s = 0.;
+    for (int e0 = 0; e0 < NE; e0 += kPotQBlock) {
+        double v[7];
+        pp_integral_terms<HEAT>(e0 + (int)threadIdx.x, NE, A, sel, D, Ef, lc2, v);
+#pragma unroll
+        for (int c = 0; c < 7; ++c) term[c][threadIdx.x] = v[c];
+        __syncthreads();
+        if (threadIdx.x < 7) {
+            const int n = min(kPotQBlock, NE - e0);
+            for (int i = 0; i < n; ++i) s += term[threadIdx.x][i];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 7) out[threadIdx.x] = s;
 }
 
 // --- the weighted stress tensor mask (PostProcessor::makeMask) ---------------
@@ -826,13 +868,14 @@ __global__ void __launch_bounds__(kBlock) k_pp_points(int n, PpArgs A, PpGrid G,
                                                       const double *__restrict__ py, int smooth,
                                                       const double *__restrict__ D, const double *__restrict__ dc,
                                                       int *__restrict__ elem, double *__restrict__ out,
-                                                      int *__restrict__ ntests)
+                                                      int *__restrict__ ntests, int given)
 {
     const int t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= n) return;
     const double x = px[t], y = py[t];
-    int nt;
-    const int k = pp_find(A, G, L, x, y, nt);
+    int nt = 0;
+    // given: elem[t] names the element on entry (checked by the host; -1: none)
+    const int k = given ? elem[t] : pp_find(A, G, L, x, y, nt);
     // (diagnostics: the elements this point is tested against)
     if (ntests) ntests[t] = nt;
     double *o = out + 8 * (size_t)t;
@@ -972,6 +1015,113 @@ __global__ void __launch_bounds__(kPotQBlock) k_pp_contour_sum(const int *__rest
         for (int c = 0; c < 3; ++c) s[c] += part[3 * (size_t)(b0 + i) + c];
     }
     block_sums<3>(s, out);
+}
+
+// --- plot bounds (OpenDocument, epproc.cpp:184-225, hpproc.cpp: its twin) -----
+//
+// Extremes of the potential over the nodes and of |D| and |E| (|F|, |G|) over
+// the elements outside the external region, and the number of external
+// elements, which names the reference's starting element.  Seven values per
+// workgroup: min V, max V, min |D|, max |D|, min |E|, max |E|, the count.
+// fmin / fmax drop a NaN as the reference's comparisons do, and neither
+// depends on the order, so the shuffles and the fold give the same bits
+// whatever the launch shape; the count is an exact sum of small integers.
+constexpr int kPpBoundsBlock = 256;
+constexpr int kPpBoundsK = 7;
+
+// the workgroup's extremes and count (wave shuffles, then the waves in
+// order) into out[7 wg .. 7 wg + 7); workgroups of kPpBoundsBlock threads
+__device__ __forceinline__ void block_bounds(double (&v)[kPpBoundsK], double *__restrict__ out)
+{
+    __shared__ double red[kPpBoundsK * (kPpBoundsBlock / 64)];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 6; c += 2) {
+            v[c] = fmin(v[c], __shfl_xor(v[c], off, 64));
+            v[c + 1] = fmax(v[c + 1], __shfl_xor(v[c + 1], off, 64));
+        }
+        v[6] += __shfl_xor(v[6], off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < kPpBoundsK; ++c) red[kPpBoundsK * (threadIdx.x >> 6) + c] = v[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s[kPpBoundsK];
+#pragma unroll
+        for (int c = 0; c < kPpBoundsK; ++c) s[c] = red[c];
+        for (int w = 1; w < kPpBoundsBlock / 64; ++w) {
+#pragma unroll
+            for (int c = 0; c < 6; c += 2) {
+                s[c] = fmin(s[c], red[kPpBoundsK * w + c]);
+                s[c + 1] = fmax(s[c + 1], red[kPpBoundsK * w + c + 1]);
+            }
+            s[6] += red[kPpBoundsK * w + 6];
+        }
+#pragma unroll
+        for (int c = 0; c < kPpBoundsK; ++c) out[kPpBoundsK * (size_t)blockIdx.x + c] = s[c];
+    }
+}
+
+__device__ __forceinline__ void pp_bounds_neutral(double (&v)[kPpBoundsK])
+{
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+#pragma unroll
+    for (int c = 0; c < 6; c += 2) {
+        v[c] = inf;
+        v[c + 1] = -inf;
+    }
+    v[6] = 0.;
+}
+
+// thread t: node t and element t, where they exist
+__global__ void __launch_bounds__(kPpBoundsBlock) k_pp_bounds(int N, int NE, const double *__restrict__ V,
+                                                              const int *__restrict__ lbl,
+                                                              const PotLabel *__restrict__ labels,
+                                                              const double *__restrict__ D,
+                                                              const double *__restrict__ Ef,
+                                                              double *__restrict__ part)
+{
+    const size_t t = (size_t)blockIdx.x * kPpBoundsBlock + threadIdx.x;
+    double v[kPpBoundsK];
+    pp_bounds_neutral(v);
+    if (t < (size_t)N) {
+        const double a = V[t];
+        v[0] = fmin(v[0], a);
+        v[1] = fmax(v[1], a);
+    }
+    if (t < (size_t)NE) {
+        if (labels[lbl[t]].external) {
+            v[6] = 1.;
+        } else {
+            const double d = pp_cabs(D[2 * t], D[2 * t + 1]), e = pp_cabs(Ef[2 * t], Ef[2 * t + 1]);
+            v[2] = fmin(v[2], d);
+            v[3] = fmax(v[3], d);
+            v[4] = fmin(v[4], e);
+            v[5] = fmax(v[5], e);
+        }
+    }
+    block_bounds(v, part);
+}
+
+// G workgroups' partials, strided per thread, then the workgroup's; one workgroup
+__global__ void __launch_bounds__(kPpBoundsBlock) k_pp_bounds_fold(int G, const double *__restrict__ part,
+                                                                   double *__restrict__ out)
+{
+    double v[kPpBoundsK];
+    pp_bounds_neutral(v);
+    for (int i = threadIdx.x; i < G; i += kPpBoundsBlock) {
+        const double *q = part + kPpBoundsK * (size_t)i;
+#pragma unroll
+        for (int c = 0; c < 6; c += 2) {
+            v[c] = fmin(v[c], q[c]);
+            v[c + 1] = fmax(v[c + 1], q[c + 1]);
+        }
+        v[6] += q[6];
+    }
+    block_bounds(v, out);
 }
 
 // --- host side ---------------------------------------------------------------
@@ -1220,7 +1370,7 @@ static void pp_div_volume(double &re, double &im, double vol)
     im = i;
 }
 
-static int pp_block_integrals(xfk_problem *P, const unsigned char *sel, double *out)
+static int pp_block_integrals(xfk_problem *P, const unsigned char *sel, double *out, bool ordered = false)
 {
     XFK_REQUIRE(sel, XFK_ERR_ARG, "null selection mask (one byte per block label)");
     XFK_REQUIRE(out, XFK_ERR_ARG, "null output");
@@ -1236,9 +1386,14 @@ static int pp_block_integrals(xfk_problem *P, const unsigned char *sel, double *
     // (epproc squares LengthConv, hpproc takes pow(., 2.))
     const double lc2 = P->heat ? std::pow(A.lc, 2.) : A.lc * A.lc;
     double *sums = P->pp_part.p + 7 * (size_t)G;
-    if (P->heat) k_pp_integrals<true><<<G, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, P->pp_part.p);
-    else k_pp_integrals<false><<<G, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, P->pp_part.p);
-    k_pot_sum<7><<<1, kPotQBlock, 0, s>>>(G, P->pp_part.p, sums);
+    if (ordered) {
+        if (P->heat) k_pp_integrals_seq<true><<<1, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, sums);
+        else k_pp_integrals_seq<false><<<1, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, sums);
+    } else {
+        if (P->heat) k_pp_integrals<true><<<G, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, P->pp_part.p);
+        else k_pp_integrals<false><<<G, kPotQBlock, 0, s>>>(NE, A, P->pp_sel.p, P->pp_D.p, P->pp_E.p, lc2, P->pp_part.p);
+        k_pot_sum<7><<<1, kPotQBlock, 0, s>>>(G, P->pp_part.p, sums);
+    }
     XFK_CHECK(hipGetLastError());
     XFK_CHECK(d2h(out, sums, 7 * sizeof(double), s));
     // the averaged types, divided after the loop as the reference does
@@ -1297,7 +1452,7 @@ static PpLists pp_lists(const xfk_problem *P)
 }
 
 static int pp_launch_points(xfk_problem *P, int n, const double *px, const double *py, int smooth, double *o,
-                            int *ntests)
+                            int *ntests, int given = 0)
 {
     const PpArgs A = pp_args(P);
     const PpGrid G = pp_grid_args(P);
@@ -1306,10 +1461,10 @@ static int pp_launch_points(xfk_problem *P, int n, const double *px, const doubl
     hipStream_t s = P->stream;
     if (P->heat)
         k_pp_points<true><<<g, kBlock, 0, s>>>(n, A, G, L, px, py, smooth ? 1 : 0, P->pp_D.p, P->pp_d.p, P->pp_pel.p, o,
-                                               ntests);
+                                               ntests, given);
     else
         k_pp_points<false><<<g, kBlock, 0, s>>>(n, A, G, L, px, py, smooth ? 1 : 0, P->pp_D.p, P->pp_d.p, P->pp_pel.p, o,
-                                                ntests);
+                                                ntests, given);
     XFK_CHECK(hipGetLastError());
     return XFK_OK;
 }
@@ -1892,6 +2047,69 @@ int xfk_pot_get_qmarks(xfk_problem *P, int *Q)
     });
 }
 
+int xfk_pot_set_qmarks(xfk_problem *P, const int *Q)
+{
+    return pp_entry(P, false, [&]() -> int {
+        XFK_REQUIRE(Q, XFK_ERR_ARG, "null marks");
+        const int nc = (int)P->pot_cel_ptr.size() - 1;
+        for (int i = 0; i < P->N; ++i)
+            XFK_REQUIRE(Q[i] >= -2 && Q[i] < std::max(0, nc), XFK_ERR_ARG,
+                        "a node mark is neither -2, -1 nor the index of a conductor");
+        P->pot_qmark.assign(Q, Q + P->N);
+        P->pot_from_file = true;
+        // the corner fields and the mask read the marks
+        pp_invalidate(P);
+        if (P->pp_mesh_ready) {
+            XFK_CHECK(upload(P->pp_q, P->pot_qmark.data(), P->pot_qmark.size(), P->stream));
+            XFK_CHECK(hipStreamSynchronize(P->stream));
+        }
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_plot_bounds(xfk_problem *P, double *out6)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(out6, XFK_ERR_ARG, "null output");
+        int rc = pp_fields(P);
+        if (rc != XFK_OK) return rc;
+        hipStream_t s = P->stream;
+        const int N = P->N, NE = P->NE;
+        XFK_REQUIRE(N > 0 && NE > 0, XFK_ERR_ARG, "plot bounds need a node and an element");
+        const int G = (std::max(N, NE) + kPpBoundsBlock - 1) / kPpBoundsBlock;
+        DBuf<double> part;
+        XFK_CHECK(part.alloc(kPpBoundsK * ((size_t)G + 1)));
+        double *sums = part.p + kPpBoundsK * (size_t)G;
+        k_pp_bounds<<<G, kPpBoundsBlock, 0, s>>>(N, NE, P->V.p, P->lbl_raw.p, P->pot_labels.p, P->pp_D.p, P->pp_E.p,
+                                                 part.p);
+        k_pp_bounds_fold<<<1, kPpBoundsBlock, 0, s>>>(G, part.p, sums);
+        XFK_CHECK(hipGetLastError());
+        double h[kPpBoundsK];
+        XFK_CHECK(d2h(h, sums, sizeof(h), s));
+        XFK_CHECK(hipStreamSynchronize(s));
+        // The reference's starting values: |D| of the element whose index is
+        // the count of external elements, |E| of element 0, external or not
+        // (epproc.cpp:205-208).  With every element external that index is
+        // past the end in the reference; element 0 stands in here.
+        const int ext = (int)h[6], d0 = ext < NE ? ext : 0;
+        double Ds[2], Es[2];
+        XFK_CHECK(d2h(Ds, P->pp_D.p + 2 * (size_t)d0, sizeof(Ds), s));
+        XFK_CHECK(d2h(Es, P->pp_E.p, sizeof(Es), s));
+        XFK_CHECK(hipStreamSynchronize(s));
+        out6[0] = h[0];
+        out6[1] = h[1];
+        const double start[2] = {pp_cabs(Ds[0], Ds[1]), pp_cabs(Es[0], Es[1])};
+        for (int k = 0; k < 2; ++k) {
+            double lo = start[k], hi = start[k];
+            if (h[3 + 2 * k] > hi) hi = h[3 + 2 * k];
+            if (h[2 + 2 * k] < lo) lo = h[2 + 2 * k];
+            out6[2 + 2 * k] = lo;
+            out6[3 + 2 * k] = hi;
+        }
+        return XFK_OK;
+    });
+}
+
 int xfk_pot_mask_info(xfk_problem *P, double *out9)
 {
     return pp_entry(P, false, [&]() -> int {
@@ -1955,6 +2173,32 @@ int xfk_pot_point_values(xfk_problem *P, int n, const double *x, const double *y
         XFK_CHECK(d2h(out, o, sizeof(double) * 8 * (size_t)n, P->stream));
         return XFK_OK;
     });
+}
+
+int xfk_pot_point_values_at(xfk_problem *P, int n, const double *x, const double *y, const int *elem, int smooth,
+                            double *out)
+{
+    return pp_entry(P, true, [&]() -> int {
+        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of points");
+        if (n == 0) return XFK_OK;
+        XFK_REQUIRE(x && y && elem && out, XFK_ERR_ARG, "null point arrays");
+        for (int i = 0; i < n; ++i)
+            XFK_REQUIRE(elem[i] >= -1 && elem[i] < P->NE, XFK_ERR_ARG, "a point's element is outside the element range");
+        int rc = smooth ? pp_corners(P, nullptr) : pp_fields(P);
+        if (rc == XFK_OK) rc = pp_upload_points(P, n, x, y);
+        if (rc != XFK_OK) return rc;
+        XFK_CHECK(hipMemcpyAsync(P->pp_pel.p, elem, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, P->stream));
+        double *px = P->pp_pts.p, *o = px + 2 * (size_t)n;
+        rc = pp_launch_points(P, n, px, px + n, smooth, o, nullptr, 1);
+        if (rc != XFK_OK) return rc;
+        XFK_CHECK(d2h(out, o, sizeof(double) * 8 * (size_t)n, P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_pot_block_integrals_ordered(xfk_problem *P, const unsigned char *label_selected, double *out7)
+{
+    return pp_entry(P, true, [&]() -> int { return pp_block_integrals(P, label_selected, out7, true); });
 }
 
 int xfk_pot_grid_info(xfk_problem *P, double *out8)

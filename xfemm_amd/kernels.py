@@ -7,6 +7,7 @@ is present, every solve raises.
 from __future__ import annotations
 
 import ctypes as C
+import cmath
 import math
 import os
 from typing import Optional, Sequence
@@ -60,7 +61,8 @@ EXPORTED = (
     "xfk_problem_create_electrostatic", "xfk_electrostatic", "xfk_get_conductors", "xfk_conductor_charge",
     "xfk_problem_create_heatflow", "xfk_heatflow", "xfk_heatflow_assemble", "xfk_heatflow_set_step",
     "xfk_heatflow_advance", "xfk_hf_get_conductors", "xfk_hf_conductor_flow",
-    "xfk_pot_set_solution", "xfk_pot_get_qmarks", "xfk_pot_element_fields", "xfk_pot_corner_fields", "xfk_pot_corner_branches",
+    "xfk_pot_set_solution", "xfk_pot_get_qmarks", "xfk_pot_set_qmarks", "xfk_pot_plot_bounds", "xfk_pot_block_integrals_ordered",
+    "xfk_pot_point_values_at", "xfk_pot_element_fields", "xfk_pot_corner_fields", "xfk_pot_corner_branches",
     "xfk_pot_block_integrals", "xfk_pot_block_integral", "xfk_pot_point_values", "xfk_pot_grid_info", "xfk_pot_time",
     "xfk_pot_make_mask", "xfk_pot_get_mask", "xfk_pot_mask_info", "xfk_pot_mask_problem", "xfk_pot_stress_time",
     "xfk_pot_line_integrals", "xfk_pot_line_integral", "xfk_pot_contour_samples", "xfk_pot_contour_time",
@@ -321,6 +323,10 @@ def load_library(path: str = KERNELS_SO):
     ubptr = C.POINTER(C.c_ubyte)
     L.xfk_pot_set_solution.argtypes = [C.c_void_p, dptr]
     L.xfk_pot_get_qmarks.argtypes = [C.c_void_p, iptr]
+    L.xfk_pot_set_qmarks.argtypes = [C.c_void_p, iptr]
+    L.xfk_pot_plot_bounds.argtypes = [C.c_void_p, dptr]
+    L.xfk_pot_block_integrals_ordered.argtypes = [C.c_void_p, ubptr, dptr]
+    L.xfk_pot_point_values_at.argtypes = [C.c_void_p, C.c_int, dptr, dptr, iptr, C.c_int, dptr]
     L.xfk_pot_element_fields.argtypes = [C.c_void_p, dptr, dptr]
     L.xfk_pot_corner_fields.argtypes = [C.c_void_p, dptr]
     L.xfk_pot_corner_branches.argtypes = [C.c_void_p, ubptr]
@@ -729,6 +735,96 @@ class Contour:
         self.points = []
         return self
 
+    def add_point_from_node(self, geometry, x, y):
+        """addContourPointFromNode (PostProcessor.cpp:173-298) over the input
+        geometry of a solution file (pproc.EPProc.geometry(): points (n, 2),
+        segments (n, 2), arcs (n, 2) with arc_length and arc_maxside in
+        degrees): the input point closest to (x, y) is added; when it and the
+        last contour point are the two ends of an arc segment, the arc is
+        followed in ceil(ArcLength / MaxSideLength) steps, the last of which is
+        the input point itself."""
+        P = np.asarray(geometry["points"], float).reshape(-1, 2)
+        if len(P) == 0:
+            return self
+        pi = 3.141592653589793238462643383
+
+        def closest(px, py):
+            return int(np.argmin(np.sqrt((px - P[:, 0]) ** 2 + (py - P[:, 1]) ** 2)))
+
+        def circle(k):
+            a0, a1 = complex(*P[geometry["arcs"][k][0]]), complex(*P[geometry["arcs"][k][1]])
+            d = abs(a1 - a0)
+            t = (a1 - a0) / d
+            tta = geometry["arc_length"][k] * pi / 180.
+            R = d / (2. * math.sin(tta / 2.))
+            return a0 + (d / 2. + 1j * math.sqrt(R * R - d * d / 4.)) * t, R
+
+        def dist_arc(p, k):
+            c, R = circle(k)
+            d = abs(p - c)
+            if d == 0:
+                return R
+            a0, a1 = complex(*P[geometry["arcs"][k][0]]), complex(*P[geometry["arcs"][k][1]])
+            t = (p - c) / d
+            z = cmath.phase(t / (a0 - c)) * 180 / pi
+            if 0 < z < geometry["arc_length"][k]:
+                return abs(p - c - R * t)
+            return min(abs(p - a0), abs(p - a1))
+
+        def dist_seg(k):
+            (x0, y0), (x1, y1) = P[geometry["segments"][k][0]], P[geometry["segments"][k][1]]
+            t = ((x - x0) * (x1 - x0) + (y - y0) * (y1 - y0)) / ((x1 - x0) ** 2 + (y1 - y0) ** 2)
+            t = min(1., max(0., t))
+            return math.hypot(x - (x0 + t * (x1 - x0)), y - (y0 + t * (y1 - y0)))
+
+        x, y = float(x), float(y)
+        n0 = closest(x, y)
+        z = complex(*P[n0])
+        if not self.points:
+            self.points.append((z.real, z.imag))
+            return self
+        last = complex(*self.points[-1])
+        if last == z:
+            return self
+        n1 = closest(last.real, last.imag)
+        line, arc, rev, d1 = -1, -1, False, 1.e08
+        if abs(complex(*P[n1]) - last) < 1.e-08:
+            for k, (a, b) in enumerate(np.asarray(geometry["segments"], int).reshape(-1, 2)):
+                if (a, b) in ((n1, n0), (n0, n1)):
+                    d2 = dist_seg(k)
+                    if d2 < d1:
+                        line, d1 = k, d2
+            for k, (a, b) in enumerate(np.asarray(geometry["arcs"], int).reshape(-1, 2)):
+                for r in (True, False):
+                    if (a, b) == ((n1, n0) if r else (n0, n1)):
+                        d2 = dist_arc(complex(x, y), k)
+                        if d2 < d1:
+                            arc, line, rev, d1 = k, -1, r, d2
+
+        def behind(q):
+            return len(self.points) > 1 and abs(complex(*self.points[-2]) - q) < 1.e-08
+
+        if line < 0 and arc < 0:
+            self.points.append((z.real, z.imag))
+        if line >= 0:
+            if behind(z):
+                return self
+            self.points.append((z.real, z.imag))
+        if arc >= 0:
+            c, _ = circle(arc)
+            n = int(math.ceil(geometry["arc_length"][arc] / geometry["arc_maxside"][arc]))
+            th = geometry["arc_length"][arc] * pi / (180. * float(n))
+            rot = complex(math.cos(th), math.sin(th) if rev else -math.sin(th))
+            w = last
+            for i in range(n):
+                w = (w - c) * rot + c
+                if i == n - 1:
+                    w = z
+                if behind(w):
+                    return self
+                self.points.append((w.real, w.imag))
+        return self
+
     def bend(self, angle, step=1.0):
         """bendContour (PostProcessor.cpp:772-820): the last segment becomes an
         arc of `angle` degrees in steps of `step` (0: 1).  An angle of 0 or
@@ -781,6 +877,31 @@ class _PotentialPostProc:
         if v.shape != (self.n_nodes,):
             raise ValueError("expected one value per node (%d), got shape %s" % (self.n_nodes, v.shape))
         _check(_lib.xfk_pot_set_solution(self._h, v.ctypes.data_as(dptr)))
+
+    def qmarks(self) -> np.ndarray:
+        """The mark of every node as the reference's L.Q holds it: a conductor's
+        index, else -1 on a fixed node, else -2."""
+        Q = np.zeros(self.n_nodes, np.int32)
+        _check(_lib.xfk_pot_get_qmarks(self._h, Q.ctypes.data_as(iptr)))
+        return Q
+
+    def set_qmarks(self, Q):
+        """The Q column of a solution file in place of the descriptor's marks,
+        before set_solution.  The problem then counts as opened from a file:
+        solve() is refused from here on (xfk_pot_set_qmarks)."""
+        q = np.ascontiguousarray(Q, dtype=np.int32)
+        if q.shape != (self.n_nodes,):
+            raise ValueError("expected one mark per node (%d), got shape %s" % (self.n_nodes, q.shape))
+        _check(_lib.xfk_pot_set_qmarks(self._h, q.ctypes.data_as(iptr)))
+
+    def plot_bounds(self) -> np.ndarray:
+        """d_PlotBounds of the reference's OpenDocument, (3, 2): min and max of
+        the potential over the nodes, of |D| (|F|) and of |E| (|G|) over the
+        elements that are not external, with the reference's starting
+        elements (xfk_pot_plot_bounds)."""
+        o = np.zeros(6)
+        _check(_lib.xfk_pot_plot_bounds(self._h, o.ctypes.data_as(dptr)))
+        return o.reshape(3, 2)
 
     def element_fields(self) -> dict:
         """Per element D and E (F and G for heat flow), (n_elems, 2) each."""
@@ -843,6 +964,25 @@ class _PotentialPostProc:
         _check(_lib.xfk_pot_block_integrals(self._h, mp, o.ctypes.data_as(dptr)))
         n = self._INTEGRAL_NAMES
         return {n[0]: o[0], n[1]: o[1], n[2]: o[2], n[3]: o[3:5].copy(), n[4]: o[5:7].copy(), "raw": o}
+
+    def block_integrals_ordered(self, selected_labels) -> np.ndarray:
+        """The seven sums of block_integrals taken element by element, in the
+        reference's order of summation (xfk_pot_block_integrals_ordered)."""
+        keep, mp = self._mask(selected_labels)
+        o = np.zeros(7)
+        _check(_lib.xfk_pot_block_integrals_ordered(self._h, mp, o.ctypes.data_as(dptr)))
+        return o
+
+    def point_values_at(self, x, y, elem, smooth: bool = False) -> np.ndarray:
+        """The 8 values per point with the element of every point given, (n, 8)
+        (xfk_pot_point_values_at)."""
+        x = np.ascontiguousarray(np.atleast_1d(x), dtype=np.float64)
+        y = np.ascontiguousarray(np.atleast_1d(y), dtype=np.float64)
+        el = np.ascontiguousarray(np.atleast_1d(elem), dtype=np.int32)
+        o = np.zeros((max(1, len(x)), 8))
+        _check(_lib.xfk_pot_point_values_at(self._h, len(x), x.ctypes.data_as(dptr), y.ctypes.data_as(dptr),
+                                            el.ctypes.data_as(iptr), int(bool(smooth)), o.ctypes.data_as(dptr)))
+        return o[:len(x)]
 
     def block_integral(self, selected_labels, kind: int) -> complex:
         """One block integral in the reference's numbering: 0-4, and on an
