@@ -847,7 +847,9 @@ int xfk_pot_contour_time(xfk_problem *prob, int n_contours, const int *ptr, cons
  * level that was coarsened.
  * xfk_amg_probe_apply: U[:, k] = V-cycle(R[:, k]), nvec columns of n doubles
  * each stored one after the other.
- * xfk_amg_probe_refresh: new level-0 values (same pattern), Amg::refresh. */
+ * xfk_amg_probe_refresh: new level-0 values (same pattern), Amg::refresh.
+ * xfk_amg_probe_create takes the CSR under xfk_pcg_solve_csr's input contract
+ * (below) and refuses what breaks it in the same way. */
 typedef struct xfk_amg_probe xfk_amg_probe;
 typedef struct {
     int sweeps;
@@ -891,7 +893,17 @@ int xfk_get_stream(xfk_problem *prob, void **hip_stream);
 
 /* Stand-alone PCG on a host-supplied full symmetric CSR (testing the solver
  * alone, CBigLinProb::PCGSolve semantics with the device preconditioner).
- * V is the initial guess (used when flag != 0) and receives the solution. */
+ * V is the initial guess (used when flag != 0) and receives the solution.
+ * Input contract, checked on the host before any device work: rowptr[0] == 0
+ * and ascending, every column in [0, n), and no column twice in one row --
+ * each is refused with XFK_ERR_ARG; a row without a diagonal entry is
+ * XFK_ERR_SINGULAR.  The columns of a row may come in any order, with either
+ * preconditioner.  The matrix is taken to be symmetric positive definite
+ * (not checked).
+ * iters is the index of the iteration whose test stopped the solve and er its
+ * sqrt(r.M^-1 r / b.M^-1 b).  b == 0 returns at once (iters 0, er 0; V is 0
+ * with flag == 0 and left as given otherwise), and so does an initial guess
+ * whose residual is exactly zero (iters 0, er 0, V as given). */
 int xfk_pcg_solve_csr(int n, const int *rowptr, const int *col, const double *val,
                       const double *b, double *V, int flag, double precision,
                       int device, long long *iters, double *er);

@@ -2967,6 +2967,26 @@ static int csr_problem_upload(int n, const int *rowptr, const int *col, const do
                               std::vector<int> &diag, xfk_problem **out)
 {
     *out = nullptr;
+    // the input contract, checked on the host before any device work: row
+    // pointers that ascend from 0, columns in range, no column twice in a row
+    // (the SpMV would add both, the dense coarsest level's scatter keeps one),
+    // a diagonal entry in every row.  Rows need not be sorted by column.
+    {
+        XFK_REQUIRE(rowptr[0] == 0, XFK_ERR_ARG, "CSR: rowptr[0] is not 0");
+        std::vector<int> seen((size_t)n, -1);
+        diag.assign(n, -1);
+        for (int i = 0; i < n; ++i) {
+            XFK_REQUIRE(rowptr[i + 1] >= rowptr[i], XFK_ERR_ARG, "CSR: row pointers descend");
+            for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+                const int c = col[k];
+                XFK_REQUIRE(c >= 0 && c < n, XFK_ERR_ARG, "CSR: column index out of range");
+                XFK_REQUIRE(seen[c] != i, XFK_ERR_ARG, "CSR: a row holds the same column twice");
+                seen[c] = i;
+                if (c == i) diag[i] = k;
+            }
+        }
+        for (int i = 0; i < n; ++i) XFK_REQUIRE(diag[i] >= 0, XFK_ERR_SINGULAR, "row without a diagonal entry");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device available (the fsolver hot path has no CPU fallback)");
@@ -2983,16 +3003,6 @@ static int csr_problem_upload(int n, const int *rowptr, const int *col, const do
     P->NR = n;
     int rc = XFK_OK;
     hipError_t e = stream_acquire(&P->stream);
-    // diagonal positions
-    diag.assign(n, -1);
-    for (int i = 0; i < n; ++i)
-        for (int k = rowptr[i]; k < rowptr[i + 1]; ++k)
-            if (col[k] == i) diag[i] = k;
-    for (int i = 0; i < n && rc == XFK_OK; ++i)
-        if (diag[i] < 0) {
-            set_error("row without a diagonal entry");
-            rc = XFK_ERR_SINGULAR;
-        }
     hipStream_t s = P->stream;
     if (e == hipSuccess) e = upload(P->rowptr, rowptr, (size_t)n + 1, s);
     if (e == hipSuccess) e = upload(P->col, col, (size_t)P->nnz, s);

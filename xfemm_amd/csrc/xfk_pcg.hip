@@ -177,8 +177,11 @@ __global__ void __launch_bounds__(kAxBlock) k_cg_axpy(CgAxpyArgs A)
     }
     const double er = (res_o == 0.0) ? 0.0 : sqrt(gam / res_o);
     // spars.cpp:259, 313; an inexact Newton pass also stops once the residual
-    // ratio fell by tol_rel from its iteration-0 value
-    const bool stop = (res_o == 0.0) || (A.it >= 1 && (er <= S->tol || er <= S->tol_rel * S->er0));
+    // ratio fell by tol_rel from its iteration-0 value.  gamma_0 == 0 is an
+    // initial guess whose residual is exactly zero: alpha would be 0 / 0 and
+    // its NaN er would never meet the test, so the guess is the answer
+    const bool stop = (res_o == 0.0) || (A.it == 0 && gam == 0.0) ||
+                      (A.it >= 1 && (er <= S->tol || er <= S->tol_rel * S->er0));
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (A.it == 0) {
             S->res_o = res_o;
