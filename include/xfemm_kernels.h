@@ -829,6 +829,58 @@ int xfk_pot_contour_samples(xfk_problem *prob, int n, const double *x, const dou
 int xfk_pot_contour_time(xfk_problem *prob, int n_contours, const int *ptr, const double *x, const double *y,
                          int type, int smooth, int npts, int repeats, double *ms);
 
+/* ---------------------------------------------------------------------------
+ * Post-processing of a magnetostatic problem: the element flux density and the
+ * block integrals of the reference's fpproc that need no mask
+ * (FPProc::GetElementB, fpproc.cpp:2970-3082; FPProc::BlockIntegral, 3642-4092;
+ * CMMaterialProp::DoEnergy / DoCoEnergy, CMaterialProp.cpp:595-677), of a
+ * problem made by xfk_problem_create, planar or axisymmetric, after
+ * xfk_static2d or xfk_mag_set_solution.  fpproc's arithmetic in its operation
+ * order, in the problem's length units; the sums are taken per workgroup and
+ * then over the workgroups in a fixed order, so a call repeats bit for bit.
+ *
+ * Refused, with the cause in xfk_last_error: a harmonic problem and a sharded
+ * problem (XFK_ERR_UNSUPPORTED), an electrostatic or heat-flow problem
+ * (XFK_ERR_ARG); and by the block integrals a selection holding a label whose
+ * block has LamType > 2 (a wound region with proximity effects) or is a
+ * nonlinear permanent magnet (H_c != 0 with a B-H curve)
+ * (XFK_ERR_UNSUPPORTED).  The problem stays usable after a refusal.
+ *
+ * A label's circuit columns (Case, J, dVolts: what GetJA reads,
+ * fpproc.cpp:3495-3578) are the solve's circuit results (xfk_get_circuits),
+ * the ones FSolver writes to the .ans label lines.  The conductivity of a
+ * specified-voltage region is the solver's (0 in a wound label,
+ * static2d.cpp:118-122); the descriptor carries no Lam_d, so fpproc's zero
+ * conductivity of an in-plane laminated block with Lam_d != 0 is not applied.
+ *
+ * xfk_mag_set_solution: A[n_nodes] as the .ans carries it (A, or the flux
+ * 2 pi r A on an axisymmetric problem: what xfk_get_solution returns) replaces
+ * the solution for post-processing, without a solve; the next xfk_static2d
+ * replaces it again.
+ * xfk_mag_set_depth: [Depth] in the problem's length units; -1 (a .fem without
+ * the line), and a problem it was never called on: the reference's default of
+ * 1 m (fpproc.cpp:1618).
+ * xfk_mag_element_b: B1[n_elems], B2[n_elems] (either may be NULL).
+ * xfk_mag_block_integrals: label_selected[n_labels] (non-zero: selected);
+ * out[52]: (re, im) of inttype 0 .. 25.  Answered: 0 A.J, 1 A, 2 stored energy,
+ * 5 area, 7 total current, 8 9 B over the volume, 10 volume, 11 12 Lorentz
+ * force (11 is 0 when axisymmetric), 15 Lorentz torque (planar, else 0),
+ * 17 coenergy, 24 moment of inertia, 25 centroid (re x, im y; 0 / 0 = NaN with
+ * nothing selected).  0 for every other type: 3, 13, 14 and 16 are 0 at
+ * Frequency 0 in the reference as well; 4 (resistive losses) and 6 (total
+ * losses) are not built; 18-23 need the mask.
+ * xfk_mag_block_integral: one type into out2[2]; types 18-23 are refused.
+ * xfk_mag_time: HIP-event ms of the element-B launch (ms[0]) and of the
+ * integral launch with its sum, every label selected (ms[1]): the median of
+ * `repeats` runs after a warm-up.
+ * ------------------------------------------------------------------------- */
+int xfk_mag_set_solution(xfk_problem *prob, const double *A);
+int xfk_mag_set_depth(xfk_problem *prob, double depth);
+int xfk_mag_element_b(xfk_problem *prob, double *B1, double *B2);
+int xfk_mag_block_integrals(xfk_problem *prob, const unsigned char *label_selected, double *out);
+int xfk_mag_block_integral(xfk_problem *prob, const unsigned char *label_selected, int type, double *out2);
+int xfk_mag_time(xfk_problem *prob, int repeats, double *ms);
+
 /* Diagnostics of the AMG hierarchy (single device), for tests; not part of the
  * interface a caller should build on.  A probe holds one hierarchy built from
  * a host CSR (full symmetric, a diagonal in every row) with the options the

@@ -69,6 +69,15 @@ int xfemm_fsolver_set_comm(xfemm_fsolver *h, xfk_comm *comm)
     return 1;
 }
 
+int xfemm_fsolver_set_keep_problem(xfemm_fsolver *h, int keep)
+{
+    if (!h) return 0;
+    h->s.keepProblem = keep != 0;
+    return 1;
+}
+
+xfk_problem *xfemm_fsolver_problem(xfemm_fsolver *h) { return h ? h->s.problem : nullptr; }
+
 int xfemm_fsolver_set_delete_mesh_files(xfemm_fsolver *h, int del)
 {
     if (!h) return 0;

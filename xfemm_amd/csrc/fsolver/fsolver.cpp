@@ -39,6 +39,7 @@ FSolver::FSolver() {}
 FSolver::~FSolver()
 {
     if (ele_fmt_.joinable()) ele_fmt_.join();
+    if (problem) xfk_problem_destroy(problem);
 }
 
 bool FSolver::writes_output() const { return !comm || xfk_comm_rank(comm) == 0; }
@@ -630,6 +631,10 @@ int FSolver::Static2D()
             ele_text_ = format_static_elements();
             node_parts_ = format_static_node_parts();
         });
+    if (problem) {   // (a kept problem of the last solve)
+        xfk_problem_destroy(problem);
+        problem = nullptr;
+    }
     xfk_problem *prob = nullptr;
     int rc = comm ? xfk_problem_create_dist(&ds.d, device, comm, &prob) : xfk_problem_create(&ds.d, device, &prob);
     ms_phase[2] = ms_since(t);
@@ -653,6 +658,10 @@ int FSolver::Static2D()
         if (ele_fmt_.joinable()) ele_fmt_.join();
         ele_text_ = Formatted();
         node_parts_ = NodeParts();
+    }
+    if (rc == XFK_OK && keepProblem && !comm && xfk_mag_set_depth(prob, Depth) == XFK_OK) {
+        problem = prob;   // post-processed by the caller (the xfk_mag_ entry points)
+        prob = nullptr;
     }
     if (prob) xfk_problem_destroy(prob);
     ms_phase[3] = ms_since(t);

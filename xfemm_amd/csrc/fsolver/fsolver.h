@@ -53,6 +53,12 @@ public:
     xfk_comm *comm = nullptr;
     bool writes_output() const;
 
+    // keepProblem: Static2D() leaves its solved device problem in `problem`
+    // (with the file's [Depth] set for post-processing, xfk_mag_set_depth)
+    // until the next solve or the solver's end, instead of destroying it
+    bool keepProblem = false;
+    xfk_problem *problem = nullptr;
+
     bool LoadProblemFile();                              // fsolver.cpp:202-348
     bool loadPreviousSolution(bool loadAprev);           // fsolver.cpp:990-1081
     LoadMeshErr LoadMesh(bool deleteFiles = true);       // fsolver.cpp:350-718

@@ -2404,6 +2404,17 @@ int build_local(const xfk_problem_desc *d, const GlobalPrep &G, const PartPlan *
         set_error(std::string("upload failed: ") + hipGetErrorString(e));
         return fail(XFK_ERR_HIP);
     }
+    if (!plan) {   // host tables of the magnetostatic post-processor (xfk_magpost.hip)
+        P->mag_hblk = G.blk;
+        P->mag_hlab.assign(labp, labp + nlab);
+        P->mag_nlabels = d->n_labels;
+        P->mag_lab_orig.resize(nlab);
+        for (size_t k = 0; k < nlab; ++k) P->mag_lab_orig[k] = (int)std::min<size_t>(k, d->n_labels - 1);
+        for (int i = 0; i < NE && !G.elab.empty(); ++i) P->mag_lab_orig[G.elab[i]] = d->lbl[i];
+        P->mag_ext_user[0] = d->ext_ro;
+        P->mag_ext_user[1] = d->ext_ri;
+        P->mag_ext_user[2] = d->ext_zo;
+    }
     P->nblocks = d->n_blocks;
     P->nlabels = (int)nlab;
     P->nlines = d->n_lines;
@@ -2623,6 +2634,7 @@ int static2d_run(xfk_problem *P, int flags, xfk_result *res)
     int rc = XFK_OK;
     float ms = 0;
     if (P->comm && (rc = P->comm->solve_boundary()) != XFK_OK) return rc;
+    P->mag_A_ready = false;   // (xfk_magpost.hip: its A no longer belongs to V)
     P->pcg_tol = 0;
     P->pcg_tol_rel = 0;
     P->time_spmv = (flags & XFK_TIME_SPMV) != 0;

@@ -664,6 +664,23 @@ struct xfk_problem {
     const double *hf_vo = nullptr;               // the temperatures the next assembly reads (Vo)
     std::vector<xfk_hf_conductor_desc> hf_cond;  // host: the conductor table (q of CircType 1 filled by the solve)
 
+    // post-processing of a magnetostatic problem (xfk_magpost.hip), in the
+    // problem's length units as the reference's fpproc works.  The host tables
+    // are copies of what the problem was created from; mag_A is the solution
+    // as the .ans carries it, derived from V after a solve (mag_A_ready
+    // cleared by static2d_run) or given by xfk_mag_set_solution
+    std::vector<xfk::DevBlock> mag_hblk;         // host: the block table
+    std::vector<xfk::DevLabel> mag_hlab;         // host: the label table (one entry per element of a MagDirFctn label)
+    std::vector<int> mag_lab_orig;               // host: entry of the label table -> the descriptor's label
+    int mag_nlabels = 0;                         // the descriptor's labels (a selection mask's length)
+    double mag_ext_user[3] = {0, 0, 0};          // [extRo] [extRi] [extZo], user units
+    double mag_depth = 1.;                       // Depth in m (the reference's default: 1 m)
+    bool mag_A_ready = false, mag_xy_ready = false;
+    xfk::DBuf<double> mag_x, mag_y, mag_A;       // N: coordinates in user units; A (planar) or 2 pi r A (axisymmetric)
+    xfk::DBuf<double> mag_B;                     // 2 NE: B1 then B2 (xfk_mag_element_b)
+    xfk::DBuf<double> mag_part;                  // block-integral partials and sums
+    xfk::DBuf<char> mag_lab;                     // the per-label table of the last block integral (MagLabel)
+
     // live SpMV launch timing (XFK_TIME_SPMV)
     bool time_spmv = false;
     std::vector<hipEvent_t> spmv_ev;   // pairs

@@ -1,0 +1,742 @@
+// Post-processing of a magnetostatic problem on the device: the element flux
+// density and the volume integrals of the reference's fpproc that need no
+// mask, for MI355X (gfx950).  Frequency 0 only, planar and axisymmetric.
+//
+//   element B         FPProc::GetElementB (fpproc.cpp:2970-3082)
+//   J and A           FPProc::GetJA (3495-3578), PlnInt / AxiInt (3580-3612),
+//                     Ctr (3426-3438), ElmArea (3440-3468), AECF (5286-5304)
+//   energy            CMMaterialProp::GetH, GetEnergy, GetCoEnergy, DoEnergy,
+//                     DoCoEnergy (CMaterialProp.cpp:488-519, 537-677)
+//   block integrals   FPProc::BlockIntegral types 0 1 2 5 7 8 9 10 11 12 15 17
+//                     24 25 (3642-4092)
+//
+// fpproc works in the problem's own length units with LengthConv[] to metres;
+// the solver in cm.  The coordinates are divided back by the solver's unit once
+// (mag_x, mag_y) and everything below reads those.  A is the value the .ans
+// carries: V c, times 2 pi r on an axisymmetric problem (static2d.cpp:1018-1021,
+// staticaxi.cpp:774-779).  All arithmetic is the reference's, operation by
+// operation, in double, without contraction into fused multiply-adds.
+//
+// One pass over the elements gives every integral type: a thread per element
+// evaluates the element's B, J, A and the integrands of all types (zero where
+// the element's label is not selected), and the workgroup's sums go to partials
+// in a fixed order (block_sums); one workgroup then sums the partials in a
+// fixed order (k_pot_sum).  No atomics: two calls give the same bits.
+#include "xfk_potential.h"
+
+#pragma clang fp contract(off)
+
+namespace xfk {
+
+// FPProc's LengthConv[]: user length units -> m; and the solver's: -> cm
+static const double kMagLengthConv[] = {0.0254, 0.001, 0.01, 1., 2.54e-5, 1.e-6};
+static const double kMagUnitCm[] = {2.54, 0.1, 1., 100., 0.00254, 1.e-04};
+
+// the sums one pass makes, in this order
+enum {
+    MS_AJ, MS_A, MS_ENERGY, MS_AREA, MS_CURRENT, MS_B1, MS_B2, MS_VOLUME, MS_FX, MS_FY, MS_TORQUE, MS_COENERGY,
+    MS_INERTIA, MS_CX, MS_CY, kMagSums
+};
+constexpr int kMagTypes = 26;   // inttype 0 .. 25
+
+// What GetJA and the energy read of a block label: the circuit columns are
+// the ones the .ans label lines carry (fpproc.cpp:1289-1308)
+struct MagLabel {
+    double J, dV;           // blocklist[lbl].J (Case 1), dVolts (Case 0)
+    double cos_m, sin_m;    // exp(I PI magdir / 180)
+    int blk;
+    int ccase;              // blocklist[lbl].Case; -1: InCircuit < 0
+    int wound;              // FillFactor > 0: no bulk conductivity
+    int external;
+    int sel;
+    int pad;
+};
+
+struct MagArgs {
+    const double *x, *y, *A;       // user length units; the .ans solution
+    const int *p, *lbl;
+    const MagLabel *labels;
+    const DevBlock *blocks;
+    const double *bhB, *bhH, *bhS;
+    double lc, lc2;                // LengthConv[LengthUnits] and its pow(., 2.)
+    double depth;                  // Depth in m
+    double ext_ro, ext_ri, ext_zo; // user units
+};
+
+// abs(CComplex) (femmcomplex.cpp:749-757)
+__device__ __forceinline__ double mag_cabs(double re, double im)
+{
+    if ((re == 0) && (im == 0)) return 0.;
+    if (fabs(re) > fabs(im)) return fabs(re) * sqrt(1. + (im / re) * (im / re));
+    return fabs(im) * sqrt(1. + (re / im) * (re / im));
+}
+
+// FPProc::GetElementB (fpproc.cpp:2970-3082), without the incremental columns
+template <bool AXI>
+__device__ __forceinline__ void mag_element_b(double lc, const double (&X)[3], const double (&Y)[3],
+                                              const double (&A)[3], double &B1, double &B2)
+{
+    double b[3], c[3];
+    b[0] = Y[1] - Y[2];
+    b[1] = Y[2] - Y[0];
+    b[2] = Y[0] - Y[1];
+    c[0] = X[2] - X[1];
+    c[1] = X[0] - X[2];
+    c[2] = X[1] - X[0];
+    double da = (b[0] * c[1] - b[1] * c[0]);
+    if (!AXI) {
+        B1 = 0;
+        B2 = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            B1 += A[i] * c[i] / (da * lc);
+            B2 -= A[i] * b[i] / (da * lc);
+        }
+        return;
+    }
+    double v[6], r = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r += X[i] / 3.;
+    v[0] = A[0];
+    v[2] = A[1];
+    v[4] = A[2];
+    // mid-side values
+    if ((X[0] < 1.e-06) && (X[1] < 1.e-06)) v[1] = (v[0] + v[2]) / 2.;
+    else v[1] = (X[1] * (3. * v[0] + v[2]) + X[0] * (v[0] + 3. * v[2])) / (4. * (X[0] + X[1]));
+    if ((X[1] < 1.e-06) && (X[2] < 1.e-06)) v[3] = (v[2] + v[4]) / 2.;
+    else v[3] = (X[2] * (3. * v[2] + v[4]) + X[1] * (v[2] + 3. * v[4])) / (4. * (X[1] + X[2]));
+    if ((X[2] < 1.e-06) && (X[0] < 1.e-06)) v[5] = (v[4] + v[0]) / 2.;
+    else v[5] = (X[0] * (3. * v[4] + v[0]) + X[2] * (v[4] + 3. * v[0])) / (4. * (X[2] + X[0]));
+    const double dp = (-v[0] + v[2] + 4. * v[3] - 4. * v[5]) / 3.;
+    const double dq = (-v[0] - 4. * v[1] + 4. * v[3] + v[4]) / 3.;
+    da *= 2. * kPI * r * lc * lc;
+    B1 = -(c[1] * dp + c[2] * dq) / da;
+    B2 = (b[1] * dp + b[2] * dq) / da;
+}
+
+// CMMaterialProp::GetH(double) on B >= 0 (CMaterialProp.cpp:488-519): the
+// section search is a loop over the block's BHpoints knots
+__device__ __forceinline__ double mag_get_h(const MagArgs &M, const DevBlock &bp, double x)
+{
+    const double b = fabs(x);
+    const int n = bp.BHpoints;
+    if ((n == 0) || (b == 0)) return 0;
+    const double *B = M.bhB + bp.bh_off, *H = M.bhH + bp.bh_off, *S = M.bhS + bp.bh_off;
+    const double p = x / b;
+    if (b > B[n - 1]) return p * (H[n - 1] + S[n - 1] * (b - B[n - 1]));
+    for (int i = 0; i < n - 1; ++i)
+        if ((b >= B[i]) && (b <= B[i + 1])) {
+            const double l = B[i + 1] - B[i];
+            const double z = (b - B[i]) / l;
+            const double z2 = z * z;
+            const double h = (1. - 3. * z2 + 2. * z2 * z) * H[i] + z * (1. - 2. * z + z2) * l * S[i] +
+                             z2 * (3. - 2. * z) * H[i + 1] + z2 * (z - 1.) * l * S[i + 1];
+            return p * h;
+        }
+    return 0;
+}
+
+// CMMaterialProp::GetEnergy (CMaterialProp.cpp:537-588)
+__device__ __forceinline__ double mag_get_energy(const MagArgs &M, const DevBlock &bp, double x)
+{
+    const double b = fabs(x);
+    double nrg = 0.;
+    const int n = bp.BHpoints;
+    if (n == 0) return 0;
+    const double *B = M.bhB + bp.bh_off, *H = M.bhH + bp.bh_off, *S = M.bhS + bp.bh_off;
+    for (int i = 0; i < n - 1; ++i) {
+        const double b0 = B[i], h0 = H[i], b1 = B[i + 1], h1 = H[i + 1];
+        const double dh0 = S[i], dh1 = S[i + 1];
+        if ((b >= b0) && (b <= b1)) {
+            const double l = b1 - b0;
+            const double z = (b - b0) / l;
+            const double z2 = z * z;
+            nrg += (dh0 * l * l * (6. + z * (-8. + 3. * z)) * z2) / 12. + (h0 * l * z * (2. + (-2. + z) * z2)) / 2. -
+                   (h1 * l * (-2. + z) * z2 * z) / 2. + (dh1 * l * l * (-4. + 3. * z) * z2 * z) / 12;
+            return nrg;
+        }
+        nrg += ((b0 - b1) * ((b0 - b1) * (dh0 - dh1) - 6. * (h0 + h1))) / 12.;
+    }
+    // off the scale: extrapolate the rest of the way
+    const double h0 = H[n - 1], dh0 = S[n - 1], b0 = B[n - 1];
+    nrg += ((b - b0) * (b * dh0 - b0 * dh0 + 2 * h0)) / 2.;
+    return nrg;
+}
+
+// GetCoEnergy (CMaterialProp.cpp:590-593)
+__device__ __forceinline__ double mag_get_coenergy(const MagArgs &M, const DevBlock &bp, double b)
+{
+    return (fabs(b) * mag_get_h(M, bp, b) - mag_get_energy(M, bp, b));
+}
+
+// DoEnergy / DoCoEnergy (CMaterialProp.cpp:595-677), LamType 0 1 2 (a
+// LamType > 2 label is refused on the host).  The linear LamType 1 and 2
+// cases multiply b1 where one would expect b2: kept as written.
+template <bool CO>
+__device__ __forceinline__ double mag_do_energy(const MagArgs &M, const DevBlock &bp, double b1, double b2)
+{
+    const double muo = kMUO;
+    const double LamFill = bp.LamFill;
+    if (bp.BHpoints == 0) {
+        double h1 = 0, h2 = 0;
+        if (bp.LamType == 0) {
+            h1 = b1 / ((1. + LamFill * (bp.mu_x - 1.)) * muo);
+            h2 = b2 / ((1. + LamFill * (bp.mu_y - 1.)) * muo);
+        }
+        if (bp.LamType == 1) {
+            h1 = b1 / ((1. + LamFill * (bp.mu_x - 1.)) * muo);
+            h2 = b1 * (LamFill / (bp.mu_y * muo) + (1. - LamFill) / muo);
+        }
+        if (bp.LamType == 2) {
+            h2 = b1 / ((1. + LamFill * (bp.mu_y - 1.)) * muo);
+            h1 = b1 * (LamFill / (bp.mu_x * muo) + (1. - LamFill) / muo);
+        }
+        return ((h1 * b1 + h2 * b2) / 2.);
+    }
+    auto raw = [&](double b) { return CO ? mag_get_coenergy(M, bp, b) : mag_get_energy(M, bp, b); };
+    double nrg = 0;
+    if (bp.LamType == 0) nrg = raw(sqrt(b1 * b1 + b2 * b2));
+    if (bp.LamType == 1) {
+        const double biron = sqrt((b1 / LamFill) * (b1 / LamFill) + b2 * b2);
+        const double bair = b2;
+        nrg = LamFill * raw(biron) + (1 - LamFill) * bair * bair / (2. * muo);
+    }
+    if (bp.LamType == 2) {
+        const double biron = sqrt((b2 / LamFill) * (b2 / LamFill) + b1 * b1);
+        const double bair = b1;
+        nrg = LamFill * raw(biron) + (1 - LamFill) * bair * bair / (2. * muo);
+    }
+    return nrg;
+}
+
+// PlnInt / AxiInt (fpproc.cpp:3580-3612) on real arguments
+__device__ __forceinline__ double mag_pln_int(double a, const double (&u)[3], const double (&v)[3])
+{
+    double z[3], x = 0;
+    z[0] = 2. * u[0] + u[1] + u[2];
+    z[1] = u[0] + 2. * u[1] + u[2];
+    z[2] = u[0] + u[1] + 2. * u[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) x += v[i] * z[i];
+    return a * x / 12.;
+}
+
+__device__ __forceinline__ double mag_axi_int(double a, const double (&u)[3], const double (&v)[3],
+                                              const double (&r)[3])
+{
+    double Mx[3][3], z[3], x = 0;
+    Mx[0][0] = 6. * r[0] + 2. * r[1] + 2. * r[2];
+    Mx[0][1] = 2. * r[0] + 2. * r[1] + 1. * r[2];
+    Mx[0][2] = 2. * r[0] + 1. * r[1] + 2. * r[2];
+    Mx[1][1] = 2. * r[0] + 6. * r[1] + 2. * r[2];
+    Mx[1][2] = 1. * r[0] + 2. * r[1] + 2. * r[2];
+    Mx[2][2] = 2. * r[0] + 2. * r[1] + 6. * r[2];
+    Mx[1][0] = Mx[0][1];
+    Mx[2][0] = Mx[0][2];
+    Mx[2][1] = Mx[1][2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) z[i] = Mx[i][0] * u[0] + Mx[i][1] * u[1] + Mx[i][2] * u[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) x += v[i] * z[i];
+    return kPI * a * x / 30.;
+}
+
+struct MagElem {
+    double X[3], Y[3], A[3];
+    int lbl;
+};
+
+__device__ __forceinline__ void mag_load(const MagArgs &M, int e, MagElem &E)
+{
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int n = M.p[3 * e + j];
+        E.X[j] = M.x[n];
+        E.Y[j] = M.y[n];
+        E.A[j] = M.A[n];
+    }
+    E.lbl = M.lbl[e];
+}
+
+template <bool AXI>
+__global__ void __launch_bounds__(kBlock) k_mag_element_b(int NE, MagArgs M, double *__restrict__ B1,
+                                                          double *__restrict__ B2)
+{
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= NE) return;
+    MagElem E;
+    mag_load(M, e, E);
+    double b1, b2;
+    mag_element_b<AXI>(M.lc, E.X, E.Y, E.A, b1, b2);
+    B1[e] = b1;
+    B2[e] = b2;
+}
+
+// The integrands of one element of a selected label: one case of
+// FPProc::BlockIntegral's switch per sum, in the reference's operation order
+template <bool AXI>
+__device__ __forceinline__ void mag_integrands(const MagArgs &M, const MagElem &E, const MagLabel &lab,
+                                               double (&v)[kMagSums])
+{
+    const DevBlock bp = M.blocks[lab.blk];
+    const double lc = M.lc, Depth = M.depth;
+    double B1, B2;
+    mag_element_b<AXI>(lc, E.X, E.Y, E.A, B1, B2);
+    // Ctr
+    double cx = 0., cy = 0.;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        cx += E.X[j] / 3.;
+        cy += E.Y[j] / 3.;
+    }
+    // GetJA (fpproc.cpp:3495-3578) at Frequency 0
+    double A[3], Jn[3], J;
+    double rn = 0, r = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (!AXI) A[i] = E.A[i];
+        else {
+            rn = E.X[i] * lc;
+            if (fabs(rn / lc) < 1.e-06) A[i] = 0;
+            else A[i] = E.A[i] / (2. * kPI * rn);
+        }
+    }
+    if (AXI) r = cx * lc;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) Jn[i] = bp.J_re;
+    J = bp.J_re;
+    double c = bp.Cduct;
+    if (lab.wound) c = 0;
+    if (lab.ccase == 0) {
+        if (!AXI) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) Jn[i] -= c * lab.dV;
+            J -= c * lab.dV;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                rn = E.X[i];
+                if (fabs(rn / lc) < 1.e-06) Jn[i] -= c * lab.dV / r;
+                else Jn[i] -= c * lab.dV / (rn * lc);
+            }
+            J -= c * lab.dV / r;
+        }
+    } else if (lab.ccase > 0) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) Jn[i] += lab.J;
+        J += lab.J;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) Jn[i] *= 1.e06;
+    J = J * 1.e06;
+
+    // ElmArea, r[], R
+    const double b0 = E.Y[1] - E.Y[2], b1 = E.Y[2] - E.Y[0];
+    const double c0 = E.X[2] - E.X[1], c1 = E.X[0] - E.X[2];
+    const double a = ((b0 * c1 - b1 * c0) / 2.) * M.lc2;
+    double rr[3] = {0, 0, 0}, R = 0;
+    if (AXI) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) rr[k] = E.X[k] * lc;
+        R = (rr[0] + rr[1] + rr[2]) / 3.;
+    }
+    const double av = AXI ? a * (2. * kPI * R) : a * Depth;   // the element's volume
+    const double ones[3] = {1., 1., 1.};
+    // AECF (fpproc.cpp:5286-5304)
+    double aecf = 1.;
+    if (AXI && lab.external) {
+        const double q = mag_cabs(cx, cy - M.ext_zo);
+        aecf = (q * q * M.ext_ri) / (M.ext_ro * M.ext_ro * M.ext_ro);
+    }
+
+    // 0: A.J
+    v[MS_AJ] = AXI ? mag_axi_int(a, A, Jn, rr) : mag_pln_int(a, A, Jn) * Depth;
+    // 1: A
+    if (AXI) v[MS_A] = mag_axi_int(a, ones, A, rr);
+    else {
+        double y = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) y += a * Depth * A[k] / 3.;
+        v[MS_A] = y;
+    }
+    // 2: stored energy, with the second-quadrant correction of a linear magnet
+    {
+        double y;
+        if (bp.H_c != 0 && bp.BHpoints == 0) {
+            const double mu1 = bp.mu_x, mu2 = bp.mu_y;
+            double H1 = B1 / (mu1 * kMUO), H2 = B2 / (mu2 * kMUO);
+            H1 = H1 - bp.H_c * lab.cos_m;
+            H2 = H2 - bp.H_c * lab.sin_m;
+            y = av * 0.5 * kMUO * (mu1 * H1 * H1 + mu2 * H2 * H2);
+        } else y = av * mag_do_energy<false>(M, bp, B1, B2);
+        v[MS_ENERGY] = y * aecf;
+    }
+    // 5, 10: area, volume
+    v[MS_AREA] = a;
+    v[MS_VOLUME] = av;
+    // 7: total current
+    v[MS_CURRENT] = a * J;
+    // 8, 9: B over the volume
+    v[MS_B1] = av * B1;
+    v[MS_B2] = av * B2;
+    // 11, 12: Lorentz force
+    if (AXI) v[MS_FX] = a * 0.;
+    else {
+        double y = -(B2 * J);
+        y *= Depth;
+        v[MS_FX] = a * y;
+    }
+    {
+        double V[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) V[k] = B1 * Jn[k];
+        v[MS_FY] = AXI ? mag_axi_int(-a, ones, V, rr) : mag_pln_int(a, ones, V) * Depth;
+    }
+    // 15: Lorentz torque (planar)
+    if (AXI) v[MS_TORQUE] = 0.;
+    else {
+        const double ccx = cx * lc, ccy = cy * lc;
+        const double y = ccy * (B2 * J) + ccx * (B1 * J);
+        v[MS_TORQUE] = a * y * Depth;
+    }
+    // 17: coenergy
+    v[MS_COENERGY] = av * mag_do_energy<true>(M, bp, B1, B2) * aecf;
+    // 24: moment of inertia
+    if (AXI) v[MS_INERTIA] = mag_axi_int(a, rr, rr, rr);
+    else {
+        double U[3], V[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            U[k] = E.X[k] * lc;
+            V[k] = E.Y[k] * lc;
+        }
+        double y = U[0] * U[0] + U[1] * U[1] + U[2] * U[2];
+        y += U[0] * U[1] + U[0] * U[2] + U[1] * U[2];
+        y += V[0] * V[0] + V[1] * V[1] + V[2] * V[2];
+        y += V[0] * V[1] + V[0] * V[2] + V[1] * V[2];
+        y *= (a * Depth / 6.);
+        v[MS_INERTIA] = y;
+    }
+    // 25: the centroid's two area-weighted sums
+    v[MS_CX] = cx * a;
+    v[MS_CY] = cy * a;
+}
+
+template <bool AXI>
+__global__ void __launch_bounds__(kPotQBlock) k_mag_integrands(int NE, MagArgs M, double *__restrict__ part)
+{
+    const int e = blockIdx.x * kPotQBlock + threadIdx.x;
+    double v[kMagSums];
+#pragma unroll
+    for (int c = 0; c < kMagSums; ++c) v[c] = 0.;
+    if (e < NE) {
+        MagElem E;
+        mag_load(M, e, E);
+        const MagLabel lab = M.labels[E.lbl];
+        if (lab.sel) mag_integrands<AXI>(M, E, lab, v);
+    }
+    block_sums<kMagSums>(v, part);
+}
+
+// user-unit coordinates
+static __global__ void k_mag_xy(int N, const double *__restrict__ x, const double *__restrict__ y, double u,
+                                double *__restrict__ mx, double *__restrict__ my)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    mx[i] = x[i] / u;
+    my[i] = y[i] / u;
+}
+
+// A as xfk_get_solution gives it: V c, then (x 0.01 2 PI) on an axisymmetric problem
+static __global__ void k_mag_a(int N, int axi, const double *__restrict__ V, const double *__restrict__ xcm,
+                               double *__restrict__ A)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    double a = V[i] * kC;
+    if (axi) a *= (xcm[i] * 0.01 * 2 * kPI);
+    A[i] = a;
+}
+
+// The problem kinds this post-processor answers; every other is refused with
+// its name.  body runs with the problem's device and arena active.
+template <class F>
+static int mag_entry(xfk_problem *P, F &&body)
+{
+    try {
+        XFK_REQUIRE(P, XFK_ERR_ARG, "null problem");
+        XFK_REQUIRE(!P->electro && !P->heat, XFK_ERR_ARG,
+                    "not a magnetics problem: xfk_mag_* post-processes magnetostatic problems (xfk_pot_* is for "
+                    "electrostatic and heat-flow problems)");
+        XFK_REQUIRE(!P->harmonic, XFK_ERR_UNSUPPORTED,
+                    "harmonic problem: magnetics post-processing is built for magnetostatic problems only "
+                    "(Frequency 0)");
+        XFK_REQUIRE(!P->comm, XFK_ERR_UNSUPPORTED,
+                    "sharded problem: magnetics post-processing needs the whole mesh on one device");
+        XFK_CHECK(hipSetDevice(P->device));
+        int rc;
+        {
+            ArenaScope arena_scope(&P->arena);
+            rc = body();
+        }
+        problem_recycle(P);
+        return rc;
+    } catch (const std::exception &e) {
+        set_error(std::string("post-processing failed: ") + e.what());
+        return XFK_ERR_ARG;
+    } catch (...) {
+        set_error("post-processing failed: unknown exception");
+        return XFK_ERR_ARG;
+    }
+}
+
+// coordinates in user units (once) and A of the solution in V (after a solve)
+static int mag_prepare(xfk_problem *P)
+{
+    hipStream_t s = P->stream;
+    const int N = P->N, G = (N + kBlock - 1) / kBlock;
+    if (!P->mag_xy_ready) {
+        XFK_CHECK(P->mag_x.alloc((size_t)N));
+        XFK_CHECK(P->mag_y.alloc((size_t)N));
+        k_mag_xy<<<G, kBlock, 0, s>>>(N, P->x.p, P->y.p, kMagUnitCm[P->length_units], P->mag_x.p, P->mag_y.p);
+        XFK_CHECK(hipGetLastError());
+        P->mag_xy_ready = true;
+    }
+    if (!P->mag_A_ready) {
+        XFK_REQUIRE(P->symbolic_ready && P->V.p, XFK_ERR_ARG,
+                    "no solution yet (solve the problem or xfk_mag_set_solution)");
+        XFK_CHECK(P->mag_A.alloc((size_t)N));
+        k_mag_a<<<G, kBlock, 0, s>>>(N, P->axi ? 1 : 0, P->V.p, P->x.p, P->mag_A.p);
+        XFK_CHECK(hipGetLastError());
+        P->mag_A_ready = true;
+    }
+    return XFK_OK;
+}
+
+static MagArgs mag_args(const xfk_problem *P)
+{
+    MagArgs M = {};
+    M.x = P->mag_x.p;
+    M.y = P->mag_y.p;
+    M.A = P->mag_A.p;
+    M.p = P->p_raw.p;
+    M.lbl = P->lbl_raw.p;
+    M.labels = reinterpret_cast<const MagLabel *>(P->mag_lab.p);
+    M.blocks = P->blocks.p;
+    M.bhB = P->bhB.p;
+    M.bhH = P->bhH.p;
+    M.bhS = P->bhS.p;
+    M.lc = kMagLengthConv[P->length_units];
+    M.lc2 = std::pow(M.lc, 2.);
+    M.depth = P->mag_depth;
+    M.ext_ro = P->mag_ext_user[0];
+    M.ext_ri = P->mag_ext_user[1];
+    M.ext_zo = P->mag_ext_user[2];
+    return M;
+}
+
+// The per-label table of a selection: the label's block, direction and flags
+// from the problem's tables, its circuit's Case / J / dVolts from the solve's
+// circuit results -- the columns FSolver writes to the .ans label lines
+// (WriteStatic2D) and fpproc reads back (fpproc.cpp:1289-1308).  Refuses a
+// selected label whose energy this post-processor does not compute.
+static int mag_labels(xfk_problem *P, const unsigned char *sel)
+{
+    hipStream_t s = P->stream;
+    const size_t nlab = P->mag_hlab.size();
+    std::vector<DevCirc> circ(std::max(1, P->ncircs));
+    if (P->ncircs > 0) XFK_CHECK(d2h(circ.data(), P->circs.p, sizeof(DevCirc) * P->ncircs, s));
+    std::vector<MagLabel> t(std::max<size_t>(1, nlab), MagLabel{});
+    for (size_t k = 0; k < nlab; ++k) {
+        const DevLabel &L = P->mag_hlab[k];
+        const DevBlock &B = P->mag_hblk[L.blk];
+        MagLabel &o = t[k];
+        o.blk = L.blk;
+        o.cos_m = L.cos_m;
+        o.sin_m = L.sin_m;
+        o.wound = L.is_wound ? 1 : 0;
+        o.external = L.external ? 1 : 0;
+        o.sel = sel[P->mag_lab_orig[k]] ? 1 : 0;
+        o.ccase = -1;
+        if (L.in_circuit >= 0 && L.in_circuit < P->ncircs) {
+            const DevCirc &C = circ[L.in_circuit];
+            o.ccase = C.ccase;
+            if (C.ccase == 0) o.dV = C.dV;
+            else o.J = C.J;
+        }
+        if (!o.sel) continue;
+        XFK_REQUIRE(B.LamType <= 2, XFK_ERR_UNSUPPORTED,
+                    "a selected label's block has LamType > 2 (a wound region with proximity effects): its energy "
+                    "needs the label's effective conductivity and fill factor (GetFillFactor), which are not built");
+        XFK_REQUIRE(!(B.H_c != 0 && B.BHpoints > 0), XFK_ERR_UNSUPPORTED,
+                    "a selected label's block is a nonlinear permanent magnet (H_c != 0 with a B-H curve): its "
+                    "energy needs fpproc's shifted curve and Nrg, which are not built");
+    }
+    XFK_CHECK(P->mag_lab.alloc(sizeof(MagLabel) * t.size()));
+    XFK_CHECK(hipMemcpyAsync(P->mag_lab.p, t.data(), sizeof(MagLabel) * t.size(), hipMemcpyHostToDevice, s));
+    XFK_CHECK(hipStreamSynchronize(s));   // (t leaves scope)
+    return XFK_OK;
+}
+
+static int mag_launch_integrals(xfk_problem *P, const MagArgs &M)
+{
+    hipStream_t s = P->stream;
+    const int NE = P->NE, G = (NE + kPotQBlock - 1) / kPotQBlock;
+    double *part = P->mag_part.p, *sums = part + kMagSums * (size_t)G;
+    if (P->axi) k_mag_integrands<true><<<G, kPotQBlock, 0, s>>>(NE, M, part);
+    else k_mag_integrands<false><<<G, kPotQBlock, 0, s>>>(NE, M, part);
+    k_pot_sum<kMagSums><<<1, kPotQBlock, 0, s>>>(G, part, sums);
+    return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
+}
+
+// every type as (re, im) pairs indexed by inttype
+static int mag_block_integrals(xfk_problem *P, const unsigned char *sel, double *out)
+{
+    XFK_REQUIRE(sel, XFK_ERR_ARG, "null selection mask (one byte per block label)");
+    XFK_REQUIRE(out, XFK_ERR_ARG, "null output");
+    int rc = mag_labels(P, sel);
+    if (rc == XFK_OK) rc = mag_prepare(P);
+    if (rc != XFK_OK) return rc;
+    const int G = (P->NE + kPotQBlock - 1) / kPotQBlock;
+    XFK_CHECK(P->mag_part.alloc(kMagSums * ((size_t)G + 1)));
+    if ((rc = mag_launch_integrals(P, mag_args(P))) != XFK_OK) {
+        set_error("block integral launch failed");
+        return rc;
+    }
+    double h[kMagSums];
+    XFK_CHECK(d2h(h, P->mag_part.p + kMagSums * (size_t)G, sizeof(h), P->stream));
+    for (int k = 0; k < 2 * kMagTypes; ++k) out[k] = 0.;
+    out[2 * 0] = h[MS_AJ];
+    out[2 * 1] = h[MS_A];
+    out[2 * 2] = h[MS_ENERGY];
+    out[2 * 5] = h[MS_AREA];
+    out[2 * 7] = h[MS_CURRENT];
+    out[2 * 8] = h[MS_B1];
+    out[2 * 9] = h[MS_B2];
+    out[2 * 10] = h[MS_VOLUME];
+    out[2 * 11] = h[MS_FX];
+    out[2 * 12] = h[MS_FY];
+    out[2 * 15] = h[MS_TORQUE];
+    out[2 * 17] = h[MS_COENERGY];
+    out[2 * 24] = h[MS_INERTIA];
+    // the centroid: the two sums over BlockIntegral(5) (0 / 0 with nothing selected)
+    out[2 * 25] = h[MS_CX] / h[MS_AREA];
+    out[2 * 25 + 1] = h[MS_CY] / h[MS_AREA];
+    return XFK_OK;
+}
+
+}  // namespace xfk
+
+using namespace xfk;
+
+extern "C" {
+
+int xfk_mag_set_solution(xfk_problem *P, const double *A)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(A, XFK_ERR_ARG, "null solution");
+        P->mag_A_ready = false;
+        XFK_CHECK(P->mag_A.alloc((size_t)P->N));
+        XFK_CHECK(hipMemcpyAsync(P->mag_A.p, A, sizeof(double) * P->N, hipMemcpyHostToDevice, P->stream));
+        XFK_CHECK(hipStreamSynchronize(P->stream));
+        P->mag_A_ready = true;
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_set_depth(xfk_problem *P, double depth)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(depth > 0 || depth == -1, XFK_ERR_ARG,
+                    "depth must be positive (length units), or -1 for the reference's default of 1 m");
+        // fpproc.cpp:1618-1619
+        P->mag_depth = depth == -1 ? 1. : depth * kMagLengthConv[P->length_units];
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_element_b(xfk_problem *P, double *B1, double *B2)
+{
+    return mag_entry(P, [&]() -> int {
+        int rc = mag_prepare(P);
+        if (rc != XFK_OK) return rc;
+        const int NE = P->NE;
+        XFK_CHECK(P->mag_B.alloc(2 * (size_t)NE));
+        const MagArgs M = mag_args(P);
+        const int G = (NE + kBlock - 1) / kBlock;
+        if (P->axi) k_mag_element_b<true><<<G, kBlock, 0, P->stream>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
+        else k_mag_element_b<false><<<G, kBlock, 0, P->stream>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
+        XFK_CHECK(hipGetLastError());
+        if (B1) XFK_CHECK(d2h(B1, P->mag_B.p, sizeof(double) * (size_t)NE, P->stream));
+        if (B2) XFK_CHECK(d2h(B2, P->mag_B.p + NE, sizeof(double) * (size_t)NE, P->stream));
+        XFK_CHECK(hipStreamSynchronize(P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_block_integrals(xfk_problem *P, const unsigned char *label_selected, double *out)
+{
+    return mag_entry(P, [&]() -> int { return mag_block_integrals(P, label_selected, out); });
+}
+
+int xfk_mag_block_integral(xfk_problem *P, const unsigned char *label_selected, int type, double *out2)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(type >= 0 && type < kMagTypes, XFK_ERR_ARG, "block integral type out of range (0-25)");
+        XFK_REQUIRE(type < 18 || type > 23, XFK_ERR_UNSUPPORTED,
+                    "block integral types 18-23 (weighted stress tensor, Henrotte) need the mask, which is not built");
+        XFK_REQUIRE(out2, XFK_ERR_ARG, "null output");
+        double o[2 * kMagTypes];
+        const int rc = mag_block_integrals(P, label_selected, o);
+        if (rc != XFK_OK) return rc;
+        out2[0] = o[2 * type];
+        out2[1] = o[2 * type + 1];
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_time(xfk_problem *P, int repeats, double *ms)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(repeats > 0 && ms, XFK_ERR_ARG, "xfk_mag_time needs repeats > 0 and its output");
+        std::vector<unsigned char> sel(std::max(1, P->mag_nlabels), 1);
+        int rc = mag_labels(P, sel.data());
+        if (rc == XFK_OK) rc = mag_prepare(P);
+        if (rc != XFK_OK) return rc;
+        hipStream_t s = P->stream;
+        const int NE = P->NE, G = (NE + kPotQBlock - 1) / kPotQBlock, GB = (NE + kBlock - 1) / kBlock;
+        XFK_CHECK(P->mag_part.alloc(kMagSums * ((size_t)G + 1)));
+        XFK_CHECK(P->mag_B.alloc(2 * (size_t)NE));
+        const MagArgs M = mag_args(P);
+        ScopedEvents<2> ev;
+        XFK_CHECK(ev.create());
+        std::vector<double> t;
+        // f() between two events on the stream, repeats + 1 times (the first a warm-up)
+        auto timed = [&](auto f, double &out) -> int {
+            for (int k = 0; k <= repeats; ++k) {
+                XFK_CHECK(hipEventRecord(ev[0], s));
+                const int r = f();
+                if (r != XFK_OK) return r;
+                XFK_CHECK(hipEventRecord(ev[1], s));
+                XFK_CHECK(hipEventSynchronize(ev[1]));
+                float m = 0;
+                XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
+                if (k) t.push_back(m);
+            }
+            std::sort(t.begin(), t.end());
+            out = t[t.size() / 2];
+            t.clear();
+            return XFK_OK;
+        };
+        rc = timed([&] {
+            if (P->axi) k_mag_element_b<true><<<GB, kBlock, 0, s>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
+            else k_mag_element_b<false><<<GB, kBlock, 0, s>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
+            return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
+        }, ms[0]);
+        if (rc != XFK_OK) return rc;
+        return timed([&] { return mag_launch_integrals(P, M); }, ms[1]);
+    });
+}
+
+}  // extern "C"

@@ -30,6 +30,7 @@ EXPORTED = (
     "xfemm_fsolver_frequency", "xfemm_fsolver_num_line_props", "xfemm_fsolver_num_node_props",
     "xfemm_fsolver_num_block_props", "xfemm_fsolver_num_circ_props", "xfemm_fsolver_num_block_labels",
     "xfemm_fsolver_set_comm", "xfemm_fsolver_num_air_gaps", "xfemm_fsolver_get_air_gap_nodes",
+    "xfemm_fsolver_set_keep_problem", "xfemm_fsolver_problem",
 )
 
 _lib = None
@@ -53,6 +54,9 @@ def load_library(path: str = FSOLVER_SO):
     L.xfemm_fsolver_set_device.argtypes = [vp, C.c_int]
     L.xfemm_fsolver_set_delete_mesh_files.argtypes = [vp, C.c_int]
     L.xfemm_fsolver_set_comm.argtypes = [vp, vp]
+    L.xfemm_fsolver_set_keep_problem.argtypes = [vp, C.c_int]
+    L.xfemm_fsolver_problem.argtypes = [vp]
+    L.xfemm_fsolver_problem.restype = vp
     for nm in ("xfemm_fsolver_load_problem_file", "xfemm_fsolver_load_mesh", "xfemm_fsolver_cuthill",
                "xfemm_fsolver_num_nodes", "xfemm_fsolver_num_elements", "xfemm_fsolver_num_pbcs",
                "xfemm_fsolver_bandwidth", "xfemm_fsolver_num_air_gaps"):
@@ -116,6 +120,10 @@ def bh_get_slopes_ac(B, H, omega, lam_type=0, lam_fill=1.0, theta_hn=0.0, lam_d=
     return B, H + 1j * Hi, S + 1j * Si, mu.value, mm.value
 
 
+class _SolvedProblem(kernels._MagPostProc):
+    """A solved problem an FSolver keeps (FSolver.problem)."""
+
+
 class FSolver:
     """The reference FSolver workflow over the MI355X hot path."""
 
@@ -135,6 +143,26 @@ class FSolver:
         FSolver on the same files, rank 0 writes the .ans."""
         self._comm = comm
         _lib.xfemm_fsolver_set_comm(self._h, comm._h if comm is not None else None)
+
+    def keep_problem(self, keep: bool = True):
+        """Have a static single-device runSolver leave its solved device
+        problem alive for post-processing (xfemm_fsolver_set_keep_problem)."""
+        _lib.xfemm_fsolver_set_keep_problem(self._h, int(bool(keep)))
+
+    def problem(self):
+        """The kept problem of the last solve as a post-processing view
+        (kernels._MagPostProc: element_b, block_integrals, ...), with the
+        file's [Depth] and the solve's circuit table; None without one.  The
+        solver owns it: the view is valid until the next solve or the
+        solver's end."""
+        h = _lib.xfemm_fsolver_problem(self._h)
+        if not h:
+            return None
+        v = _SolvedProblem()
+        v._h, v._owner = C.c_void_p(h), self
+        v.n_nodes, v.n_elems = self.NumNodes, self.NumEls
+        v.n_labels = _lib.xfemm_fsolver_num_block_labels(self._h)
+        return v
 
     def __del__(self):
         try:

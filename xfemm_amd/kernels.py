@@ -66,6 +66,8 @@ EXPORTED = (
     "xfk_pot_block_integrals", "xfk_pot_block_integral", "xfk_pot_point_values", "xfk_pot_grid_info", "xfk_pot_time",
     "xfk_pot_make_mask", "xfk_pot_get_mask", "xfk_pot_mask_info", "xfk_pot_mask_problem", "xfk_pot_stress_time",
     "xfk_pot_line_integrals", "xfk_pot_line_integral", "xfk_pot_contour_samples", "xfk_pot_contour_time",
+    "xfk_mag_set_solution", "xfk_mag_set_depth", "xfk_mag_element_b", "xfk_mag_block_integrals",
+    "xfk_mag_block_integral", "xfk_mag_time",
     "xfk_amg_probe_create", "xfk_amg_probe_info", "xfk_amg_probe_level_size", "xfk_amg_probe_level_csr",
     "xfk_amg_probe_tiles", "xfk_amg_probe_vector", "xfk_amg_probe_trace", "xfk_amg_probe_apply",
     "xfk_amg_probe_refresh", "xfk_amg_probe_destroy",
@@ -344,6 +346,12 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_pot_line_integral.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, C.c_int, C.c_int, dptr, iptr]
     L.xfk_pot_contour_samples.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, C.c_int, dptr, iptr]
     L.xfk_pot_contour_time.argtypes = [C.c_void_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_int, C.c_int, C.c_int, dptr]
+    L.xfk_mag_set_solution.argtypes = [C.c_void_p, dptr]
+    L.xfk_mag_set_depth.argtypes = [C.c_void_p, C.c_double]
+    L.xfk_mag_element_b.argtypes = [C.c_void_p, dptr, dptr]
+    L.xfk_mag_block_integrals.argtypes = [C.c_void_p, ubptr, dptr]
+    L.xfk_mag_block_integral.argtypes = [C.c_void_p, ubptr, C.c_int, dptr]
+    L.xfk_mag_time.argtypes = [C.c_void_p, C.c_int, dptr]
     L.xfk_sort_elements.argtypes = [C.c_int, C.POINTER(C.c_uint), C.c_int, iptr]
     L.xfk_magdir_eval.argtypes = [C.c_char_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_double, dptr]
     L.xfk_lua_run.argtypes = [C.c_char_p, C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong)]
@@ -551,7 +559,76 @@ def age_element_matrix(ci: float, co: float, K: float, Ki: float) -> np.ndarray:
     return out.reshape(10, 10)
 
 
-class Static2DProblem:
+class _MagPostProc:
+    """Post-processing of a magnetostatic problem (the xfk_mag_ entry points):
+    fpproc's element flux density and its block integrals that need no mask.
+    The subclass provides _h, n_nodes, n_elems and n_labels.  A harmonic or a
+    sharded problem is refused by the library with its cause."""
+
+    # inttype -> name of the types answered (the others are 0)
+    MAG_INTEGRALS = {0: "AJ", 1: "A", 2: "energy", 5: "area", 7: "current", 8: "B1", 9: "B2", 10: "volume",
+                     11: "force_x", 12: "force_y", 15: "torque", 17: "coenergy", 24: "inertia", 25: "centroid"}
+
+    def set_solution(self, A):
+        """Post-process a given solution (one value per node as the .ans
+        carries it: A, or the flux 2 pi r A on an axisymmetric problem)
+        without solving (xfk_mag_set_solution)."""
+        a = np.ascontiguousarray(A, dtype=np.float64)
+        if a.shape != (self.n_nodes,):
+            raise ValueError("expected one value per node (%d), got shape %s" % (self.n_nodes, a.shape))
+        _check(_lib.xfk_mag_set_solution(self._h, a.ctypes.data_as(dptr)))
+
+    def set_depth(self, depth: float):
+        """[Depth] in the problem's length units; -1: the reference's default
+        of 1 m, which also holds when this is never called (xfk_mag_set_depth)."""
+        _check(_lib.xfk_mag_set_depth(self._h, float(depth)))
+
+    def element_b(self) -> np.ndarray:
+        """The flux density of every element, (n_elems, 2) (xfk_mag_element_b)."""
+        B1 = np.zeros(self.n_elems)
+        B2 = np.zeros(self.n_elems)
+        _check(_lib.xfk_mag_element_b(self._h, B1.ctypes.data_as(dptr), B2.ctypes.data_as(dptr)))
+        return np.stack([B1, B2], axis=1)
+
+    def _mag_mask(self, selected_labels):
+        m = np.zeros(max(1, self.n_labels), np.uint8)
+        s = np.asarray(selected_labels)
+        if s.dtype == np.bool_:
+            m[:len(s)] = s
+        elif s.size:
+            m[s.astype(np.int64)] = 1
+        return m, m.ctypes.data_as(C.POINTER(C.c_ubyte))
+
+    def block_integrals(self, selected_labels) -> dict:
+        """Every block integral over the elements of the selected labels
+        (indices, or a boolean mask per label) from one pass over the mesh:
+        the named types of MAG_INTEGRALS, and "raw", the complex values
+        indexed by the reference's inttype (26 of them)."""
+        keep, mp = self._mag_mask(selected_labels)
+        o = np.zeros(52)
+        _check(_lib.xfk_mag_block_integrals(self._h, mp, o.ctypes.data_as(dptr)))
+        raw = o[0::2] + 1j * o[1::2]
+        r = {name: (raw[t] if t == 25 else raw[t].real) for t, name in self.MAG_INTEGRALS.items()}
+        r["raw"] = raw
+        return r
+
+    def block_integral(self, selected_labels, kind: int) -> complex:
+        """One block integral in the reference's numbering (xfk_mag_block_integral)."""
+        keep, mp = self._mag_mask(selected_labels)
+        o = np.zeros(2)
+        _check(_lib.xfk_mag_block_integral(self._h, mp, int(kind), o.ctypes.data_as(dptr)))
+        return complex(o[0], o[1])
+
+    def time_postproc(self, repeats: int = 5) -> dict:
+        """Diagnostic: HIP-event times (ms, medians after a warm-up) of the
+        element-B launch and of the block-integral launch with its sum, every
+        label selected (xfk_mag_time)."""
+        ms = np.zeros(2)
+        _check(_lib.xfk_mag_time(self._h, int(repeats), ms.ctypes.data_as(dptr)))
+        return dict(element_b=float(ms[0]), block_integrals=float(ms[1]))
+
+
+class Static2DProblem(_MagPostProc):
     """One device-resident static 2-D magnetostatic problem (FSolver::Static2D).
 
     Arrays follow the reference's in-memory state after FSolver::LoadMesh and
@@ -592,6 +669,7 @@ class Static2DProblem:
         self.n_nodes = D.n_nodes
         self.n_elems = D.n_elems
         self.n_circs = len(circuits)
+        self.n_labels = len(labels)
         h = C.c_void_p()
         self.comm = comm
         if comm is None:
@@ -1423,11 +1501,13 @@ class HarmonicDesc(C.Structure):
                 ("label_prox_mu", C.POINTER(C.c_double))]
 
 
-class Harmonic2DProblem:
+class Harmonic2DProblem(_MagPostProc):
     """One device-resident time-harmonic planar problem (FSolver::Harmonic2D).
     Same keyword arguments as Static2DProblem plus ``frequency`` (Hz) and the
     AC fields: blocks J_im, Theta_hx, Theta_hy, Lam_d; lines c0_im, c1_im, Mu,
-    Sig (BdryFormat 1); circuits amps_im, dvolts_im."""
+    Sig (BdryFormat 1); circuits amps_im, dvolts_im.  The post-processing
+    methods it shares with Static2DProblem are refused: they are built for
+    magnetostatic problems only."""
 
     def __init__(self, *, x, y, p, lbl, blocks: Sequence[dict], labels: Sequence[dict], frequency: float,
                  lines: Sequence[dict] = (), points: Sequence[dict] = (), circuits: Sequence[dict] = (),
@@ -1467,7 +1547,9 @@ class Harmonic2DProblem:
         keep.extend([ba, la, ca])
         self._keep = keep
         self.n_nodes = D.n_nodes
+        self.n_elems = D.n_elems
         self.n_circs = len(circuits)
+        self.n_labels = len(labels)
         h = C.c_void_p()
         self.comm = comm
         if comm is None:
