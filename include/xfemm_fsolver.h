@@ -106,6 +106,13 @@ int xfemm_fsolver_num_node_props(xfemm_fsolver *s);          /* nodeproplist.siz
 int xfemm_fsolver_num_block_props(xfemm_fsolver *s);         /* blockproplist.size() */
 int xfemm_fsolver_num_circ_props(xfemm_fsolver *s);          /* circproplist.size(), after the serial expansion */
 int xfemm_fsolver_num_block_labels(xfemm_fsolver *s);        /* labellist.size() */
+/* What fpproc's MakeMask reads of the .fem beyond the device problem's
+ * descriptor, for xfk_mag_make_mask on the kept problem: the labels' MaxArea
+ * (pi d^2 / 4 of the label's mesh size d; 0: none) into label_max_area
+ * [num_block_labels], and into block_not_air[num_block_props] 1 where a block
+ * has a non-zero hysteresis angle (<Phi_h>, <Phi_hx>, <Phi_hy>).  Either may
+ * be NULL.  1 on success. */
+int xfemm_fsolver_get_mask_inputs(xfemm_fsolver *s, double *label_max_area, unsigned char *block_not_air);
 
 /* CMMaterialProp::GetSlopes(0) (libfemm/CMaterialProp.cpp:127): processes a
  * B-H curve in place (B, H: n points) and writes the knot slopes; returns the

@@ -831,7 +831,8 @@ int xfk_pot_contour_time(xfk_problem *prob, int n_contours, const int *ptr, cons
 
 /* ---------------------------------------------------------------------------
  * Post-processing of a magnetostatic problem: the element flux density and the
- * block integrals of the reference's fpproc that need no mask
+ * block integrals of the reference's fpproc that need no mask (the masked
+ * ones, 18-23, follow below)
  * (FPProc::GetElementB, fpproc.cpp:2970-3082; FPProc::BlockIntegral, 3642-4092;
  * CMMaterialProp::DoEnergy / DoCoEnergy, CMaterialProp.cpp:595-677), of a
  * problem made by xfk_problem_create, planar or axisymmetric, after
@@ -868,8 +869,10 @@ int xfk_pot_contour_time(xfk_problem *prob, int n_contours, const int *ptr, cons
  * 17 coenergy, 24 moment of inertia, 25 centroid (re x, im y; 0 / 0 = NaN with
  * nothing selected).  0 for every other type: 3, 13, 14 and 16 are 0 at
  * Frequency 0 in the reference as well; 4 (resistive losses) and 6 (total
- * losses) are not built; 18-23 need the mask.
- * xfk_mag_block_integral: one type into out2[2]; types 18-23 are refused.
+ * losses) are not built; 18-23 (below) are filled when the problem holds the
+ * mask of this very selection, and are 0 otherwise.
+ * xfk_mag_block_integral: one type into out2[2]; a type in 18-23 without the
+ * mask of this very selection is refused (XFK_ERR_ARG, naming xfk_mag_make_mask).
  * xfk_mag_time: HIP-event ms of the element-B launch (ms[0]) and of the
  * integral launch with its sum, every label selected (ms[1]): the median of
  * `repeats` runs after a warm-up.
@@ -880,6 +883,56 @@ int xfk_mag_element_b(xfk_problem *prob, double *B1, double *B2);
 int xfk_mag_block_integrals(xfk_problem *prob, const unsigned char *label_selected, double *out);
 int xfk_mag_block_integral(xfk_problem *prob, const unsigned char *label_selected, int type, double *out2);
 int xfk_mag_time(xfk_problem *prob, int repeats, double *ms);
+
+/* The weighted stress tensor force and torque of a magnetostatic problem:
+ * fpproc's block integrals 18-23 (fpproc.cpp:3966-4079, HenrotteVector
+ * 3614-3640) over the mask of FPProc::MakeMask (makemask.cpp:48-379,
+ * WeightingScheme 0; IsKosher 383-414; FindBoundaryEdges, fpproc.cpp:5356-5415).
+ *
+ * xfk_mag_make_mask fixes nodal values by the reference's rules in its order, a
+ * later rule overwriting an earlier one (free nodes -1): the ends of exterior
+ * edges 0 (an edge no other element around its first node shares, the rings
+ * of an air-gap element and periodic edges included; with an axisymmetric
+ * selection touching r < 1e-6 only where IsKosher holds); the nodes of
+ * selected elements 1 and of unselected elements that are not air 0, in
+ * element order; a still-free node with a point property 0.  A block is not
+ * air when mu_x != 1, mu_y != 1, BHpoints != 0, LamType != 0, H_c != 0,
+ * J_re != 0, Cduct != 0 or block_not_air[block] != 0 (one byte per block, may
+ * be NULL: the descriptor carries no hysteresis angles Theta_hn / hx / hy, a
+ * caller who knows one to be non-zero says so here); a label in a circuit is
+ * not air.  The reference matches the input geometry's points to mesh nodes
+ * by their coordinates; here a node carries a point property when its
+ * descriptor marker is >= 0.  An unselected element that is not air with a
+ * node not fixed at 0 refuses the selection (XFK_ERR_ARG, the reference's
+ * two-line message); the problem stays usable.  The Laplacian, weighted per
+ * element by sqrt(label_max_area[label]) (sqrt of the element's area where that
+ * is <= 0 or label_max_area is NULL), is formed in the problem's length units,
+ * planar for both problem types, and solved by the AMG-PCG to the problem's
+ * Precision on an auxiliary problem over the mesh's connectivity (no periodic
+ * pairs, no air-gap elements, no circuits); the result is thresholded at 0.5.
+ * A solve, xfk_mag_set_solution and a new xfk_mag_make_mask drop the mask.
+ *
+ * With the mask of the very selection passed, xfk_mag_block_integrals fills
+ * and xfk_mag_block_integral answers, summed over ALL elements in a fixed
+ * order (a call repeats bit for bit): 18 / 19 the x (r) / y (z) force, N;
+ * 20 / 21 their "2x" parts, which the reference evaluates at Frequency 0 as
+ * well; 22 / 23 the torque about the origin and its 2x part, N m.  18, 20, 22
+ * and 23 are 0 on an axisymmetric problem.  Asked singly
+ * (xfk_mag_block_integral), they are answered whatever the selected labels'
+ * blocks are: the LamType > 2 and nonlinear-magnet refusals above concern the
+ * energy integrals, which xfk_mag_block_integrals makes in the same pass.
+ *
+ * xfk_mag_get_mask: W[n_nodes] the solved values, msk[n_nodes] the 0 / 1 mask
+ * (either may be NULL).  xfk_mag_mask_info: the layout of xfk_pot_mask_info.
+ * xfk_mag_mask_problem: the auxiliary problem (owned by prob), for xfk_get_csr.
+ * xfk_mag_stress_time: HIP-event ms of the launch of types 18-23 with its sum,
+ * the median of `repeats` runs after a warm-up. */
+int xfk_mag_make_mask(xfk_problem *prob, const unsigned char *label_selected, const double *label_max_area,
+                      const unsigned char *block_not_air);
+int xfk_mag_get_mask(xfk_problem *prob, double *W, double *msk);
+int xfk_mag_mask_info(xfk_problem *prob, double *out9);
+int xfk_mag_mask_problem(xfk_problem *prob, xfk_problem **aux);
+int xfk_mag_stress_time(xfk_problem *prob, int repeats, double *ms);
 
 /* Diagnostics of the AMG hierarchy (single device), for tests; not part of the
  * interface a caller should build on.  A probe holds one hierarchy built from

@@ -250,6 +250,17 @@ int xfemm_fsolver_num_circ_props(xfemm_fsolver *h) { return h ? (int)h->s.circpr
 
 int xfemm_fsolver_num_block_labels(xfemm_fsolver *h) { return h ? (int)h->s.labellist.size() : -1; }
 
+int xfemm_fsolver_get_mask_inputs(xfemm_fsolver *h, double *label_max_area, unsigned char *block_not_air)
+{
+    if (!h) return 0;
+    for (size_t k = 0; label_max_area && k < h->s.labellist.size(); ++k) label_max_area[k] = h->s.labellist[k].MaxArea;
+    for (size_t k = 0; block_not_air && k < h->s.blockproplist.size(); ++k) {
+        const auto &m = h->s.blockproplist[k];
+        block_not_air[k] = (m.Theta_hn != 0) || (m.Theta_hx != 0) || (m.Theta_hy != 0);
+    }
+    return 1;
+}
+
 int xfemm_bh_get_slopes(int n, double *B, double *H, double *slope, int lam_type, double lam_fill, double *mu_x)
 {
     if (n < 2 || !B || !H || !slope) return 0;

@@ -2414,6 +2414,8 @@ int build_local(const xfk_problem_desc *d, const GlobalPrep &G, const PartPlan *
         P->mag_ext_user[0] = d->ext_ro;
         P->mag_ext_user[1] = d->ext_ri;
         P->mag_ext_user[2] = d->ext_zo;
+        P->mag_has_point.assign(d->n_nodes, 0);
+        for (int i = 0; i < d->n_nodes && d->marker; ++i) P->mag_has_point[i] = d->marker[i] >= 0;
     }
     P->nblocks = d->n_blocks;
     P->nlabels = (int)nlab;
@@ -2634,7 +2636,8 @@ int static2d_run(xfk_problem *P, int flags, xfk_result *res)
     int rc = XFK_OK;
     float ms = 0;
     if (P->comm && (rc = P->comm->solve_boundary()) != XFK_OK) return rc;
-    P->mag_A_ready = false;   // (xfk_magpost.hip: its A no longer belongs to V)
+    P->mag_A_ready = false;   // (xfk_magpost.hip: its A no longer belongs to V,
+    P->mask_ready = false;    //  nor does its mask: the reference clears bHasMask with a new solution)
     P->pcg_tol = 0;
     P->pcg_tol_rel = 0;
     P->time_spmv = (flags & XFK_TIME_SPMV) != 0;

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <cstdlib>
 #include <map>
@@ -622,11 +623,13 @@ struct xfk_problem {
     xfk::DBuf<int> pp_pel;                       // ... and the element of each point
 
     // the weighted stress tensor mask of an electrostatic problem
-    // (PostProcessor::makeMask, xfk_postproc.hip): a Laplace problem of its own
+    // (PostProcessor::makeMask, xfk_postproc.hip) or of a magnetostatic one
+    // (FPProc::MakeMask, xfk_magpost.hip): a Laplace problem of its own
     // on the mesh's connectivity, kept in an auxiliary problem (mask_aux: no
     // conductors, no periodic pairs, coordinates in user units) that is created
-    // at the first xfk_pot_make_mask and destroyed with this one.  The mask
-    // follows the solution like the fields do (pp_invalidate)
+    // at the first xfk_pot_make_mask / xfk_mag_make_mask and destroyed with
+    // this one.  The mask follows the solution like the fields do
+    // (pp_invalidate; static2d_run and xfk_mag_set_solution)
     std::vector<unsigned char> pot_has_point;    // host, N: the node carries a point property (marker >= 0)
     xfk_problem *mask_aux = nullptr;
     bool mask_ready = false, mask_ext_ready = false;
@@ -680,6 +683,10 @@ struct xfk_problem {
     xfk::DBuf<double> mag_B;                     // 2 NE: B1 then B2 (xfk_mag_element_b)
     xfk::DBuf<double> mag_part;                  // block-integral partials and sums
     xfk::DBuf<char> mag_lab;                     // the per-label table of the last block integral (MagLabel)
+    // ... its weighted stress tensor mask (the mask_ group above holds the rest)
+    std::vector<unsigned char> mag_has_point;    // host, N: the node carries a point property (marker >= 0)
+    xfk::DBuf<int> mag_n2e_ptr, mag_n2e;         // node -> elements of p_raw, ascending
+    xfk::DBuf<unsigned char> mag_mlab;           // per entry of the label table: selected, then not air
 
     // live SpMV launch timing (XFK_TIME_SPMV)
     bool time_spmv = false;
@@ -788,6 +795,21 @@ void launch_electro_rows(hipStream_t s, xfk_problem *P);
 void launch_heat_rows(hipStream_t s, xfk_problem *P);
 // xfk_postproc.hip: the same with the element of the weighted stress tensor mask (an auxiliary problem, P->mask)
 void launch_mask_rows(hipStream_t s, xfk_problem *P);
+// xfk_postproc.hip, shared by the electrostatic and the magnetostatic mask (xfk_magpost.hip):
+// the mask's auxiliary problem of P over a mesh in user units (lab: one entry per label of lbl), once
+int mask_aux_create(xfk_problem *P, const std::vector<double> &x, const std::vector<double> &y,
+                    const std::vector<int> &p, const std::vector<int> &lbl, const std::vector<PotLabel> &lab,
+                    int length_units);
+// its solve from P->mask_lv and P->mask_area, thresholded into P->mask_msk
+int mask_aux_solve(xfk_problem *P, xfk_result *res);
+void mask_set_info(xfk_problem *P, const xfk_result &res, double ms_create, double ms_rules, double ms_total);
+int launch_mask_exterior(hipStream_t s, int N, int NE, const int *p, const int *n2e_ptr, const int *n2e,
+                         unsigned char *ext);
+// wall-clock milliseconds since t0
+inline double wall_ms(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 // the integrals of the prescribed-value conductors from the solution in V, into the host conductor tables
 int electro_conductor_integrals(xfk_problem *P);
 int heat_conductor_integrals(xfk_problem *P);

@@ -1,6 +1,7 @@
 // Post-processing of a magnetostatic problem on the device: the element flux
-// density and the volume integrals of the reference's fpproc that need no
-// mask, for MI355X (gfx950).  Frequency 0 only, planar and axisymmetric.
+// density, the volume integrals of the reference's fpproc that need no mask,
+// and the weighted stress tensor force and torque over its mask, for MI355X
+// (gfx950).  Frequency 0 only, planar and axisymmetric.
 //
 //   element B         FPProc::GetElementB (fpproc.cpp:2970-3082)
 //   J and A           FPProc::GetJA (3495-3578), PlnInt / AxiInt (3580-3612),
@@ -9,6 +10,10 @@
 //                     DoCoEnergy (CMaterialProp.cpp:488-519, 537-677)
 //   block integrals   FPProc::BlockIntegral types 0 1 2 5 7 8 9 10 11 12 15 17
 //                     24 25 (3642-4092)
+//   the mask          FPProc::MakeMask, IsKosher (makemask.cpp:48-414),
+//                     FindBoundaryEdges (fpproc.cpp:5356-5415)
+//   force and torque  HenrotteVector (3614-3640), BlockIntegral types 18-23
+//                     (3966-4079)
 //
 // fpproc works in the problem's own length units with LengthConv[] to metres;
 // the solver in cm.  The coordinates are divided back by the solver's unit once
@@ -246,6 +251,15 @@ struct MagElem {
     int lbl;
 };
 
+// AECF (fpproc.cpp:5286-5304) of an element with centroid (cx, cy)
+template <bool AXI>
+__device__ __forceinline__ double mag_aecf(const MagArgs &M, const MagLabel &lab, double cx, double cy)
+{
+    if (!(AXI && lab.external)) return 1.;
+    const double q = mag_cabs(cx, cy - M.ext_zo);
+    return (q * q * M.ext_ri) / (M.ext_ro * M.ext_ro * M.ext_ro);
+}
+
 __device__ __forceinline__ void mag_load(const MagArgs &M, int e, MagElem &E)
 {
 #pragma unroll
@@ -342,12 +356,7 @@ __device__ __forceinline__ void mag_integrands(const MagArgs &M, const MagElem &
     }
     const double av = AXI ? a * (2. * kPI * R) : a * Depth;   // the element's volume
     const double ones[3] = {1., 1., 1.};
-    // AECF (fpproc.cpp:5286-5304)
-    double aecf = 1.;
-    if (AXI && lab.external) {
-        const double q = mag_cabs(cx, cy - M.ext_zo);
-        aecf = (q * q * M.ext_ri) / (M.ext_ro * M.ext_ro * M.ext_ro);
-    }
+    const double aecf = mag_aecf<AXI>(M, lab, cx, cy);
 
     // 0: A.J
     v[MS_AJ] = AXI ? mag_axi_int(a, A, Jn, rr) : mag_pln_int(a, A, Jn) * Depth;
@@ -438,6 +447,162 @@ __global__ void __launch_bounds__(kPotQBlock) k_mag_integrands(int NE, MagArgs M
     block_sums<kMagSums>(v, part);
 }
 
+// --- the weighted stress tensor mask (FPProc::MakeMask, makemask.cpp:48-379) ---
+//
+// WeightingScheme 0.  The rules that fix nodal values are independent per node
+// apart from their order, so a thread per node applies them in the reference's
+// order; the Laplace problem is the one of xfk_postproc.hip (mask_aux_create,
+// MaskPhys), solved on an auxiliary problem over the caller's connectivity.
+
+struct MagMaskArgs {
+    const double *x;               // user length units
+    const int *p, *lbl;
+    const int *n2e_ptr, *n2e;      // node -> elements of p, ascending
+    const unsigned char *mlab;     // per entry of the label table: selected, then not air (lblflag)
+    const unsigned char *ext;      // the node ends an exterior edge (FindBoundaryEdges, fpproc.cpp:5356-5415)
+    const unsigned char *point;    // the node carries a point property
+    int axi;
+};
+
+// bOnAxis (makemask.cpp:94-106): a selected element with a node at r < 1e-6;
+// flag[0] (zeroed by the caller) is set
+__global__ void __launch_bounds__(kBlock) k_mag_mask_on_axis(int NE, MagMaskArgs A, int *__restrict__ flag)
+{
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= NE || !A.mlab[2 * A.lbl[e]]) return;
+    bool on = false;
+    for (int j = 0; j < 3; ++j) on |= A.x[A.p[3 * e + j]] < 1.e-6;
+    if (on) flag[0] = 1;
+}
+
+// L.V of makemask.cpp:136-201, one thread per node; -1: free
+__global__ void __launch_bounds__(kBlock) k_mag_mask_fix(int N, MagMaskArgs A, const int *__restrict__ flag,
+                                                         double *__restrict__ lv)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    const int l0 = A.n2e_ptr[i], l1 = A.n2e_ptr[i + 1];
+    double v = -1.;
+    // the ends of exterior edges; with the selection on the axis only where IsKosher (makemask.cpp:383-414)
+    if (A.ext[i]) {
+        bool kosher = true;
+        if (flag[0] && A.axi && !(A.x[i] > 1.e-6)) {
+            int score = 0;
+            for (int m = l0; m < l1; ++m)
+                for (int j = 0; j < 3; ++j) {
+                    const int n = A.p[3 * A.n2e[m] + j];
+                    if ((n != i) && (A.x[n] < 1.e-6)) score++;
+                }
+            kosher = !(score > 1);
+        }
+        if (kosher) v = 0.;
+    }
+    // the nodes of selected elements 1, of unselected elements that are not
+    // air 0, in element order: the highest-numbered such element decides
+    int last = -1;
+    bool last_sel = false;
+    for (int m = l0; m < l1; ++m) {
+        const int e = A.n2e[m];
+        if (e < last) continue;
+        const unsigned char *f = A.mlab + 2 * A.lbl[e];
+        if (f[0] || f[1]) {
+            last = e;
+            last_sel = f[0] != 0;
+        }
+    }
+    if (last >= 0) v = last_sel ? 1. : 0.;
+    // a still-free node with a point property
+    if (A.point[i] && (v < 0)) v = 0.;
+    lv[i] = v;
+}
+
+// the consistency check (makemask.cpp:233-254): an unselected element that is
+// not air with a node not fixed at exactly 0 sets flag[1]
+__global__ void __launch_bounds__(kBlock) k_mag_mask_valid(int NE, MagMaskArgs A, const double *__restrict__ lv,
+                                                           int *__restrict__ flag)
+{
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= NE) return;
+    const unsigned char *f = A.mlab + 2 * A.lbl[e];
+    if (f[0] || !f[1]) return;
+    int k = 0;
+    for (int j = 0; j < 3; ++j)
+        if (lv[A.p[3 * e + j]] == 0) k++;
+    if (k < 3) flag[1] = 1;
+}
+
+// BlockIntegral types 18-23 (fpproc.cpp:3966-4079) with HenrotteVector
+// (3614-3640) at Frequency 0: one thread per element over ALL elements,
+// whatever the selection; per workgroup the six sums in the order 18 .. 23
+// into part.  B1 and B2 are real, so the reference's complex products reduce
+// to the real ones written here, operation by operation.
+enum { MW_FX, MW_FY, MW_FX2, MW_FY2, MW_T, MW_T2, kMagStressSums };
+
+template <bool AXI>
+__global__ void __launch_bounds__(kPotQBlock) k_mag_stress(int NE, MagArgs M, const double *__restrict__ msk,
+                                                           double *__restrict__ part)
+{
+    const int e = blockIdx.x * kPotQBlock + threadIdx.x;
+    double v[kMagStressSums];
+#pragma unroll
+    for (int c = 0; c < kMagStressSums; ++c) v[c] = 0.;
+    if (e < NE) {
+        MagElem E;
+        mag_load(M, e, E);
+        const MagLabel lab = M.labels[E.lbl];
+        const double lc = M.lc, muo = kMUO;
+        double B1, B2;
+        mag_element_b<AXI>(lc, E.X, E.Y, E.A, B1, B2);
+        double b[3], c[3], m[3];
+        b[0] = E.Y[1] - E.Y[2]; b[1] = E.Y[2] - E.Y[0]; b[2] = E.Y[0] - E.Y[1];
+        c[0] = E.X[2] - E.X[1]; c[1] = E.X[0] - E.X[2]; c[2] = E.X[1] - E.X[0];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) m[j] = msk[M.p[3 * e + j]];
+        const double da = (b[0] * c[1] - b[1] * c[0]);
+        // HenrotteVector
+        double hr = 0., hi = 0.;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            hr -= (m[j] * b[j]) / (da * lc);
+            hi -= (m[j] * c[j]) / (da * lc);
+        }
+        double a = (da / 2.) * M.lc2;
+        double cx = 0., cy = 0.;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            cx += E.X[j] / 3.;
+            cy += E.Y[j] / 3.;
+        }
+        if (AXI) {
+            const double r0 = E.X[0] * lc, r1 = E.X[1] * lc, r2 = E.X[2] * lc;
+            const double R = (r0 + r1 + r2) / 3.;
+            a *= (2. * kPI * R);
+        } else a *= M.depth;
+        const double aecf = mag_aecf<AXI>(M, lab, cx, cy);
+        // (cases 18 19 22 write 2. * Re(B1 * conj(B2)), cases 20 21 23 2. * B1 * B2)
+        const double d12 = (B1 * B1) - (B2 * B2), d21 = (B2 * B2) - (B1 * B1);
+        const double bb = 2. * (B1 * B2), b2 = 2. * B1 * B2;
+        const double F1 = (d12 * hr + bb * hi) / (2. * muo), F2 = (d21 * hi + bb * hr) / (2. * muo);
+        const double G1 = (d12 * hr + b2 * hi) / (4. * muo), G2 = (d21 * hi + b2 * hr) / (4. * muo);
+        if (!AXI) {
+            v[MW_FX] = a * (F1 * aecf);
+            v[MW_FX2] = (a * G1) * aecf;
+            // the torque about the origin: the centroid in metres
+            double tr = 0., ti = 0.;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                tr += (E.X[j] * lc) / 3.;
+                ti += (E.Y[j] * lc) / 3.;
+            }
+            v[MW_T] = a * ((tr * F2 - ti * F1) * aecf);
+            v[MW_T2] = (a * (tr * G2 - ti * G1)) * aecf;
+        }
+        v[MW_FY] = a * (F2 * aecf);
+        v[MW_FY2] = (a * G2) * aecf;
+    }
+    block_sums<kMagStressSums>(v, part);
+}
+
 // user-unit coordinates
 static __global__ void k_mag_xy(int N, const double *__restrict__ x, const double *__restrict__ y, double u,
                                 double *__restrict__ mx, double *__restrict__ my)
@@ -491,18 +656,26 @@ static int mag_entry(xfk_problem *P, F &&body)
     }
 }
 
-// coordinates in user units (once) and A of the solution in V (after a solve)
+// coordinates in user units (once)
+static int mag_prepare_xy(xfk_problem *P)
+{
+    const int N = P->N, G = (N + kBlock - 1) / kBlock;
+    if (P->mag_xy_ready) return XFK_OK;
+    XFK_CHECK(P->mag_x.alloc((size_t)N));
+    XFK_CHECK(P->mag_y.alloc((size_t)N));
+    k_mag_xy<<<G, kBlock, 0, P->stream>>>(N, P->x.p, P->y.p, kMagUnitCm[P->length_units], P->mag_x.p, P->mag_y.p);
+    XFK_CHECK(hipGetLastError());
+    P->mag_xy_ready = true;
+    return XFK_OK;
+}
+
+// ... and A of the solution in V (after a solve)
 static int mag_prepare(xfk_problem *P)
 {
     hipStream_t s = P->stream;
     const int N = P->N, G = (N + kBlock - 1) / kBlock;
-    if (!P->mag_xy_ready) {
-        XFK_CHECK(P->mag_x.alloc((size_t)N));
-        XFK_CHECK(P->mag_y.alloc((size_t)N));
-        k_mag_xy<<<G, kBlock, 0, s>>>(N, P->x.p, P->y.p, kMagUnitCm[P->length_units], P->mag_x.p, P->mag_y.p);
-        XFK_CHECK(hipGetLastError());
-        P->mag_xy_ready = true;
-    }
+    const int rc = mag_prepare_xy(P);
+    if (rc != XFK_OK) return rc;
     if (!P->mag_A_ready) {
         XFK_REQUIRE(P->symbolic_ready && P->V.p, XFK_ERR_ARG,
                     "no solution yet (solve the problem or xfk_mag_set_solution)");
@@ -539,9 +712,10 @@ static MagArgs mag_args(const xfk_problem *P)
 // The per-label table of a selection: the label's block, direction and flags
 // from the problem's tables, its circuit's Case / J / dVolts from the solve's
 // circuit results -- the columns FSolver writes to the .ans label lines
-// (WriteStatic2D) and fpproc reads back (fpproc.cpp:1289-1308).  Refuses a
-// selected label whose energy this post-processor does not compute.
-static int mag_labels(xfk_problem *P, const unsigned char *sel)
+// (WriteStatic2D) and fpproc reads back (fpproc.cpp:1289-1308).  With energy
+// set, refuses a selected label whose energy this post-processor does not
+// compute (types 18-23 read B and the mask alone: their callers clear it).
+static int mag_labels(xfk_problem *P, const unsigned char *sel, bool energy = true)
 {
     hipStream_t s = P->stream;
     const size_t nlab = P->mag_hlab.size();
@@ -565,7 +739,7 @@ static int mag_labels(xfk_problem *P, const unsigned char *sel)
             if (C.ccase == 0) o.dV = C.dV;
             else o.J = C.J;
         }
-        if (!o.sel) continue;
+        if (!o.sel || !energy) continue;
         XFK_REQUIRE(B.LamType <= 2, XFK_ERR_UNSUPPORTED,
                     "a selected label's block has LamType > 2 (a wound region with proximity effects): its energy "
                     "needs the label's effective conductivity and fill factor (GetFillFactor), which are not built");
@@ -590,6 +764,161 @@ static int mag_launch_integrals(xfk_problem *P, const MagArgs &M)
     return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
 }
 
+// --- the weighted stress tensor mask: host side --------------------------------
+
+static const char *const kMagMaskInvalid =
+    "The selected region is invalid. A valid selection\ncannot abut a region which is not free space.";
+
+// What the mask reads of the mesh, once: the node -> element lists over the
+// caller's numbering (ascending: the reference's element order), the exterior
+// edges, the point marks, and the auxiliary problem over the same connectivity
+// in user units
+static int mag_mask_mesh(xfk_problem *P, double &ms_create)
+{
+    ms_create = 0.;
+    if (P->mask_ext_ready && P->mask_aux) return XFK_OK;
+    hipStream_t s = P->stream;
+    const int N = P->N, NE = P->NE;
+    std::vector<double> x(N), y(N);
+    std::vector<int> p(3 * (size_t)NE), lbl(NE);
+    XFK_CHECK(d2h(x.data(), P->mag_x.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(y.data(), P->mag_y.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(p.data(), P->p_raw.p, sizeof(int) * 3 * (size_t)NE, s));
+    XFK_CHECK(d2h(lbl.data(), P->lbl_raw.p, sizeof(int) * NE, s));
+    std::vector<int> ptr(N + 1, 0);
+    for (size_t k = 0; k < 3 * (size_t)NE; ++k) ptr[p[k] + 1]++;
+    for (int i = 0; i < N; ++i) ptr[i + 1] += ptr[i];
+    std::vector<int> lst(3 * (size_t)NE), fill(ptr.begin(), ptr.end() - 1);
+    for (int e = 0; e < NE; ++e)
+        for (int j = 0; j < 3; ++j) lst[fill[p[3 * (size_t)e + j]]++] = e;
+    XFK_CHECK(upload(P->mag_n2e_ptr, ptr.data(), ptr.size(), s));
+    XFK_CHECK(upload(P->mag_n2e, lst.data(), lst.size(), s));
+    XFK_CHECK(upload(P->mask_point, P->mag_has_point.data(), (size_t)N, s));
+    XFK_CHECK(P->mask_ext.alloc((size_t)N));
+    int rc = launch_mask_exterior(s, N, NE, P->p_raw.p, P->mag_n2e_ptr.p, P->mag_n2e.p, P->mask_ext.p);
+    if (rc != XFK_OK) return rc;
+    XFK_CHECK(hipStreamSynchronize(s));   // (ptr and lst leave scope)
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<PotLabel> lab(std::max<size_t>(1, P->mag_hlab.size()), PotLabel{0, 0});
+    if ((rc = mask_aux_create(P, x, y, p, lbl, lab, P->length_units)) != XFK_OK) return rc;
+    ms_create = wall_ms(t0);
+    P->mask_ext_ready = true;
+    return XFK_OK;
+}
+
+// FPProc::MakeMask for the selection (one byte per label); max_area, one double
+// per label, and not_air, one byte per block, may be null
+static int mag_make_mask(xfk_problem *P, const unsigned char *sel, const double *max_area,
+                         const unsigned char *not_air)
+{
+    XFK_REQUIRE(sel, XFK_ERR_ARG, "null selection mask (one byte per block label)");
+    P->mask_ready = false;
+    const auto t_all = std::chrono::steady_clock::now();
+    int rc = mag_prepare_xy(P);
+    if (rc != XFK_OK) return rc;
+    hipStream_t s = P->stream;
+    const int N = P->N, NE = P->NE;
+    const size_t nlab = P->mag_hlab.size();
+    double ms_create = 0.;
+    if ((rc = mag_mask_mesh(P, ms_create)) != XFK_OK) return rc;
+
+    // the air test per block and per label (makemask.cpp:108-132), the labels' MaxArea
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<unsigned char> mlab(2 * std::max<size_t>(1, nlab), 0);
+    std::vector<double> area(std::max<size_t>(1, nlab), 0.);
+    for (size_t k = 0; k < nlab; ++k) {
+        const DevLabel &L = P->mag_hlab[k];
+        const DevBlock &B = P->mag_hblk[L.blk];
+        int f = 0;
+        if ((B.mu_x != 1) || (B.mu_y != 1)) f = 1;
+        if (B.BHpoints != 0) f = 1;
+        if (B.LamType != 0) f = 1;
+        if (B.H_c != 0) f = 1;
+        if (B.J_re != 0) f = 1;
+        if (B.Cduct != 0) f = 1;
+        if (not_air && not_air[L.blk]) f = 1;
+        if (L.in_circuit >= 0) f = 1;
+        mlab[2 * k] = sel[P->mag_lab_orig[k]] ? 1 : 0;
+        mlab[2 * k + 1] = (unsigned char)f;
+        if (max_area) area[k] = max_area[P->mag_lab_orig[k]];
+    }
+    XFK_CHECK(upload(P->mag_mlab, mlab.data(), mlab.size(), s));
+    XFK_CHECK(upload(P->mask_area, area.data(), area.size(), s));
+    XFK_CHECK(P->mask_flag.alloc(2));
+    XFK_CHECK(P->mask_lv.alloc((size_t)N));
+    XFK_CHECK(P->mask_msk.alloc((size_t)N));
+    XFK_CHECK(hipMemsetAsync(P->mask_flag.p, 0, 2 * sizeof(int), s));
+    MagMaskArgs A = {};
+    A.x = P->mag_x.p;
+    A.p = P->p_raw.p;
+    A.lbl = P->lbl_raw.p;
+    A.n2e_ptr = P->mag_n2e_ptr.p;
+    A.n2e = P->mag_n2e.p;
+    A.mlab = P->mag_mlab.p;
+    A.ext = P->mask_ext.p;
+    A.point = P->mask_point.p;
+    A.axi = P->axi ? 1 : 0;
+    const int GE = (NE + kBlock - 1) / kBlock;
+    if (P->axi) k_mag_mask_on_axis<<<GE, kBlock, 0, s>>>(NE, A, P->mask_flag.p);
+    k_mag_mask_fix<<<(N + kBlock - 1) / kBlock, kBlock, 0, s>>>(N, A, P->mask_flag.p, P->mask_lv.p);
+    k_mag_mask_valid<<<GE, kBlock, 0, s>>>(NE, A, P->mask_lv.p, P->mask_flag.p);
+    XFK_CHECK(hipGetLastError());
+    int flag[2] = {0, 0};
+    XFK_CHECK(d2h(flag, P->mask_flag.p, sizeof(flag), s));   // (the stream is idle after this: mlab and area were read)
+    XFK_REQUIRE(!flag[1], XFK_ERR_ARG, kMagMaskInvalid);
+    const double ms_rules = wall_ms(t0);
+
+    xfk_result res{};
+    if ((rc = mask_aux_solve(P, &res)) != XFK_OK) return rc;
+    P->mask_sel.assign(sel, sel + P->mag_nlabels);
+    P->mask_ready = true;
+    mask_set_info(P, res, ms_create, ms_rules, wall_ms(t_all));
+    return XFK_OK;
+}
+
+// the mask P holds was made for the selection sel
+static bool mag_mask_matches(const xfk_problem *P, const unsigned char *sel)
+{
+    if (!P->mask_ready || !sel || (int)P->mask_sel.size() != P->mag_nlabels) return false;
+    for (size_t k = 0; k < P->mask_sel.size(); ++k)
+        if ((P->mask_sel[k] != 0) != (sel[k] != 0)) return false;
+    return true;
+}
+
+// mag_part: the partials and sums of the mask-free integrals, then those of
+// the weighted stress tensor ones
+static size_t mag_part_size(int G) { return (kMagSums + kMagStressSums) * ((size_t)G + 1); }
+static double *mag_stress_part(xfk_problem *P, int G) { return P->mag_part.p + kMagSums * ((size_t)G + 1); }
+
+// the six sums of k_mag_stress over all elements, in a fixed order
+static int mag_launch_stress(xfk_problem *P, const MagArgs &M)
+{
+    hipStream_t s = P->stream;
+    const int NE = P->NE, G = (NE + kPotQBlock - 1) / kPotQBlock;
+    double *part = mag_stress_part(P, G), *sums = part + kMagStressSums * (size_t)G;
+    if (P->axi) k_mag_stress<true><<<G, kPotQBlock, 0, s>>>(NE, M, P->mask_msk.p, part);
+    else k_mag_stress<false><<<G, kPotQBlock, 0, s>>>(NE, M, P->mask_msk.p, part);
+    k_pot_sum<kMagStressSums><<<1, kPotQBlock, 0, s>>>(G, part, sums);
+    return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
+}
+
+// types 18-23 alone into w[6], of the selection whose mask P holds: whatever
+// the selected labels' blocks are
+static int mag_stress_integrals(xfk_problem *P, const unsigned char *sel, double *w)
+{
+    int rc = mag_labels(P, sel, false);
+    if (rc == XFK_OK) rc = mag_prepare(P);
+    if (rc != XFK_OK) return rc;
+    const int G = (P->NE + kPotQBlock - 1) / kPotQBlock;
+    XFK_CHECK(P->mag_part.alloc(mag_part_size(G)));
+    if ((rc = mag_launch_stress(P, mag_args(P))) != XFK_OK) {
+        set_error("block integral launch failed");
+        return rc;
+    }
+    XFK_CHECK(d2h(w, mag_stress_part(P, G) + kMagStressSums * (size_t)G, sizeof(double) * kMagStressSums, P->stream));
+    return XFK_OK;
+}
+
 // every type as (re, im) pairs indexed by inttype
 static int mag_block_integrals(xfk_problem *P, const unsigned char *sel, double *out)
 {
@@ -599,13 +928,16 @@ static int mag_block_integrals(xfk_problem *P, const unsigned char *sel, double 
     if (rc == XFK_OK) rc = mag_prepare(P);
     if (rc != XFK_OK) return rc;
     const int G = (P->NE + kPotQBlock - 1) / kPotQBlock;
-    XFK_CHECK(P->mag_part.alloc(kMagSums * ((size_t)G + 1)));
-    if ((rc = mag_launch_integrals(P, mag_args(P))) != XFK_OK) {
+    XFK_CHECK(P->mag_part.alloc(mag_part_size(G)));
+    const bool stress = mag_mask_matches(P, sel);   // types 18-23: with the mask of this very selection
+    const MagArgs M = mag_args(P);
+    if ((rc = mag_launch_integrals(P, M)) != XFK_OK || (stress && (rc = mag_launch_stress(P, M)) != XFK_OK)) {
         set_error("block integral launch failed");
         return rc;
     }
-    double h[kMagSums];
+    double h[kMagSums], w[kMagStressSums];
     XFK_CHECK(d2h(h, P->mag_part.p + kMagSums * (size_t)G, sizeof(h), P->stream));
+    if (stress) XFK_CHECK(d2h(w, mag_stress_part(P, G) + kMagStressSums * (size_t)G, sizeof(w), P->stream));
     for (int k = 0; k < 2 * kMagTypes; ++k) out[k] = 0.;
     out[2 * 0] = h[MS_AJ];
     out[2 * 1] = h[MS_A];
@@ -623,6 +955,7 @@ static int mag_block_integrals(xfk_problem *P, const unsigned char *sel, double 
     // the centroid: the two sums over BlockIntegral(5) (0 / 0 with nothing selected)
     out[2 * 25] = h[MS_CX] / h[MS_AREA];
     out[2 * 25 + 1] = h[MS_CY] / h[MS_AREA];
+    for (int k = 0; stress && k < kMagStressSums; ++k) out[2 * (18 + k)] = w[k];
     return XFK_OK;
 }
 
@@ -637,6 +970,7 @@ int xfk_mag_set_solution(xfk_problem *P, const double *A)
     return mag_entry(P, [&]() -> int {
         XFK_REQUIRE(A, XFK_ERR_ARG, "null solution");
         P->mag_A_ready = false;
+        P->mask_ready = false;   // (the reference clears bHasMask with a new solution)
         XFK_CHECK(P->mag_A.alloc((size_t)P->N));
         XFK_CHECK(hipMemcpyAsync(P->mag_A.p, A, sizeof(double) * P->N, hipMemcpyHostToDevice, P->stream));
         XFK_CHECK(hipStreamSynchronize(P->stream));
@@ -684,9 +1018,18 @@ int xfk_mag_block_integral(xfk_problem *P, const unsigned char *label_selected, 
 {
     return mag_entry(P, [&]() -> int {
         XFK_REQUIRE(type >= 0 && type < kMagTypes, XFK_ERR_ARG, "block integral type out of range (0-25)");
-        XFK_REQUIRE(type < 18 || type > 23, XFK_ERR_UNSUPPORTED,
-                    "block integral types 18-23 (weighted stress tensor, Henrotte) need the mask, which is not built");
+        XFK_REQUIRE(type < 18 || type > 23 || mag_mask_matches(P, label_selected), XFK_ERR_ARG,
+                    "block integral types 18-23 (weighted stress tensor force and torque) need the mask of this "
+                    "very selection: xfk_mag_make_mask");
         XFK_REQUIRE(out2, XFK_ERR_ARG, "null output");
+        if (type >= 18 && type <= 23) {
+            double w[kMagStressSums];
+            const int rc = mag_stress_integrals(P, label_selected, w);
+            if (rc != XFK_OK) return rc;
+            out2[0] = w[type - 18];
+            out2[1] = 0.;
+            return XFK_OK;
+        }
         double o[2 * kMagTypes];
         const int rc = mag_block_integrals(P, label_selected, o);
         if (rc != XFK_OK) return rc;
@@ -706,7 +1049,7 @@ int xfk_mag_time(xfk_problem *P, int repeats, double *ms)
         if (rc != XFK_OK) return rc;
         hipStream_t s = P->stream;
         const int NE = P->NE, G = (NE + kPotQBlock - 1) / kPotQBlock, GB = (NE + kBlock - 1) / kBlock;
-        XFK_CHECK(P->mag_part.alloc(kMagSums * ((size_t)G + 1)));
+        XFK_CHECK(P->mag_part.alloc(mag_part_size(G)));
         XFK_CHECK(P->mag_B.alloc(2 * (size_t)NE));
         const MagArgs M = mag_args(P);
         ScopedEvents<2> ev;
@@ -736,6 +1079,74 @@ int xfk_mag_time(xfk_problem *P, int repeats, double *ms)
         }, ms[0]);
         if (rc != XFK_OK) return rc;
         return timed([&] { return mag_launch_integrals(P, M); }, ms[1]);
+    });
+}
+
+int xfk_mag_make_mask(xfk_problem *P, const unsigned char *label_selected, const double *label_max_area,
+                      const unsigned char *block_not_air)
+{
+    return mag_entry(P, [&]() -> int { return mag_make_mask(P, label_selected, label_max_area, block_not_air); });
+}
+
+int xfk_mag_get_mask(xfk_problem *P, double *W, double *msk)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(P->mask_ready && P->mask_aux, XFK_ERR_ARG,
+                    "no mask (xfk_mag_make_mask; a new solution drops the mask)");
+        const size_t bytes = sizeof(double) * (size_t)P->N;
+        if (W) XFK_CHECK(d2h(W, P->mask_aux->V.p, bytes, P->stream));
+        if (msk) XFK_CHECK(d2h(msk, P->mask_msk.p, bytes, P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_mask_info(xfk_problem *P, double *out9)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(out9, XFK_ERR_ARG, "null output");
+        out9[0] = P->mask_ready ? 1. : 0.;
+        for (int k = 0; k < 8; ++k) out9[1 + k] = P->mask_info[k];
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_mask_problem(xfk_problem *P, xfk_problem **aux)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(aux, XFK_ERR_ARG, "null output");
+        XFK_REQUIRE(P->mask_aux && P->mask_aux->symbolic_ready, XFK_ERR_ARG, "no mask problem yet (xfk_mag_make_mask)");
+        *aux = P->mask_aux;
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_stress_time(xfk_problem *P, int repeats, double *ms)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(repeats > 0 && ms, XFK_ERR_ARG, "xfk_mag_stress_time needs repeats > 0 and its output");
+        XFK_REQUIRE(P->mask_ready, XFK_ERR_ARG, "no mask (xfk_mag_make_mask; a new solution drops the mask)");
+        int rc = mag_labels(P, P->mask_sel.data(), false);
+        if (rc == XFK_OK) rc = mag_prepare(P);
+        if (rc != XFK_OK) return rc;
+        hipStream_t s = P->stream;
+        const int G = (P->NE + kPotQBlock - 1) / kPotQBlock;
+        XFK_CHECK(P->mag_part.alloc(mag_part_size(G)));
+        const MagArgs M = mag_args(P);
+        ScopedEvents<2> ev;
+        XFK_CHECK(ev.create());
+        std::vector<double> t;
+        for (int k = 0; k <= repeats; ++k) {   // (the first a warm-up)
+            XFK_CHECK(hipEventRecord(ev[0], s));
+            if ((rc = mag_launch_stress(P, M)) != XFK_OK) return rc;
+            XFK_CHECK(hipEventRecord(ev[1], s));
+            XFK_CHECK(hipEventSynchronize(ev[1]));
+            float m = 0;
+            XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
+            if (k) t.push_back(m);
+        }
+        std::sort(t.begin(), t.end());
+        *ms = t[t.size() / 2];
+        return XFK_OK;
     });
 }
 

@@ -1481,28 +1481,17 @@ static int pp_upload_points(xfk_problem *P, int n, const double *x, const double
 
 // --- the weighted stress tensor mask: host side --------------------------------
 
-static double wall_ms(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-// The auxiliary problem of the mask: the mesh's own connectivity (pot_p: a
-// floating conductor's nodes stay apart), coordinates in user units, no
-// boundary data at all -- the element eliminates the prescribed values
-// itself.  Created once and kept with P.
-static int mask_aux_create(xfk_problem *P)
+// The auxiliary problem of the mask, owned by P (P->mask_aux): the mesh's own
+// connectivity p (a floating conductor's nodes stay apart), coordinates in
+// user units, no boundary data at all -- the element eliminates the prescribed
+// values itself.  lab: a table the length of the problem's labels (the mask's
+// element reads none of it).  Created once and kept with P.
+int xfk::mask_aux_create(xfk_problem *P, const std::vector<double> &x, const std::vector<double> &y,
+                    const std::vector<int> &p, const std::vector<int> &lbl, const std::vector<PotLabel> &lab,
+                    int length_units)
 {
     if (P->mask_aux) return XFK_OK;
-    hipStream_t s = P->stream;
     const int N = P->N, NE = P->NE;
-    std::vector<double> x(N), y(N);
-    std::vector<int> p(3 * (size_t)NE), lbl(NE);
-    std::vector<PotLabel> lab(P->pot_labels.n);
-    XFK_CHECK(d2h(x.data(), P->pp_x.p, sizeof(double) * N, s));
-    XFK_CHECK(d2h(y.data(), P->pp_y.p, sizeof(double) * N, s));
-    XFK_CHECK(d2h(p.data(), P->pot_p.p, sizeof(int) * 3 * (size_t)NE, s));
-    XFK_CHECK(d2h(lbl.data(), P->lbl_raw.p, sizeof(int) * NE, s));
-    XFK_CHECK(d2h(lab.data(), P->pot_labels.p, sizeof(PotLabel) * lab.size(), s));
     GlobalPrep G;
     G.blk.assign(1, DevBlock{});
     G.lab.assign(1, DevLabel{});
@@ -1525,7 +1514,7 @@ static int mask_aux_create(xfk_problem *P)
     md.n_blocks = 1;
     md.n_labels = (int)lab.size();
     md.precision = P->precision;
-    md.length_units = P->pot_length_units;
+    md.length_units = length_units;
     md.relax = 1.0;
     md.problem_type = XFK_PLANAR;
     xfk_problem *Q = nullptr;
@@ -1555,6 +1544,73 @@ static int mask_aux_create(xfk_problem *P)
     return XFK_OK;
 }
 
+// ... of a scalar-potential problem: from its post-processing mesh tables
+static int pot_mask_aux_create(xfk_problem *P)
+{
+    if (P->mask_aux) return XFK_OK;
+    hipStream_t s = P->stream;
+    const int N = P->N, NE = P->NE;
+    std::vector<double> x(N), y(N);
+    std::vector<int> p(3 * (size_t)NE), lbl(NE);
+    std::vector<PotLabel> lab(P->pot_labels.n);
+    XFK_CHECK(d2h(x.data(), P->pp_x.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(y.data(), P->pp_y.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(p.data(), P->pot_p.p, sizeof(int) * 3 * (size_t)NE, s));
+    XFK_CHECK(d2h(lbl.data(), P->lbl_raw.p, sizeof(int) * NE, s));
+    XFK_CHECK(d2h(lab.data(), P->pot_labels.p, sizeof(PotLabel) * lab.size(), s));
+    return mask_aux_create(P, x, y, p, lbl, lab, P->pot_length_units);
+}
+
+// The Laplace solve of the mask on P's auxiliary problem, from the fixed
+// values in P->mask_lv and the labels' MaxArea in P->mask_area: symbolic phase
+// (first call), row gather, AMG-PCG to the problem's Precision; then the
+// threshold into P->mask_msk.  Host-synchronising.
+int xfk::mask_aux_solve(xfk_problem *P, xfk_result *res)
+{
+    xfk_problem *Q = P->mask_aux;
+    hipStream_t s = P->stream;
+    const int N = P->N;
+    Q->mask_lv_p = P->mask_lv.p;
+    Q->mask_area_p = P->mask_area.p;
+    Q->precision = P->precision;
+    Q->precond = P->precond;
+    int rc;
+    {
+        ArenaScope arena_scope(&Q->arena);
+        rc = static2d_run(Q, 0, res);
+        problem_recycle(Q);
+    }
+    if (rc != XFK_OK) return rc;
+    k_mask_threshold<<<(N + kBlock - 1) / kBlock, kBlock, 0, s>>>(N, Q->V.p, P->mask_msk.p);
+    XFK_CHECK(hipGetLastError());
+    XFK_CHECK(hipStreamSynchronize(s));
+    return XFK_OK;
+}
+
+// what xfk_pot_mask_info / xfk_mag_mask_info report of the last mask
+void xfk::mask_set_info(xfk_problem *P, const xfk_result &res, double ms_create, double ms_rules, double ms_total)
+{
+    double *o = P->mask_info;
+    o[0] = (double)res.cg_iters;
+    o[1] = ms_create;
+    o[2] = ms_rules;
+    o[3] = res.ms_symbolic;
+    o[4] = res.ms_assemble;
+    o[5] = res.ms_amg_setup;
+    o[6] = res.ms_solve;
+    o[7] = ms_total;
+}
+
+// FindBoundaryEdges into ext[N] (zeroed here) for a mesh and its node -> element lists
+int xfk::launch_mask_exterior(hipStream_t s, int N, int NE, const int *p, const int *n2e_ptr, const int *n2e,
+                         unsigned char *ext)
+{
+    XFK_CHECK(hipMemsetAsync(ext, 0, (size_t)N, s));
+    k_mask_exterior<<<(3 * NE + kBlock - 1) / kBlock, kBlock, 0, s>>>(NE, p, n2e_ptr, n2e, ext);
+    XFK_CHECK(hipGetLastError());
+    return XFK_OK;
+}
+
 static const char *const kMaskInvalid =
     "The selected region is invalid. A valid selection cannot abut a region which is not free space.";
 
@@ -1576,8 +1632,7 @@ static int mask_make(xfk_problem *P, const unsigned char *sel, const unsigned ch
     const size_t nlab = P->pot_labels.n;
     auto t0 = std::chrono::steady_clock::now();
     const bool fresh = !P->mask_aux;
-    if ((rc = mask_aux_create(P)) != XFK_OK) return rc;
-    xfk_problem *Q = P->mask_aux;
+    if ((rc = pot_mask_aux_create(P)) != XFK_OK) return rc;
     const double ms_create = fresh ? wall_ms(t0) : 0.;
 
     // the fixed values and the validity of the selection
@@ -1593,9 +1648,8 @@ static int mask_make(xfk_problem *P, const unsigned char *sel, const unsigned ch
     if (!P->mask_ext_ready) {   // (the exterior edges and the point marks are the mesh's)
         XFK_CHECK(upload(P->mask_point, P->pot_has_point.data(), (size_t)N, s));
         XFK_CHECK(P->mask_ext.alloc((size_t)N));
-        XFK_CHECK(hipMemsetAsync(P->mask_ext.p, 0, (size_t)N, s));
-        k_mask_exterior<<<(3 * NE + kBlock - 1) / kBlock, kBlock, 0, s>>>(NE, P->pot_p.p, P->pp_n2e_ptr.p,
-                                                                         P->pp_n2e.p, P->mask_ext.p);
+        if ((rc = launch_mask_exterior(s, N, NE, P->pot_p.p, P->pp_n2e_ptr.p, P->pp_n2e.p, P->mask_ext.p)) != XFK_OK)
+            return rc;
         P->mask_ext_ready = true;
     }
     XFK_CHECK(P->mask_flag.alloc(2));
@@ -1615,33 +1669,11 @@ static int mask_make(xfk_problem *P, const unsigned char *sel, const unsigned ch
     XFK_REQUIRE(!flag[1], XFK_ERR_ARG, kMaskInvalid);
     const double ms_rules = wall_ms(t0);
 
-    // the Laplace solve: symbolic phase (first call), row gather, AMG-PCG to
-    // the problem's Precision
-    Q->mask_lv_p = P->mask_lv.p;
-    Q->mask_area_p = P->mask_area.p;
-    Q->precision = P->precision;
-    Q->precond = P->precond;
     xfk_result res{};
-    {
-        ArenaScope arena_scope(&Q->arena);
-        rc = static2d_run(Q, 0, &res);
-        problem_recycle(Q);
-    }
-    if (rc != XFK_OK) return rc;
-    k_mask_threshold<<<(N + kBlock - 1) / kBlock, kBlock, 0, s>>>(N, Q->V.p, P->mask_msk.p);
-    XFK_CHECK(hipGetLastError());
-    XFK_CHECK(hipStreamSynchronize(s));
+    if ((rc = mask_aux_solve(P, &res)) != XFK_OK) return rc;
     P->mask_sel.assign(sel, sel + nlab);
     P->mask_ready = true;
-    double *o = P->mask_info;
-    o[0] = (double)res.cg_iters;
-    o[1] = ms_create;
-    o[2] = ms_rules;
-    o[3] = res.ms_symbolic;
-    o[4] = res.ms_assemble;
-    o[5] = res.ms_amg_setup;
-    o[6] = res.ms_solve;
-    o[7] = wall_ms(t_all);
+    mask_set_info(P, res, ms_create, ms_rules, wall_ms(t_all));
     return XFK_OK;
 }
 

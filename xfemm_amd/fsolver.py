@@ -29,6 +29,7 @@ EXPORTED = (
     "xfemm_fsolver_set_previous_solution_file", "xfemm_fsolver_previous_solution_file", "xfemm_fsolver_ac_solver",
     "xfemm_fsolver_frequency", "xfemm_fsolver_num_line_props", "xfemm_fsolver_num_node_props",
     "xfemm_fsolver_num_block_props", "xfemm_fsolver_num_circ_props", "xfemm_fsolver_num_block_labels",
+    "xfemm_fsolver_get_mask_inputs",
     "xfemm_fsolver_set_comm", "xfemm_fsolver_num_air_gaps", "xfemm_fsolver_get_air_gap_nodes",
     "xfemm_fsolver_set_keep_problem", "xfemm_fsolver_problem",
 )
@@ -74,6 +75,7 @@ def load_library(path: str = FSOLVER_SO):
     L.xfemm_fsolver_get_stats.argtypes = [vp, C.POINTER(kernels.Result)]
     L.xfemm_fsolver_get_times.argtypes = [vp, C.POINTER(C.c_double)]
     L.xfemm_fsolver_last_error.argtypes = [vp]
+    L.xfemm_fsolver_get_mask_inputs.argtypes = [vp, dptr, C.POINTER(C.c_ubyte)]
     L.xfemm_fsolver_set_previous_solution_file.argtypes = [vp, C.c_char_p]
     L.xfemm_fsolver_previous_solution_file.argtypes = [vp]
     L.xfemm_fsolver_previous_solution_file.restype = C.c_char_p
@@ -123,6 +125,10 @@ def bh_get_slopes_ac(B, H, omega, lam_type=0, lam_fill=1.0, theta_hn=0.0, lam_d=
 class _SolvedProblem(kernels._MagPostProc):
     """A solved problem an FSolver keeps (FSolver.problem)."""
 
+    def _mag_mask_defaults(self):
+        # the labels' MaxArea and the blocks' hysteresis angles of the .fem
+        return self._owner.mask_inputs()
+
 
 class FSolver:
     """The reference FSolver workflow over the MI355X hot path."""
@@ -162,7 +168,20 @@ class FSolver:
         v._h, v._owner = C.c_void_p(h), self
         v.n_nodes, v.n_elems = self.NumNodes, self.NumEls
         v.n_labels = _lib.xfemm_fsolver_num_block_labels(self._h)
+        v.n_blocks = _lib.xfemm_fsolver_num_block_props(self._h)
         return v
+
+    def mask_inputs(self):
+        """(max_area per label, block_not_air per block) of the loaded .fem:
+        what the kept problem's make_mask / weighted_stress take by default
+        (xfemm_fsolver_get_mask_inputs)."""
+        area = np.zeros(max(1, _lib.xfemm_fsolver_num_block_labels(self._h)))
+        notair = np.zeros(max(1, _lib.xfemm_fsolver_num_block_props(self._h)), np.uint8)
+        if not _lib.xfemm_fsolver_get_mask_inputs(self._h, area.ctypes.data_as(dptr),
+                                                  notair.ctypes.data_as(C.POINTER(C.c_ubyte))):
+            raise RuntimeError("no solver")
+        return (area[:_lib.xfemm_fsolver_num_block_labels(self._h)],
+                notair[:_lib.xfemm_fsolver_num_block_props(self._h)])
 
     def __del__(self):
         try:

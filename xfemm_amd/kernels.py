@@ -68,6 +68,7 @@ EXPORTED = (
     "xfk_pot_line_integrals", "xfk_pot_line_integral", "xfk_pot_contour_samples", "xfk_pot_contour_time",
     "xfk_mag_set_solution", "xfk_mag_set_depth", "xfk_mag_element_b", "xfk_mag_block_integrals",
     "xfk_mag_block_integral", "xfk_mag_time",
+    "xfk_mag_make_mask", "xfk_mag_get_mask", "xfk_mag_mask_info", "xfk_mag_mask_problem", "xfk_mag_stress_time",
     "xfk_amg_probe_create", "xfk_amg_probe_info", "xfk_amg_probe_level_size", "xfk_amg_probe_level_csr",
     "xfk_amg_probe_tiles", "xfk_amg_probe_vector", "xfk_amg_probe_trace", "xfk_amg_probe_apply",
     "xfk_amg_probe_refresh", "xfk_amg_probe_destroy",
@@ -352,6 +353,11 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_mag_block_integrals.argtypes = [C.c_void_p, ubptr, dptr]
     L.xfk_mag_block_integral.argtypes = [C.c_void_p, ubptr, C.c_int, dptr]
     L.xfk_mag_time.argtypes = [C.c_void_p, C.c_int, dptr]
+    L.xfk_mag_make_mask.argtypes = [C.c_void_p, ubptr, dptr, ubptr]
+    L.xfk_mag_get_mask.argtypes = [C.c_void_p, dptr, dptr]
+    L.xfk_mag_mask_info.argtypes = [C.c_void_p, dptr]
+    L.xfk_mag_mask_problem.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.xfk_mag_stress_time.argtypes = [C.c_void_p, C.c_int, dptr]
     L.xfk_sort_elements.argtypes = [C.c_int, C.POINTER(C.c_uint), C.c_int, iptr]
     L.xfk_magdir_eval.argtypes = [C.c_char_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_double, dptr]
     L.xfk_lua_run.argtypes = [C.c_char_p, C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong)]
@@ -561,7 +567,8 @@ def age_element_matrix(ci: float, co: float, K: float, Ki: float) -> np.ndarray:
 
 class _MagPostProc:
     """Post-processing of a magnetostatic problem (the xfk_mag_ entry points):
-    fpproc's element flux density and its block integrals that need no mask.
+    fpproc's element flux density, its block integrals that need no mask, and
+    the weighted stress tensor force and torque (types 18-23) over its mask.
     The subclass provides _h, n_nodes, n_elems and n_labels.  A harmonic or a
     sharded problem is refused by the library with its cause."""
 
@@ -627,6 +634,97 @@ class _MagPostProc:
         _check(_lib.xfk_mag_time(self._h, int(repeats), ms.ctypes.data_as(dptr)))
         return dict(element_b=float(ms[0]), block_integrals=float(ms[1]))
 
+    # -- the weighted stress tensor force and torque (block integrals 18-23) --
+
+    def _mag_mask_args(self, selected_labels, max_area, block_not_air):
+        sel, _ = self._mag_mask(selected_labels)
+        area = None
+        if max_area is not None:
+            area = np.ascontiguousarray(max_area, dtype=np.float64)
+            if area.shape != (self.n_labels,):
+                raise ValueError("expected one MaxArea per label (%d), got shape %s" % (self.n_labels, area.shape))
+        notair = None
+        if block_not_air is not None:
+            notair = np.ascontiguousarray(np.asarray(block_not_air) != 0, dtype=np.uint8)
+            if notair.shape != (self.n_blocks,):
+                raise ValueError("expected one flag per block (%d), got shape %s" % (self.n_blocks, notair.shape))
+        return sel, area, notair
+
+    def _mag_mask_defaults(self):
+        """(max_area, block_not_air) a make_mask without them takes: nothing
+        for an in-memory problem; a file-solved one knows its .fem's."""
+        return None, None
+
+    def _mag_mask_fill(self, max_area, block_not_air):
+        """each argument left None takes its default"""
+        if max_area is None or block_not_air is None:
+            a, b = self._mag_mask_defaults()
+            max_area = a if max_area is None else max_area
+            block_not_air = b if block_not_air is None else block_not_air
+        return max_area, block_not_air
+
+    def mask_info(self) -> dict:
+        """Whether the problem holds a mask, and the last make_mask's PCG
+        iterations and times in ms (xfk_mag_mask_info)."""
+        o = np.zeros(9)
+        _check(_lib.xfk_mag_mask_info(self._h, o.ctypes.data_as(dptr)))
+        return dict(ready=bool(o[0]), cg_iters=int(o[1]),
+                    times=dict(create=o[2], fixed_values=o[3], symbolic=o[4], assemble=o[5], amg_setup=o[6],
+                               solve=o[7], total=o[8]))
+
+    def make_mask(self, selected_labels, max_area=None, block_not_air=None) -> dict:
+        """FPProc::MakeMask for the selected labels (indices or a boolean mask
+        per label); max_area: the labels' MaxArea (None: the element areas
+        weight the Laplacian); block_not_air: per block, non-zero where a
+        hysteresis angle makes it other than air.  Returns W (the solved nodal
+        values), msk (W > 0.5 as 0 / 1), cg_iters and times (ms)."""
+        ubp = C.POINTER(C.c_ubyte)
+        max_area, block_not_air = self._mag_mask_fill(max_area, block_not_air)
+        sel, area, notair = self._mag_mask_args(selected_labels, max_area, block_not_air)
+        self._mag_mask_key = None
+        _check(_lib.xfk_mag_make_mask(self._h, sel.ctypes.data_as(ubp),
+                                      None if area is None else area.ctypes.data_as(dptr),
+                                      None if notair is None else notair.ctypes.data_as(ubp)))
+        self._mag_mask_key = tuple(None if a is None else a.tobytes() for a in (sel, area, notair))
+        W = np.zeros(self.n_nodes)
+        msk = np.zeros(self.n_nodes)
+        _check(_lib.xfk_mag_get_mask(self._h, W.ctypes.data_as(dptr), msk.ctypes.data_as(dptr)))
+        info = self.mask_info()
+        return dict(W=W, msk=msk, cg_iters=info["cg_iters"], times=info["times"])
+
+    def mask_csr(self):
+        """Diagnostic: the assembled system of the last mask solve, as csr()."""
+        h = C.c_void_p()
+        _check(_lib.xfk_mag_mask_problem(self._h, C.byref(h)))
+        nnz = _lib.xfk_get_nnz(h)
+        rp = np.zeros(self.n_nodes + 1, np.int32)
+        col = np.zeros(nnz, np.int32)
+        val = np.zeros(nnz)
+        b = np.zeros(self.n_nodes)
+        _check(_lib.xfk_get_csr(h, rp.ctypes.data_as(iptr), col.ctypes.data_as(iptr), val.ctypes.data_as(dptr),
+                                b.ctypes.data_as(dptr)))
+        return rp, col, val, b
+
+    def weighted_stress(self, selected_labels, max_area=None, block_not_air=None) -> dict:
+        """The weighted stress tensor force (N) and torque about the origin
+        (N m) on the selection with their "2x" parts: block integrals 18-23,
+        the mask made first unless the problem holds the one of these very
+        arguments."""
+        max_area, block_not_air = self._mag_mask_fill(max_area, block_not_air)
+        key = tuple(None if a is None else a.tobytes()
+                    for a in self._mag_mask_args(selected_labels, max_area, block_not_air))
+        if getattr(self, "_mag_mask_key", None) != key or not self.mask_info()["ready"]:
+            self.make_mask(selected_labels, max_area, block_not_air)
+        # (one type at a time: these are answered whatever the selected blocks are)
+        z = [self.block_integral(selected_labels, t).real for t in range(18, 24)]
+        return dict(force=np.array([z[0], z[1]]), force_2x=np.array([z[2], z[3]]), torque=z[4], torque_2x=z[5])
+
+    def time_stress(self, repeats: int = 5) -> float:
+        """Diagnostic: HIP-event ms (median) of the integral launch of types 18-23."""
+        ms = C.c_double()
+        _check(_lib.xfk_mag_stress_time(self._h, int(repeats), C.byref(ms)))
+        return ms.value
+
 
 class Static2DProblem(_MagPostProc):
     """One device-resident static 2-D magnetostatic problem (FSolver::Static2D).
@@ -670,6 +768,7 @@ class Static2DProblem(_MagPostProc):
         self.n_elems = D.n_elems
         self.n_circs = len(circuits)
         self.n_labels = len(labels)
+        self.n_blocks = len(blocks)
         h = C.c_void_p()
         self.comm = comm
         if comm is None:

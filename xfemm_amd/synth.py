@@ -165,9 +165,10 @@ def write_problem(base: str, kw: dict, label_xy: Optional[np.ndarray] = None) ->
     text += "[NumPoints] = 0\n[NumSegments] = 0\n[NumArcSegments] = 0\n[NumHoles] = 0\n"
     text += "[NumBlockLabels] = %d\n" % len(labels)
     for k, lb in enumerate(labels):
-        text += "0\t0\t%d\t-1\t%d\t%.17g\t0\t%d\t%d\n" % (lb["block"] + 1, lb.get("in_circuit", -1) + 1,
-                                                        lb.get("mag_dir", 0.0), int(lb.get("turns", 1)),
-                                                        int(lb.get("is_external", 0)))
+        # (mesh_size: the label's mesh size d, MaxArea = pi d^2 / 4; -1: none)
+        text += "0\t0\t%d\t%.17g\t%d\t%.17g\t0\t%d\t%d\n" % (lb["block"] + 1, lb.get("mesh_size", -1),
+                                                           lb.get("in_circuit", -1) + 1, lb.get("mag_dir", 0.0),
+                                                           int(lb.get("turns", 1)), int(lb.get("is_external", 0)))
     with open(base + ".fem", "w") as fh:
         fh.write(text)
     x = np.asarray(x, dtype=np.float64)
