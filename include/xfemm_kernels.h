@@ -934,6 +934,70 @@ int xfk_mag_mask_info(xfk_problem *prob, double *out9);
 int xfk_mag_mask_problem(xfk_problem *prob, xfk_problem **aux);
 int xfk_mag_stress_time(xfk_problem *prob, int repeats, double *ms);
 
+/* Point values and contour integrals of a magnetostatic problem: fpproc's
+ * GetNodalB (fpproc.cpp:2704-2967), GetPointValues with GetPointB (2257-2498,
+ * 2669-2702) and LineIntegral (4094-4515) at Frequency 0, planar and
+ * axisymmetric, in double in the reference's operation order.  Coordinates are
+ * in the problem's length units.
+ *
+ * The element of a point is the lowest-numbered element whose InTriangleTest
+ * (3387-3424) accepts it; the reference's InTriangle walks from the element of
+ * its previous call and LineIntegral over the neighbours of the previous
+ * sample's element, so the two differ only for a point exactly on an edge or a
+ * node.  A point no element contains gets element -1 and NaN values.
+ *
+ * Refused before any launch, with the cause in xfk_last_error and the problem
+ * left usable: a harmonic and a sharded problem; a problem holding a label
+ * whose block has LamType > 2 (its fill factor, conductivity and energy need
+ * GetFillFactor) or is a nonlinear permanent magnet (H_c != 0 with a B-H curve:
+ * its energy needs fpproc's shifted curve and Nrg) -- for the whole problem,
+ * wherever the points lie (XFK_ERR_UNSUPPORTED).  A static problem with
+ * PrevType != 0 is refused when it is loaded, as in the reference.
+ *
+ * xfk_mag_corner_b: b[6 n_elems], GetNodalB of every element: (b1, b2) of its
+ * corners 0, 1, 2.  Made at the first smoothed request and kept until a new
+ * solution.  Two labels are the "same material" when they are the same label,
+ * or their blocks' mu_x, mu_y, H_c and their directions are equal (mu_x, mu_y
+ * as fpproc holds them after GetSlopes; two directions are equal when their
+ * cosines and sines are).  A node carries a point current when its descriptor
+ * marker names a point property with J != 0.
+ * xfk_mag_point_values: n points; elem[n] out; out[13 n], per point
+ *   0 A (the flux 2 pi r A when axisymmetric)   1 2  B1 B2, T
+ *   3 4  mu1 mu2 (relative, divided by AECF)     5 6  H1 H2, A/m (less Hc)
+ *   7 Js, MA/m^2   8 c, MS/m   9 E, J/m^3   10 11 Hc (re, im), A/m
+ *   12 ff (1 in a wound label, else -1)
+ * (Je, Ph and Pe are 0 at Frequency 0).  smooth != 0: B interpolated from the
+ * corner values, else the element's.
+ * xfk_mag_point_values_at: the same with elem[n] given (-1: none).
+ * xfk_mag_line_integrals: the layout of xfk_pot_line_integrals; type 0 B.n (Wb,
+ * and its average), 1 H.t (A, and its average), 2 length and area, 3 stress
+ * tensor force (x, y; N; x is 0 when axisymmetric), 4 stress tensor torque
+ * about the origin (N m; 0 on an axisymmetric problem, where the reference
+ * multiplies by a depth that has no meaning), 5 (B.n)^2 and its average.
+ * out[2 n_contours], missed[n_contours] (may be NULL): the samples no element
+ * contains, which add nothing.  A contour has the same bits alone, in any
+ * batch and on a second run.
+ * xfk_mag_contour_samples: xy[2 ns], elem[ns] of one contour's samples
+ * (ns = (n - 1) npts), for tests.
+ * xfk_mag_point_time: HIP-event ms (medians of `repeats` runs after a warm-up)
+ * of ms4[0] the corner kernel, [1] the cell grid, [2] [3] the point kernel on
+ * the n points with smoothing off and on.  xfk_mag_contour_time: of the
+ * contour kernel with its sums over the batch. */
+int xfk_mag_corner_b(xfk_problem *prob, double *b);
+int xfk_mag_point_values(xfk_problem *prob, int n, const double *x, const double *y, int smooth, int *elem,
+                         double *out);
+int xfk_mag_point_values_at(xfk_problem *prob, int n, const double *x, const double *y, const int *elem, int smooth,
+                            double *out);
+int xfk_mag_line_integrals(xfk_problem *prob, int n_contours, const int *ptr, const double *x, const double *y,
+                           int type, int smooth, int npts, double *out, int *missed);
+int xfk_mag_line_integral(xfk_problem *prob, int n, const double *x, const double *y, int type, int smooth, int npts,
+                          double *out2, int *missed);
+int xfk_mag_contour_samples(xfk_problem *prob, int n, const double *x, const double *y, int type, int npts,
+                            double *xy, int *elem);
+int xfk_mag_point_time(xfk_problem *prob, int n, const double *x, const double *y, int repeats, double *ms4);
+int xfk_mag_contour_time(xfk_problem *prob, int n_contours, const int *ptr, const double *x, const double *y,
+                         int type, int smooth, int npts, int repeats, double *ms);
+
 /* Diagnostics of the AMG hierarchy (single device), for tests; not part of the
  * interface a caller should build on.  A probe holds one hierarchy built from
  * a host CSR (full symmetric, a diagonal in every row) with the options the

@@ -2416,6 +2416,11 @@ int build_local(const xfk_problem_desc *d, const GlobalPrep &G, const PartPlan *
         P->mag_ext_user[2] = d->ext_zo;
         P->mag_has_point.assign(d->n_nodes, 0);
         for (int i = 0; i < d->n_nodes && d->marker; ++i) P->mag_has_point[i] = d->marker[i] >= 0;
+        P->mag_point_j.assign(d->n_nodes, 0);
+        for (int i = 0; i < d->n_nodes && d->marker; ++i) {
+            const int m = d->marker[i];
+            if (m >= 0 && m < d->n_points) P->mag_point_j[i] = (d->points[m].J_re != 0) || (d->points[m].J_im != 0);
+        }
     }
     P->nblocks = d->n_blocks;
     P->nlabels = (int)nlab;

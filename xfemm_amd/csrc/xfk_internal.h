@@ -687,6 +687,14 @@ struct xfk_problem {
     std::vector<unsigned char> mag_has_point;    // host, N: the node carries a point property (marker >= 0)
     xfk::DBuf<int> mag_n2e_ptr, mag_n2e;         // node -> elements of p_raw, ascending
     xfk::DBuf<unsigned char> mag_mlab;           // per entry of the label table: selected, then not air
+    // ... its point values and contour integrals: the element B and the
+    // smoothed corner values follow the solution (dropped where mag_A is
+    // replaced); the cell grid is the pp_ group's, over mag_x, mag_y, p_raw
+    std::vector<unsigned char> mag_point_j;      // host, N: the node's point property carries a current
+    bool mag_n2e_ready = false, mag_B_ready = false, mag_corner_ready = false, mag_ctab_ready = false;
+    xfk::DBuf<double> mag_bc;                    // 6 NE: GetNodalB, (b1, b2) of the corners 0 1 2
+    xfk::DBuf<int> mag_clab;                     // per entry of the label table: the descriptor's label, its "same material" class
+    xfk::DBuf<unsigned char> mag_pj;             // N: mag_point_j
 
     // live SpMV launch timing (XFK_TIME_SPMV)
     bool time_spmv = false;

@@ -1,7 +1,7 @@
 // Post-processing of a magnetostatic problem on the device: the element flux
 // density, the volume integrals of the reference's fpproc that need no mask,
-// and the weighted stress tensor force and torque over its mask, for MI355X
-// (gfx950).  Frequency 0 only, planar and axisymmetric.
+// the weighted stress tensor force and torque over its mask, and its point
+// values and contour integrals, for MI355X (gfx950).  Frequency 0 only, planar and axisymmetric.
 //
 //   element B         FPProc::GetElementB (fpproc.cpp:2970-3082)
 //   J and A           FPProc::GetJA (3495-3578), PlnInt / AxiInt (3580-3612),
@@ -14,6 +14,9 @@
 //                     FindBoundaryEdges (fpproc.cpp:5356-5415)
 //   force and torque  HenrotteVector (3614-3640), BlockIntegral types 18-23
 //                     (3966-4079)
+//   point values      GetNodalB (2704-2967), GetPointB (2669-2702),
+//                     GetPointValues (2257-2498), InTriangleTest (3387-3424)
+//   contour integrals LineIntegral (4094-4515)
 //
 // fpproc works in the problem's own length units with LengthConv[] to metres;
 // the solver in cm.  The coordinates are divided back by the solver's unit once
@@ -30,6 +33,12 @@
 #include "xfk_potential.h"
 
 #pragma clang fp contract(off)
+
+#include "xfk_ppsearch.h"
+
+#include <array>
+#include <cstring>
+#include <map>
 
 namespace xfk {
 
@@ -69,6 +78,7 @@ struct MagArgs {
 };
 
 // abs(CComplex) (femmcomplex.cpp:749-757)
+static inline double mag_cabs_host(double re, double im) { return pp_cabs(re, im); }
 __device__ __forceinline__ double mag_cabs(double re, double im)
 {
     if ((re == 0) && (im == 0)) return 0.;
@@ -603,6 +613,463 @@ __global__ void __launch_bounds__(kPotQBlock) k_mag_stress(int NE, MagArgs M, co
     block_sums<kMagStressSums>(v, part);
 }
 
+// --- point values and contour integrals ----------------------------------------
+//
+//   GetNodalB        fpproc.cpp:2704-2967      k_mag_corner
+//   GetPointValues   2257-2498, GetPointB 2669-2702, FPProc::GetMu 5322-5328,
+//                    CMMaterialProp::GetMu CMaterialProp.cpp:775-844   k_mag_points
+//   LineIntegral     4094-4515                 k_mag_contour
+//
+// The element of a point is the lowest-numbered one containing it (pp_find),
+// not the one InTriangle's walk from its static k reaches.  Where
+// oracle/pointvalues.py, the restatement the recorded field values were
+// checked with, associates differently from fpproc.cpp, its order is taken:
+// an interface's tangential and normal parts are added to each other before
+// they are added to the nodal value (fpproc.cpp:2818-2821 adds them in turn),
+// and a corner value is multiplied by its weight already divided by da
+// (fpproc.cpp:2699 divides the product).
+
+constexpr int kMagPointVals = 13;   // A B1 B2 mu1 mu2 H1 H2 Js c E Hc.re Hc.im ff
+
+struct MagCornerArgs {
+    const int *n2e_ptr, *n2e;   // ConList: node -> elements, ascending
+    const int *clab;            // per entry of the label table: the descriptor's label, its "same material" class
+    const unsigned char *pj;    // the node carries a point current
+    const double *B1, *B2;      // the element flux density
+};
+
+// The interface side k-pt seen from an element with flux density (eB1, eB2)
+// (fpproc.cpp:2799-2823): tangential B from the element, normal B from the A
+// difference along the side
+template <bool AXI>
+__device__ __forceinline__ void mag_interface(const MagArgs &M, int k, int pt, double eB1, double eB2, double &R,
+                                              double &b1, double &b2, double &vx, double &vy)
+{
+    double tnx = M.x[pt] - M.x[k], tny = M.y[pt] - M.y[k];
+    const double r = (M.x[pt] + M.x[k]) * M.lc / 2.;
+    const double atn = mag_cabs(tnx, tny);
+    double bn = (M.A[pt] - M.A[k]) / (atn * M.lc);
+    if (AXI) bn /= (-2. * kPI * r);
+    const double z = 0.5 / atn;
+    tnx /= atn;
+    tny /= atn;
+    const double bt = eB1 * tnx + eB2 * tny;
+    R += z;
+    b1 += (z * tnx * bt + z * tny * bn);
+    b2 += (z * tny * bt - z * tnx * bn);
+    vx = tnx;
+    vy = tny;
+}
+
+// The walk around node k from element e to an interface, counter-clockwise or
+// clockwise (fpproc.cpp:2767-2826, 2832-2889); true: a side without a
+// neighbour, the "special-case punt" (b1, b2 are then that element's)
+template <bool AXI, bool CCW>
+__device__ __forceinline__ bool mag_walk(const MagArgs &M, const MagCornerArgs &C, int e, int k, int l0, int num,
+                                         int mylabel, double &R, double &b1, double &b2, double &vx, double &vy)
+{
+    int ec = e;
+    for (int q = 0; q < num; ++q) {
+        int pt = 0;
+        for (int j = 0; j < 3; ++j)
+            if (M.p[3 * ec + j] == k) pt = j;
+        if (CCW) {
+            pt--;
+            if (pt < 0) pt = 2;
+        } else {
+            pt++;
+            if (pt > 2) pt = 0;
+        }
+        pt = M.p[3 * ec + pt];
+        // the element adjacent to this side: the last matching entry of ConList
+        int nxt = -1;
+        for (int j = 0; j < num; ++j) {
+            const int c = C.n2e[l0 + j];
+            if (c != ec)
+                for (int l = 0; l < 3; ++l)
+                    if (M.p[3 * c + l] == pt) nxt = c;
+        }
+        if (nxt == -1) {
+            b1 = C.B1[ec];
+            b2 = C.B2[ec];
+            return true;
+        }
+        if (mylabel != C.clab[2 * M.lbl[nxt]]) {
+            mag_interface<AXI>(M, k, pt, C.B1[ec], C.B2[ec], R, b1, b2, vx, vy);
+            return false;
+        }
+        ec = nxt;
+    }
+    return false;
+}
+
+// GetNodalB: one thread per (element, corner); bc[6 e + 2 i], [.. + 1] = b1, b2
+// of corner i.  branch (may be null): 0 the patch, 1 an interface, 2 the
+// special-case punt, + 4 the sharp-corner punt
+template <bool AXI>
+__global__ void __launch_bounds__(kBlock) k_mag_corner(int NE, MagArgs M, MagCornerArgs C, double *__restrict__ bc,
+                                                       unsigned char *__restrict__ branch)
+{
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= 3 * NE) return;
+    const int e = t / 3, i = t - 3 * e;
+    const int k = M.p[3 * e + i];
+    const double px = M.x[k], py = M.y[k];
+    const int l0 = C.n2e_ptr[k], num = C.n2e_ptr[k + 1] - l0;
+    const int mylabel = C.clab[2 * M.lbl[e]], myclass = C.clab[2 * M.lbl[e] + 1];
+    double b1 = 0., b2 = 0.;
+    int br = 0;
+    int m = 0;
+    for (int j = 0; j < num; ++j) {
+        const int l = M.lbl[C.n2e[l0 + j]];
+        if (mylabel == C.clab[2 * l]) m++;
+        else if (myclass == C.clab[2 * l + 1]) m++;
+    }
+    if (m == num) {
+        // normal smoothing method for points away from any boundaries
+        double R = 0;
+        for (int j = 0; j < num; ++j) {
+            const int c = C.n2e[l0 + j];
+            double cx = 0., cy = 0.;
+            for (int q = 0; q < 3; ++q) {
+                cx += M.x[M.p[3 * c + q]] / 3.;
+                cy += M.y[M.p[3 * c + q]] / 3.;
+            }
+            const double z = 1. / mag_cabs(px - cx, py - cy);
+            R += z;
+            b1 += (z * C.B1[c]);
+            b2 += (z * C.B2[c]);
+        }
+        b1 /= R;
+        b2 /= R;
+    } else {
+        double R = 0, v1x = 0, v1y = 0, v2x = 0, v2y = 0;
+        br = 1;
+        if (mag_walk<AXI, true>(M, C, e, k, l0, num, mylabel, R, b1, b2, v1x, v1y)) {
+            v1x = 1; v1y = 0; v2x = 1; v2y = 0;
+            br = 2;
+        }
+        if ((v2x == 0) && (v2y == 0)) {   // (not after the punt, which has set the values)
+            if (mag_walk<AXI, false>(M, C, e, k, l0, num, mylabel, R, b1, b2, v2x, v2y)) {
+                v1x = 1; v1y = 0; v2x = 1; v2y = 0;
+                br = 2;
+            }
+            b1 /= R;
+            b2 /= R;
+        }
+        // too sharp a corner for the interface rule?
+        bool flag = false;
+        if ((mag_cabs(v1x, v1y) < 0.9) || (mag_cabs(v2x, v2y) < 0.9)) flag = true;
+        if ((-v1x * v2x - v1y * v2y) > 0.985) flag = true;
+        if (!flag) {
+            br += 4;
+            double bn = 0;
+            for (int j = 0; j < num; ++j) {
+                const int c = C.n2e[l0 + j];
+                if (mylabel == C.clab[2 * M.lbl[c]]) {
+                    const double bt = sqrt(C.B1[c] * C.B1[c] + C.B2[c] * C.B2[c]);
+                    if (bt > bn) bn = bt;
+                }
+            }
+            const double R2 = sqrt(C.B1[e] * C.B1[e] + C.B2[e] * C.B2[e]);
+            if (R2 != 0) {
+                b1 = bn / R2 * C.B1[e];
+                b2 = bn / R2 * C.B2[e];
+            } else {
+                b1 = 0;
+                b2 = 0;
+            }
+        }
+    }
+    // a point current at the node: the element's own values
+    if (C.pj[k]) {
+        b1 = C.B1[e];
+        b2 = C.B2[e];
+    }
+    // a node on the axis: Br = 0
+    if (AXI && (fabs(px) < 1.e-06)) b1 = 0.;
+    bc[6 * (size_t)e + 2 * i] = b1;
+    bc[6 * (size_t)e + 2 * i + 1] = b2;
+    if (branch) branch[t] = (unsigned char)br;
+}
+
+// CMMaterialProp::GetMu(double ...) (CMaterialProp.cpp:775-844) at MuMax == 0
+__device__ __forceinline__ void mag_get_mu(const MagArgs &M, const DevBlock &bp, double b1, double b2, double &mu1,
+                                           double &mu2)
+{
+    const double muo = kMUO, LamFill = bp.LamFill;
+    mu1 = mu2 = muo;
+    if (bp.BHpoints == 0) {
+        if (bp.LamType == 0) {
+            mu1 = ((1. + LamFill * (bp.mu_x - 1.)) * muo);
+            mu2 = ((1. + LamFill * (bp.mu_y - 1.)) * muo);
+        }
+        if (bp.LamType == 1) {
+            mu1 = ((1. + LamFill * (bp.mu_x - 1.)) * muo);
+            mu2 = 1. / (LamFill / (bp.mu_y * muo) + (1. - LamFill) / muo);
+        }
+        if (bp.LamType == 2) {
+            mu2 = ((1. + LamFill * (bp.mu_y - 1.)) * muo);
+            mu1 = 1. / (LamFill / (bp.mu_x * muo) + (1. - LamFill) / muo);
+        }
+    } else {
+        const double s0 = M.bhS[bp.bh_off];
+        double muiron;
+        if (bp.LamType == 0) {
+            const double biron = sqrt(b1 * b1 + b2 * b2);
+            if (biron < 1.e-08) mu1 = 1. / s0;
+            else mu1 = biron / mag_get_h(M, bp, biron);
+            mu2 = mu1;
+        }
+        if (bp.LamType == 1) {
+            const double biron = sqrt((b1 / LamFill) * (b1 / LamFill) + b2 * b2);
+            if (biron < 1.e-08) muiron = 1. / s0;
+            else muiron = biron / mag_get_h(M, bp, biron);
+            mu1 = muiron * LamFill;
+            mu2 = 1. / (LamFill / muiron + (1. - LamFill) / muo);
+        }
+        if (bp.LamType == 2) {
+            const double biron = sqrt((b2 / LamFill) * (b2 / LamFill) + b1 * b1);
+            if (biron < 1.e-08) muiron = 1. / s0;
+            else muiron = biron / mag_get_h(M, bp, biron);
+            mu2 = muiron * LamFill;
+            mu1 = 1. / (LamFill / muiron + (1. - LamFill) / muo);
+        }
+    }
+    mu1 /= muo;
+    mu2 /= muo;
+}
+
+// GetPointValues(x, y, k, u) at Frequency 0 with d_ShiftH: the kMagPointVals
+// values of a point of element k.  B: the element flux density (B1 then B2),
+// bc: the corner values (read when smooth)
+template <bool AXI>
+__device__ __forceinline__ void mag_values_at(const MagArgs &M, int NE, int k, double x, double y, int smooth,
+                                              const double *__restrict__ B, const double *__restrict__ bc,
+                                              double (&o)[kMagPointVals])
+{
+    MagElem E;
+    mag_load(M, k, E);
+    const MagLabel lab = M.labels[E.lbl];
+    const DevBlock bp = M.blocks[lab.blk];
+    const double muo = kMUO;
+    double a[3], b[3], c[3];
+    a[0] = E.X[1] * E.Y[2] - E.X[2] * E.Y[1];
+    a[1] = E.X[2] * E.Y[0] - E.X[0] * E.Y[2];
+    a[2] = E.X[0] * E.Y[1] - E.X[1] * E.Y[0];
+    b[0] = E.Y[1] - E.Y[2]; b[1] = E.Y[2] - E.Y[0]; b[2] = E.Y[0] - E.Y[1];
+    c[0] = E.X[2] - E.X[1]; c[1] = E.X[0] - E.X[2]; c[2] = E.X[1] - E.X[0];
+    const double da = (b[0] * c[1] - b[1] * c[0]);
+    double ravg = M.lc * (E.X[0] + E.X[1] + E.X[2]) / 3.;
+    // GetPointB
+    double B1, B2;
+    if (!smooth) {
+        B1 = B[k];
+        B2 = B[NE + k];
+    } else {
+        B1 = 0;
+        B2 = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double w = (a[i] + b[i] * x + c[i] * y) / da;
+            B1 += bc[6 * (size_t)k + 2 * i] * w;
+            B2 += bc[6 * (size_t)k + 2 * i + 1] * w;
+        }
+    }
+    double A = 0;
+    if (!AXI) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) A += E.A[i] * (a[i] + b[i] * x + c[i] * y) / (da);
+    } else {
+        double v[6];
+        const double (&R)[3] = E.X;
+        v[0] = E.A[0];
+        v[2] = E.A[1];
+        v[4] = E.A[2];
+        if ((R[0] < 1.e-06) && (R[1] < 1.e-06)) v[1] = (v[0] + v[2]) / 2.;
+        else v[1] = (R[1] * (3. * v[0] + v[2]) + R[0] * (v[0] + 3. * v[2])) / (4. * (R[0] + R[1]));
+        if ((R[1] < 1.e-06) && (R[2] < 1.e-06)) v[3] = (v[2] + v[4]) / 2.;
+        else v[3] = (R[2] * (3. * v[2] + v[4]) + R[1] * (v[2] + 3. * v[4])) / (4. * (R[1] + R[2]));
+        if ((R[2] < 1.e-06) && (R[0] < 1.e-06)) v[5] = (v[4] + v[0]) / 2.;
+        else v[5] = (R[0] * (3. * v[4] + v[0]) + R[2] * (v[4] + 3. * v[0])) / (4. * (R[2] + R[0]));
+        const double p = (b[1] * x + c[1] * y + a[1]) / da;
+        const double q = (b[2] * x + c[2] * y + a[2]) / da;
+        A = v[0] - p * (3. * v[0] - 4. * v[1] + v[2]) + 2. * p * p * (v[0] - 2. * v[1] + v[2]) -
+            q * (3. * v[0] + v[4] - 4. * v[5]) + 2. * q * q * (v[0] + v[4] - 2. * v[5]) +
+            4. * p * q * (v[0] - v[1] + v[3] - v[5]);
+    }
+    // FPProc::GetMu: the block's, divided by the element's AECF
+    double cx = 0., cy = 0.;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        cx += E.X[j] / 3.;
+        cy += E.Y[j] / 3.;
+    }
+    double mu1, mu2;
+    mag_get_mu(M, bp, B1, B2, mu1, mu2);
+    const double aecf = mag_aecf<AXI>(M, lab, cx, cy);
+    mu1 /= aecf;
+    mu2 /= aecf;
+    double H1 = B1 / (mu1 * muo), H2 = B2 / (mu2 * muo);
+    // the source current density
+    double Js = bp.J_re;
+    if (lab.ccase >= 0) {
+        if (lab.ccase == 0) {
+            if (!AXI) Js -= bp.Cduct * lab.dV;
+            else {
+                double R[3];
+#pragma unroll
+                for (int tn = 0; tn < 3; ++tn) {
+                    R[tn] = E.X[tn];
+                    if (R[tn] < 1.e-6) R[tn] = ravg;
+                    else R[tn] *= M.lc;
+                }
+                ravg = 0.;
+#pragma unroll
+                for (int tn = 0; tn < 3; ++tn) ravg += (1. / R[tn]) * (a[tn] + b[tn] * x + c[tn] * y) / (da);
+                Js -= bp.Cduct * lab.dV * ravg;
+            }
+        } else Js += lab.J;
+    }
+    double En = mag_do_energy<false>(M, bp, B1, B2);
+    double Hcr = 0, Hci = 0;
+    // the second-quadrant representation of a (linear) permanent magnet
+    if (bp.H_c != 0) {
+        Hcr = bp.H_c * lab.cos_m;
+        Hci = bp.H_c * lab.sin_m;
+        H1 = H1 - Hcr;
+        H2 = H2 - Hci;
+        En = 0.5 * muo * (mu1 * H1 * H1 + mu2 * H2 * H2);
+    }
+    o[0] = A;
+    o[1] = B1;
+    o[2] = B2;
+    o[3] = mu1;
+    o[4] = mu2;
+    o[5] = H1;
+    o[6] = H2;
+    o[7] = Js;
+    o[8] = bp.Cduct;
+    o[9] = En;
+    o[10] = Hcr;
+    o[11] = Hci;
+    o[12] = lab.wound ? 1. : -1.;
+}
+
+// GetPointValues of n points: the lowest-numbered element containing each
+// (-1: none, its values NaN; given: elem[t] names it on entry), then
+// kMagPointVals values per point
+template <bool AXI>
+__global__ void __launch_bounds__(kBlock) k_mag_points(int n, int NE, MagArgs M, PpGrid G, PpLists L,
+                                                       const double *__restrict__ px, const double *__restrict__ py,
+                                                       int smooth, const double *__restrict__ B,
+                                                       const double *__restrict__ bc, int *__restrict__ elem,
+                                                       double *__restrict__ out, int given)
+{
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const double x = px[t], y = py[t];
+    int nt = 0;
+    const int k = given ? elem[t] : pp_find(M.x, M.y, M.p, G, L, x, y, nt);
+    elem[t] = k;
+    double v[kMagPointVals];
+    if (k < 0) {
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+        for (int c = 0; c < kMagPointVals; ++c) v[c] = nan;
+    } else {
+        mag_values_at<AXI>(M, NE, k, x, y, smooth, B, bc, v);
+    }
+    double *o = out + kMagPointVals * (size_t)t;
+#pragma unroll
+    for (int c = 0; c < kMagPointVals; ++c) o[c] = v[c];
+}
+
+// LineIntegral types 1, 3, 4 and 5: one thread per sample of a batch of
+// contours, laid out as k_pp_contour's (xfk_postproc.hip): contour c holds the
+// vertices cptr[c] .. cptr[c + 1) and owns the workgroups bptr[c] ..
+// bptr[c + 1).  Per workgroup three sums into part: the integral's two, and
+// the samples no element holds, which add nothing to the other two.
+// dbg_xy, dbg_el (may be null; one contour only): every sample's point and element.
+template <bool AXI>
+__global__ void __launch_bounds__(kPotQBlock) k_mag_contour(int nc, int NE, MagArgs M, PpGrid G, PpLists L,
+                                                            const int *__restrict__ cptr,
+                                                            const int *__restrict__ bptr,
+                                                            const double *__restrict__ cx,
+                                                            const double *__restrict__ cy, int npts, int type,
+                                                            int smooth, const double *__restrict__ B,
+                                                            const double *__restrict__ bc,
+                                                            double *__restrict__ part, double *__restrict__ dbg_xy,
+                                                            int *__restrict__ dbg_el)
+{
+    // the contour of this workgroup: bptr[c] <= blockIdx.x < bptr[c + 1]
+    int c = 0, hi = nc;
+    while (hi - c > 1) {
+        const int mid = (c + hi) >> 1;
+        if (bptr[mid] <= (int)blockIdx.x) c = mid;
+        else hi = mid;
+    }
+    const int v0 = cptr[c], nseg = cptr[c + 1] - v0 - 1;
+    const int j = ((int)blockIdx.x - bptr[c]) * kPotQBlock + threadIdx.x;
+    double v[3] = {0., 0., 0.};
+    if (j < nseg * npts) {
+        const int k = j / npts, i = j - k * npts;
+        const double x0 = cx[v0 + k], y0 = cy[v0 + k], x1 = cx[v0 + k + 1], y1 = cy[v0 + k + 1];
+        const double dx = x1 - x0, dy = y1 - y0;
+        const double len = mag_cabs(dx, dy);
+        const double dz = len / ((double)npts);
+        const double u = (((double)i) + 0.5) / ((double)npts);
+        double ptx = x0 + u * dx, pty = y0 + u * dy;
+        const double tr = dx / len, ti = dy / len;
+        // n = I * t, the complex product as the reference forms it
+        const double nr = 0. * tr - 1. * ti, ni = 0. * ti + 1. * tr;
+        ptx += nr * 1.e-06;
+        pty += ni * 1.e-06;
+        int nt;
+        const int el = pp_find(M.x, M.y, M.p, G, L, ptx, pty, nt);
+        if (dbg_xy) {
+            dbg_xy[2 * (size_t)j] = ptx;
+            dbg_xy[2 * (size_t)j + 1] = pty;
+        }
+        if (dbg_el) dbg_el[j] = el;
+        if (el < 0) {
+            v[2] = 1.;
+        } else {
+            double o[kMagPointVals];
+            mag_values_at<AXI>(M, NE, el, ptx, pty, smooth, B, bc, o);
+            const double B1 = o[1], B2 = o[2], H1 = o[5], H2 = o[6];
+            if (type == 1) {
+                const double Ht = tr * H1 + ti * H2;
+                v[0] = (Ht * dz * M.lc);
+            } else if (type == 5) {
+                const double Bn = nr * B1 + ni * B2;
+                // Ht * Ht.Conj() of a real number: its square less (0 * -0)
+                v[0] = ((Bn * Bn - 0. * (-0.)) * dz * M.lc);
+            } else {
+                const double Hn = nr * H1 + ni * H2;
+                const double Bn = nr * B1 + ni * B2;
+                const double BH = B1 * H1 + B2 * H2;
+                double dF1 = H1 * Bn + B1 * Hn - nr * BH;
+                const double dF2 = H2 * Bn + B2 * Hn - ni * BH;
+                if (type == 3) {
+                    double dza = dz * M.lc;
+                    if (AXI) {
+                        dza *= 2. * kPI * ptx * M.lc;
+                        dF1 = 0;
+                    } else dza *= M.depth;
+                    v[0] = (dF1 * dza / 2.);
+                    v[1] = (dF2 * dza / 2.);
+                } else if (!AXI) {   // (type 4; on an axisymmetric problem 0)
+                    const double dT = ptx * dF2 - dF1 * pty;
+                    const double dza = dz * M.lc * M.lc;
+                    v[0] = (dT * dza * M.depth / 2.);
+                }
+            }
+        }
+    }
+    block_sums<3>(v, part);
+}
+
 // user-unit coordinates
 static __global__ void k_mag_xy(int N, const double *__restrict__ x, const double *__restrict__ y, double u,
                                 double *__restrict__ mx, double *__restrict__ my)
@@ -683,6 +1150,7 @@ static int mag_prepare(xfk_problem *P)
         k_mag_a<<<G, kBlock, 0, s>>>(N, P->axi ? 1 : 0, P->V.p, P->x.p, P->mag_A.p);
         XFK_CHECK(hipGetLastError());
         P->mag_A_ready = true;
+        P->mag_B_ready = P->mag_corner_ready = false;
     }
     return XFK_OK;
 }
@@ -715,7 +1183,9 @@ static MagArgs mag_args(const xfk_problem *P)
 // (WriteStatic2D) and fpproc reads back (fpproc.cpp:1289-1308).  With energy
 // set, refuses a selected label whose energy this post-processor does not
 // compute (types 18-23 read B and the mask alone: their callers clear it).
-static int mag_labels(xfk_problem *P, const unsigned char *sel, bool energy = true)
+// whole: every label counts as selected and the refusals name the problem
+// (point values and contour integrals: sel is not read).
+static int mag_labels(xfk_problem *P, const unsigned char *sel, bool energy = true, bool whole = false)
 {
     hipStream_t s = P->stream;
     const size_t nlab = P->mag_hlab.size();
@@ -731,7 +1201,7 @@ static int mag_labels(xfk_problem *P, const unsigned char *sel, bool energy = tr
         o.sin_m = L.sin_m;
         o.wound = L.is_wound ? 1 : 0;
         o.external = L.external ? 1 : 0;
-        o.sel = sel[P->mag_lab_orig[k]] ? 1 : 0;
+        o.sel = (whole || sel[P->mag_lab_orig[k]]) ? 1 : 0;
         o.ccase = -1;
         if (L.in_circuit >= 0 && L.in_circuit < P->ncircs) {
             const DevCirc &C = circ[L.in_circuit];
@@ -741,11 +1211,17 @@ static int mag_labels(xfk_problem *P, const unsigned char *sel, bool energy = tr
         }
         if (!o.sel || !energy) continue;
         XFK_REQUIRE(B.LamType <= 2, XFK_ERR_UNSUPPORTED,
-                    "a selected label's block has LamType > 2 (a wound region with proximity effects): its energy "
-                    "needs the label's effective conductivity and fill factor (GetFillFactor), which are not built");
+                    whole ? "the problem holds a label whose block has LamType > 2 (a wound region with proximity "
+                            "effects): its fill factor, conductivity and energy at a point need GetFillFactor, which "
+                            "is not built"
+                          : "a selected label's block has LamType > 2 (a wound region with proximity effects): its "
+                            "energy needs the label's effective conductivity and fill factor (GetFillFactor), which "
+                            "are not built");
         XFK_REQUIRE(!(B.H_c != 0 && B.BHpoints > 0), XFK_ERR_UNSUPPORTED,
-                    "a selected label's block is a nonlinear permanent magnet (H_c != 0 with a B-H curve): its "
-                    "energy needs fpproc's shifted curve and Nrg, which are not built");
+                    whole ? "the problem holds a nonlinear permanent magnet (H_c != 0 with a B-H curve): its energy "
+                            "at a point needs fpproc's shifted curve and Nrg, which are not built"
+                          : "a selected label's block is a nonlinear permanent magnet (H_c != 0 with a B-H curve): "
+                            "its energy needs fpproc's shifted curve and Nrg, which are not built");
     }
     XFK_CHECK(P->mag_lab.alloc(sizeof(MagLabel) * t.size()));
     XFK_CHECK(hipMemcpyAsync(P->mag_lab.p, t.data(), sizeof(MagLabel) * t.size(), hipMemcpyHostToDevice, s));
@@ -769,6 +1245,26 @@ static int mag_launch_integrals(xfk_problem *P, const MagArgs &M)
 static const char *const kMagMaskInvalid =
     "The selected region is invalid. A valid selection\ncannot abut a region which is not free space.";
 
+// The node -> element lists over the caller's numbering p (host), ascending:
+// the reference's element order, fpproc's ConList -- once
+static int mag_conlist(xfk_problem *P, const std::vector<int> &p)
+{
+    if (P->mag_n2e_ready) return XFK_OK;
+    hipStream_t s = P->stream;
+    const int N = P->N, NE = P->NE;
+    std::vector<int> ptr(N + 1, 0);
+    for (size_t k = 0; k < 3 * (size_t)NE; ++k) ptr[p[k] + 1]++;
+    for (int i = 0; i < N; ++i) ptr[i + 1] += ptr[i];
+    std::vector<int> lst(3 * (size_t)NE), fill(ptr.begin(), ptr.end() - 1);
+    for (int e = 0; e < NE; ++e)
+        for (int j = 0; j < 3; ++j) lst[fill[p[3 * (size_t)e + j]]++] = e;
+    XFK_CHECK(upload(P->mag_n2e_ptr, ptr.data(), ptr.size(), s));
+    XFK_CHECK(upload(P->mag_n2e, lst.data(), lst.size(), s));
+    XFK_CHECK(hipStreamSynchronize(s));   // (ptr and lst leave scope)
+    P->mag_n2e_ready = true;
+    return XFK_OK;
+}
+
 // What the mask reads of the mesh, once: the node -> element lists over the
 // caller's numbering (ascending: the reference's element order), the exterior
 // edges, the point marks, and the auxiliary problem over the same connectivity
@@ -785,19 +1281,12 @@ static int mag_mask_mesh(xfk_problem *P, double &ms_create)
     XFK_CHECK(d2h(y.data(), P->mag_y.p, sizeof(double) * N, s));
     XFK_CHECK(d2h(p.data(), P->p_raw.p, sizeof(int) * 3 * (size_t)NE, s));
     XFK_CHECK(d2h(lbl.data(), P->lbl_raw.p, sizeof(int) * NE, s));
-    std::vector<int> ptr(N + 1, 0);
-    for (size_t k = 0; k < 3 * (size_t)NE; ++k) ptr[p[k] + 1]++;
-    for (int i = 0; i < N; ++i) ptr[i + 1] += ptr[i];
-    std::vector<int> lst(3 * (size_t)NE), fill(ptr.begin(), ptr.end() - 1);
-    for (int e = 0; e < NE; ++e)
-        for (int j = 0; j < 3; ++j) lst[fill[p[3 * (size_t)e + j]]++] = e;
-    XFK_CHECK(upload(P->mag_n2e_ptr, ptr.data(), ptr.size(), s));
-    XFK_CHECK(upload(P->mag_n2e, lst.data(), lst.size(), s));
+    int rc = mag_conlist(P, p);
+    if (rc != XFK_OK) return rc;
     XFK_CHECK(upload(P->mask_point, P->mag_has_point.data(), (size_t)N, s));
     XFK_CHECK(P->mask_ext.alloc((size_t)N));
-    int rc = launch_mask_exterior(s, N, NE, P->p_raw.p, P->mag_n2e_ptr.p, P->mag_n2e.p, P->mask_ext.p);
+    rc = launch_mask_exterior(s, N, NE, P->p_raw.p, P->mag_n2e_ptr.p, P->mag_n2e.p, P->mask_ext.p);
     if (rc != XFK_OK) return rc;
-    XFK_CHECK(hipStreamSynchronize(s));   // (ptr and lst leave scope)
     const auto t0 = std::chrono::steady_clock::now();
     const std::vector<PotLabel> lab(std::max<size_t>(1, P->mag_hlab.size()), PotLabel{0, 0});
     if ((rc = mask_aux_create(P, x, y, p, lbl, lab, P->length_units)) != XFK_OK) return rc;
@@ -959,6 +1448,288 @@ static int mag_block_integrals(xfk_problem *P, const unsigned char *sel, double 
     return XFK_OK;
 }
 
+// --- point values and contour integrals: host side ------------------------------
+
+// What the corner kernel and the search read of the mesh and the tables, once:
+// ConList, the grid's dimensions, the labels' "same material" classes and the
+// point currents
+static int mag_point_tables(xfk_problem *P)
+{
+    int rc = mag_prepare_xy(P);
+    if (rc != XFK_OK || P->mag_ctab_ready) return rc;
+    hipStream_t s = P->stream;
+    const int N = P->N, NE = P->NE;
+    std::vector<double> x(N), y(N);
+    std::vector<int> p(3 * (size_t)NE);
+    XFK_CHECK(d2h(x.data(), P->mag_x.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(y.data(), P->mag_y.p, sizeof(double) * N, s));
+    XFK_CHECK(d2h(p.data(), P->p_raw.p, sizeof(int) * 3 * (size_t)NE, s));
+    if ((rc = mag_conlist(P, p)) != XFK_OK) return rc;
+    pp_grid_dims(P, x.data(), y.data(), N, NE);
+    // the m++ test of fpproc.cpp:2725-2738 at Frequency 0: the same label, or
+    // equal mu_x, mu_y, H_c and direction (the same block and direction is a
+    // case of that).  A class is the first entry of the label table with these.
+    const size_t nlab = P->mag_hlab.size();
+    std::vector<int> clab(2 * std::max<size_t>(1, nlab), 0);
+    // (keyed on the values' bits with -0 folded into 0, which == does; an entry
+    // holding a NaN equals nothing, itself included, and is a class of its own)
+    std::map<std::array<unsigned long long, 5>, int> first;
+    for (size_t k = 0; k < nlab; ++k) {
+        const DevLabel &L = P->mag_hlab[k];
+        const DevBlock &B = P->mag_hblk[L.blk];
+        const double v[5] = {B.mu_x, B.mu_y, B.H_c, L.cos_m, L.sin_m};
+        std::array<unsigned long long, 5> key;
+        bool nan = false;
+        for (int j = 0; j < 5; ++j) {
+            const double d = v[j] == 0 ? 0. : v[j];
+            nan |= d != d;
+            std::memcpy(&key[j], &d, sizeof(d));
+        }
+        clab[2 * k] = P->mag_lab_orig[k];
+        clab[2 * k + 1] = nan ? (int)k : first.emplace(key, (int)k).first->second;
+    }
+    XFK_CHECK(upload(P->mag_clab, clab.data(), clab.size(), s));
+    XFK_CHECK(upload(P->mag_pj, P->mag_point_j.data(), (size_t)N, s));
+    XFK_CHECK(hipStreamSynchronize(s));   // (clab leaves scope)
+    P->mag_ctab_ready = true;
+    return XFK_OK;
+}
+
+static int mag_grid(xfk_problem *P)
+{
+    const int rc = mag_point_tables(P);
+    return rc != XFK_OK ? rc : pp_grid_build(P, P->mag_x.p, P->mag_y.p, P->p_raw.p);
+}
+
+static int mag_launch_element_b(xfk_problem *P)
+{
+    const int NE = P->NE, G = (NE + kBlock - 1) / kBlock;
+    const MagArgs M = mag_args(P);
+    if (P->axi) k_mag_element_b<true><<<G, kBlock, 0, P->stream>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
+    else k_mag_element_b<false><<<G, kBlock, 0, P->stream>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
+    return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
+}
+
+// the element flux density of the solution, kept with it
+static int mag_fields(xfk_problem *P)
+{
+    int rc = mag_prepare(P);
+    if (rc != XFK_OK || P->mag_B_ready) return rc;
+    XFK_CHECK(P->mag_B.alloc(2 * (size_t)P->NE));
+    if ((rc = mag_launch_element_b(P)) != XFK_OK) return rc;
+    P->mag_B_ready = true;
+    return XFK_OK;
+}
+
+static int mag_launch_corners(xfk_problem *P, unsigned char *branch)
+{
+    const int NE = P->NE, G = (int)((3 * (long long)NE + kBlock - 1) / kBlock);
+    const MagArgs M = mag_args(P);
+    const MagCornerArgs C = {P->mag_n2e_ptr.p, P->mag_n2e.p, P->mag_clab.p, P->mag_pj.p, P->mag_B.p, P->mag_B.p + NE};
+    if (P->axi) k_mag_corner<true><<<G, kBlock, 0, P->stream>>>(NE, M, C, P->mag_bc.p, branch);
+    else k_mag_corner<false><<<G, kBlock, 0, P->stream>>>(NE, M, C, P->mag_bc.p, branch);
+    return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
+}
+
+// ... and the smoothed corner values, made at the first smoothed request
+static int mag_corners(xfk_problem *P)
+{
+    int rc = mag_fields(P);
+    if (rc == XFK_OK) rc = mag_point_tables(P);
+    if (rc != XFK_OK || P->mag_corner_ready) return rc;
+    // (one thread per corner: 3 NE must fit the kernel's int index)
+    XFK_REQUIRE(P->NE <= 0x7fffffff / 3, XFK_ERR_ARG, "too many elements for the corner kernel (3 x elements >= 2^31)");
+    XFK_CHECK(P->mag_bc.alloc(6 * (size_t)P->NE));
+    if ((rc = mag_launch_corners(P, nullptr)) != XFK_OK) return rc;
+    P->mag_corner_ready = true;
+    return XFK_OK;
+}
+
+// what every point or contour request starts with: the refusals for the whole
+// problem and the per-label table (before any launch), then the fields
+static int mag_point_ready(xfk_problem *P, int smooth, bool grid)
+{
+    int rc = mag_labels(P, nullptr, true, true);
+    if (rc == XFK_OK) rc = smooth ? mag_corners(P) : mag_fields(P);
+    if (rc == XFK_OK && grid) rc = mag_grid(P);
+    return rc;
+}
+
+// the points on the device (pp_pts: x, y, then kMagPointVals values each; pp_pel)
+static int mag_upload_points(xfk_problem *P, int n, const double *x, const double *y)
+{
+    XFK_CHECK(P->pp_pts.alloc((2 + kMagPointVals) * (size_t)n));
+    XFK_CHECK(P->pp_pel.alloc((size_t)n));
+    XFK_CHECK(hipMemcpyAsync(P->pp_pts.p, x, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
+    XFK_CHECK(hipMemcpyAsync(P->pp_pts.p + n, y, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
+    return XFK_OK;
+}
+
+static int mag_launch_points(xfk_problem *P, int n, int smooth, int given)
+{
+    const MagArgs M = mag_args(P);
+    const PpGrid G = pp_grid_args(P);
+    const PpLists L = pp_lists(P);
+    const int g = (n + kBlock - 1) / kBlock;
+    const double *px = P->pp_pts.p;
+    double *o = P->pp_pts.p + 2 * (size_t)n;
+    if (P->axi)
+        k_mag_points<true><<<g, kBlock, 0, P->stream>>>(n, P->NE, M, G, L, px, px + n, smooth ? 1 : 0, P->mag_B.p,
+                                                        P->mag_bc.p, P->pp_pel.p, o, given);
+    else
+        k_mag_points<false><<<g, kBlock, 0, P->stream>>>(n, P->NE, M, G, L, px, px + n, smooth ? 1 : 0, P->mag_B.p,
+                                                         P->mag_bc.p, P->pp_pel.p, o, given);
+    return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
+}
+
+static int mag_contour_type_check(int type)
+{
+    XFK_REQUIRE(type >= 0 && type <= 5, XFK_ERR_ARG, "line integral type out of range: a magnetostatic problem has types 0-5");
+    return XFK_OK;
+}
+
+// types 1, 3, 4, 5: the batch on the device, the fields and the grid ready
+static int mag_contour_prepare(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, int type,
+                               int smooth, int npts, PpContours &J)
+{
+    int rc = mag_point_ready(P, smooth, true);
+    if (rc == XFK_OK) rc = pp_contour_layout(P, nc, ptr, x, y, type, smooth, npts, J);
+    return rc;
+}
+
+static int mag_contour_launch(xfk_problem *P, PpContours &J, double *dbg_xy, int *dbg_el)
+{
+    const MagArgs M = mag_args(P);
+    const PpGrid G = pp_grid_args(P);
+    const PpLists L = pp_lists(P);
+    hipStream_t s = P->stream;
+    const double *cx = J.d_xy.p, *cy = cx + J.cptr[J.nc];
+    if (P->axi)
+        k_mag_contour<true><<<J.groups(), kPotQBlock, 0, s>>>(J.nc, P->NE, M, G, L, J.d_cptr.p, J.d_bptr.p, cx, cy,
+                                                              J.npts, J.type, J.smooth, P->mag_B.p, P->mag_bc.p,
+                                                              J.part.p, dbg_xy, dbg_el);
+    else
+        k_mag_contour<false><<<J.groups(), kPotQBlock, 0, s>>>(J.nc, P->NE, M, G, L, J.d_cptr.p, J.d_bptr.p, cx, cy,
+                                                               J.npts, J.type, J.smooth, P->mag_B.p, P->mag_bc.p,
+                                                               J.part.p, dbg_xy, dbg_el);
+    launch_contour_sum(s, J);
+    XFK_CHECK(hipGetLastError());
+    return XFK_OK;
+}
+
+// the contour's length in metres, and on an axisymmetric problem its swept area (fpproc.cpp:4119-4130, 4200-4213)
+static void mag_contour_length(const xfk_problem *P, int n, const double *x, const double *y, double &len, double &area)
+{
+    const double lc = kMagLengthConv[P->length_units];
+    len = 0;
+    area = 0;
+    for (int i = 0; i < n - 1; ++i) len += mag_cabs_host(x[i + 1] - x[i], y[i + 1] - y[i]);
+    len *= lc;
+    if (P->axi) {
+        for (int i = 0; i < n - 1; ++i) area += (kPI * (x[i] + x[i + 1]) * mag_cabs_host(x[i + 1] - x[i], y[i + 1] - y[i]));
+        area *= std::pow(lc, 2.);
+    }
+}
+
+// LineIntegral type 0: A at the two end points through the point kernel, then the reference's arithmetic
+static int mag_contour_ends(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, double *out,
+                            int *missed)
+{
+    int rc = mag_point_ready(P, 0, true);
+    if (rc != XFK_OK) return rc;
+    const int n = 2 * nc;
+    std::vector<double> ex(n), ey(n), val(kMagPointVals * (size_t)n);
+    for (int c = 0; c < nc; ++c) {
+        ex[2 * c] = x[ptr[c]];
+        ey[2 * c] = y[ptr[c]];
+        ex[2 * c + 1] = x[ptr[c + 1] - 1];
+        ey[2 * c + 1] = y[ptr[c + 1] - 1];
+    }
+    if ((rc = mag_upload_points(P, n, ex.data(), ey.data())) != XFK_OK) return rc;
+    if ((rc = mag_launch_points(P, n, 0, 0)) != XFK_OK) return rc;
+    std::vector<int> el(n);
+    XFK_CHECK(d2h(el.data(), P->pp_pel.p, sizeof(int) * (size_t)n, P->stream));
+    XFK_CHECK(d2h(val.data(), P->pp_pts.p + 2 * (size_t)n, sizeof(double) * val.size(), P->stream));
+    for (int c = 0; c < nc; ++c) {
+        const double a0 = val[kMagPointVals * (size_t)(2 * c)], a1 = val[kMagPointVals * (size_t)(2 * c + 1)];
+        double l, area;
+        mag_contour_length(P, ptr[c + 1] - ptr[c], x + ptr[c], y + ptr[c], l, area);
+        double z0, z1 = 0.;
+        if (!P->axi) {
+            z0 = (a0 - a1) * P->mag_depth;
+            if (l != 0) z1 = z0 / (l * P->mag_depth);
+        } else {
+            z0 = a1 - a0;
+            if (area != 0) z1 = z0 / area;
+        }
+        out[2 * c] = z0;
+        out[2 * c + 1] = z1;
+        if (missed) missed[c] = (el[2 * c] < 0) + (el[2 * c + 1] < 0);
+    }
+    return XFK_OK;
+}
+
+static int mag_line_integrals(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, int type,
+                              int smooth, int npts, double *out, int *missed)
+{
+    int rc = mag_contour_type_check(type);
+    if (rc == XFK_OK) rc = pp_contour_check(nc, ptr, x, y);
+    if (rc != XFK_OK || nc == 0) return rc;
+    XFK_REQUIRE(out, XFK_ERR_ARG, "null output");
+    if (type == 0) return mag_contour_ends(P, nc, ptr, x, y, out, missed);
+    if (type == 2) {
+        for (int c = 0; c < nc; ++c) {
+            double l, area;
+            mag_contour_length(P, ptr[c + 1] - ptr[c], x + ptr[c], y + ptr[c], l, area);
+            out[2 * c] = l;
+            out[2 * c + 1] = P->axi ? area : l * P->mag_depth;
+            if (missed) missed[c] = 0;
+        }
+        return XFK_OK;
+    }
+    PpContours J;
+    if ((rc = mag_contour_prepare(P, nc, ptr, x, y, type, smooth, npts, J)) != XFK_OK) return rc;
+    if ((rc = mag_contour_launch(P, J, nullptr, nullptr)) != XFK_OK) return rc;
+    std::vector<double> sums(3 * (size_t)nc);
+    XFK_CHECK(d2h(sums.data(), J.sums(), sizeof(double) * sums.size(), P->stream));
+    for (int c = 0; c < nc; ++c) {
+        double r0 = sums[3 * (size_t)c], r1 = sums[3 * (size_t)c + 1];
+        // the averages of types 1 and 5, divided after the loop as the reference does
+        if (type == 1 || type == 5) {
+            double l, area;
+            mag_contour_length(P, ptr[c + 1] - ptr[c], x + ptr[c], y + ptr[c], l, area);
+            r1 = 0.;
+            if (l != 0) r1 = r0 / l;
+        }
+        out[2 * c] = r0;
+        out[2 * c + 1] = r1;
+        if (missed) missed[c] = (int)sums[3 * (size_t)c + 2];
+    }
+    return XFK_OK;
+}
+
+// f() between two events on the stream, repeats + 1 times (the first a warm-up): the median in ms
+template <class F>
+static int mag_timed(xfk_problem *P, int repeats, F f, double &out)
+{
+    ScopedEvents<2> ev;
+    XFK_CHECK(ev.create());
+    std::vector<double> t;
+    for (int k = 0; k <= repeats; ++k) {
+        XFK_CHECK(hipEventRecord(ev[0], P->stream));
+        const int r = f();
+        if (r != XFK_OK) return r;
+        XFK_CHECK(hipEventRecord(ev[1], P->stream));
+        XFK_CHECK(hipEventSynchronize(ev[1]));
+        float m = 0;
+        XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
+        if (k) t.push_back(m);
+    }
+    std::sort(t.begin(), t.end());
+    out = t[t.size() / 2];
+    return XFK_OK;
+}
+
 }  // namespace xfk
 
 using namespace xfk;
@@ -970,6 +1741,7 @@ int xfk_mag_set_solution(xfk_problem *P, const double *A)
     return mag_entry(P, [&]() -> int {
         XFK_REQUIRE(A, XFK_ERR_ARG, "null solution");
         P->mag_A_ready = false;
+        P->mag_B_ready = P->mag_corner_ready = false;
         P->mask_ready = false;   // (the reference clears bHasMask with a new solution)
         XFK_CHECK(P->mag_A.alloc((size_t)P->N));
         XFK_CHECK(hipMemcpyAsync(P->mag_A.p, A, sizeof(double) * P->N, hipMemcpyHostToDevice, P->stream));
@@ -1002,6 +1774,7 @@ int xfk_mag_element_b(xfk_problem *P, double *B1, double *B2)
         if (P->axi) k_mag_element_b<true><<<G, kBlock, 0, P->stream>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
         else k_mag_element_b<false><<<G, kBlock, 0, P->stream>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
         XFK_CHECK(hipGetLastError());
+        P->mag_B_ready = true;
         if (B1) XFK_CHECK(d2h(B1, P->mag_B.p, sizeof(double) * (size_t)NE, P->stream));
         if (B2) XFK_CHECK(d2h(B2, P->mag_B.p + NE, sizeof(double) * (size_t)NE, P->stream));
         XFK_CHECK(hipStreamSynchronize(P->stream));
@@ -1147,6 +1920,132 @@ int xfk_mag_stress_time(xfk_problem *P, int repeats, double *ms)
         std::sort(t.begin(), t.end());
         *ms = t[t.size() / 2];
         return XFK_OK;
+    });
+}
+
+int xfk_mag_corner_b(xfk_problem *P, double *b)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(b, XFK_ERR_ARG, "null output");
+        const int rc = mag_point_ready(P, 1, false);
+        if (rc != XFK_OK) return rc;
+        XFK_CHECK(d2h(b, P->mag_bc.p, sizeof(double) * 6 * (size_t)P->NE, P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_point_values(xfk_problem *P, int n, const double *x, const double *y, int smooth, int *elem, double *out)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of points");
+        if (n == 0) return XFK_OK;
+        XFK_REQUIRE(x && y && elem && out, XFK_ERR_ARG, "null point arrays");
+        int rc = mag_point_ready(P, smooth, true);
+        if (rc == XFK_OK) rc = mag_upload_points(P, n, x, y);
+        if (rc == XFK_OK) rc = mag_launch_points(P, n, smooth, 0);
+        if (rc != XFK_OK) return rc;
+        XFK_CHECK(d2h(elem, P->pp_pel.p, sizeof(int) * (size_t)n, P->stream));
+        XFK_CHECK(d2h(out, P->pp_pts.p + 2 * (size_t)n, sizeof(double) * kMagPointVals * (size_t)n, P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_point_values_at(xfk_problem *P, int n, const double *x, const double *y, const int *elem, int smooth,
+                            double *out)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of points");
+        if (n == 0) return XFK_OK;
+        XFK_REQUIRE(x && y && elem && out, XFK_ERR_ARG, "null point arrays");
+        for (int i = 0; i < n; ++i)
+            XFK_REQUIRE(elem[i] >= -1 && elem[i] < P->NE, XFK_ERR_ARG, "a point's element is outside the element range");
+        int rc = mag_point_ready(P, smooth, false);
+        if (rc == XFK_OK) rc = mag_upload_points(P, n, x, y);
+        if (rc != XFK_OK) return rc;
+        XFK_CHECK(hipMemcpyAsync(P->pp_pel.p, elem, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, P->stream));
+        if ((rc = mag_launch_points(P, n, smooth, 1)) != XFK_OK) return rc;
+        XFK_CHECK(d2h(out, P->pp_pts.p + 2 * (size_t)n, sizeof(double) * kMagPointVals * (size_t)n, P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_line_integrals(xfk_problem *P, int n_contours, const int *ptr, const double *x, const double *y, int type,
+                           int smooth, int npts, double *out, int *missed)
+{
+    return mag_entry(P, [&]() -> int {
+        return mag_line_integrals(P, n_contours, ptr, x, y, type, smooth, npts, out, missed);
+    });
+}
+
+int xfk_mag_line_integral(xfk_problem *P, int n, const double *x, const double *y, int type, int smooth, int npts,
+                          double *out2, int *missed)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of contour points");
+        const int ptr[2] = {0, n};
+        return mag_line_integrals(P, 1, ptr, x, y, type, smooth, npts, out2, missed);
+    });
+}
+
+int xfk_mag_contour_samples(xfk_problem *P, int n, const double *x, const double *y, int type, int npts, double *xy,
+                            int *elem)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of contour points");
+        const int ptr[2] = {0, n};
+        int rc = mag_contour_type_check(type);
+        if (rc == XFK_OK) rc = pp_contour_check(1, ptr, x, y);
+        if (rc != XFK_OK) return rc;
+        XFK_REQUIRE(type != 0 && type != 2, XFK_ERR_ARG, "line integral types 0 and 2 take no samples");
+        XFK_REQUIRE(xy && elem, XFK_ERR_ARG, "null output");
+        PpContours J;
+        if ((rc = mag_contour_prepare(P, 1, ptr, x, y, type, 0, npts, J)) != XFK_OK) return rc;
+        const size_t ns = (size_t)(n - 1) * J.npts;
+        DBuf<double> dxy;
+        DBuf<int> del;
+        XFK_CHECK(dxy.alloc(2 * ns));
+        XFK_CHECK(del.alloc(ns));
+        if ((rc = mag_contour_launch(P, J, dxy.p, del.p)) != XFK_OK) return rc;
+        XFK_CHECK(d2h(xy, dxy.p, sizeof(double) * 2 * ns, P->stream));
+        XFK_CHECK(d2h(elem, del.p, sizeof(int) * ns, P->stream));
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_point_time(xfk_problem *P, int n, const double *x, const double *y, int repeats, double *ms4)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(n > 0 && x && y && repeats > 0 && ms4, XFK_ERR_ARG,
+                    "xfk_mag_point_time needs points, repeats > 0 and its output");
+        int rc = mag_point_ready(P, 1, true);
+        if (rc != XFK_OK) return rc;
+        if ((rc = mag_timed(P, repeats, [&] { return mag_launch_corners(P, nullptr); }, ms4[0])) != XFK_OK) return rc;
+        rc = mag_timed(P, repeats, [&] {
+            P->pp_grid_ready = false;
+            return pp_grid_build(P, P->mag_x.p, P->mag_y.p, P->p_raw.p);
+        }, ms4[1]);
+        if (rc != XFK_OK) return rc;
+        if ((rc = mag_upload_points(P, n, x, y)) != XFK_OK) return rc;
+        for (int smooth = 0; smooth < 2; ++smooth)
+            if ((rc = mag_timed(P, repeats, [&] { return mag_launch_points(P, n, smooth, 0); }, ms4[2 + smooth])) != XFK_OK)
+                return rc;
+        return XFK_OK;
+    });
+}
+
+int xfk_mag_contour_time(xfk_problem *P, int n_contours, const int *ptr, const double *x, const double *y, int type,
+                         int smooth, int npts, int repeats, double *ms)
+{
+    return mag_entry(P, [&]() -> int {
+        XFK_REQUIRE(repeats > 0 && ms && n_contours > 0, XFK_ERR_ARG,
+                    "xfk_mag_contour_time needs contours, repeats > 0 and its output");
+        int rc = mag_contour_type_check(type);
+        if (rc == XFK_OK) rc = pp_contour_check(n_contours, ptr, x, y);
+        if (rc != XFK_OK) return rc;
+        XFK_REQUIRE(type != 0 && type != 2, XFK_ERR_ARG, "line integral types 0 and 2 launch no contour kernel");
+        PpContours J;
+        if ((rc = mag_contour_prepare(P, n_contours, ptr, x, y, type, smooth, npts, J)) != XFK_OK) return rc;
+        return mag_timed(P, repeats, [&] { return mag_contour_launch(P, J, nullptr, nullptr); }, *ms);
     });
 }
 

@@ -31,6 +31,8 @@
 
 #pragma clang fp contract(off)
 
+#include "xfk_ppsearch.h"
+
 namespace xfk {
 
 constexpr double kPpEo = 8.85418781762e-12;   // femmconstants.h:24
@@ -57,14 +59,6 @@ struct PpArgs {
     double depth;                  // Depth in m
     double ext_ro, ext_ri, ext_zo; // user units
 };
-
-// abs(CComplex) (femmcomplex.cpp:749-757)
-__host__ __device__ __forceinline__ double pp_cabs(double re, double im)
-{
-    if ((re == 0) && (im == 0)) return 0.;
-    if (fabs(re) > fabs(im)) return fabs(re) * sqrt(1. + (im / re) * (im / re));
-    return fabs(im) * sqrt(1. + (re / im) * (re / im));
-}
 
 // PostProcessor::Ctr: the thirds summed in corner order
 __device__ __forceinline__ void pp_ctr(const double (&X)[3], const double (&Y)[3], double &cx, double &cy)
@@ -662,19 +656,6 @@ __global__ void __launch_bounds__(kPotQBlock) k_pp_stress(int NE, PpArgs A, cons
 
 // --- the cell grid ----------------------------------------------------------
 
-struct PpGrid {
-    double x0, y0, ihx, ihy;
-    int nx, ny;
-};
-
-__device__ __forceinline__ int pp_cell1(double v, double v0, double ih, int n)
-{
-    const double f = floor((v - v0) * ih);
-    if (!(f > 0.)) return 0;
-    if (f >= (double)(n - 1)) return n - 1;
-    return (int)f;
-}
-
 // the cells an element's bounding box touches (the box widened by a hair, so
 // a point the edge tests accept through rounding finds the element too)
 __device__ __forceinline__ void pp_cells_of(const PpGrid &G, const double *__restrict__ x,
@@ -745,56 +726,6 @@ __global__ void __launch_bounds__(kPpScanBlock) k_pp_scan(int n, const int *__re
         ptr[i] = s;
         s += cnt[i];
     }
-}
-
-// InTriangleTest (PostProcessor.cpp:359-398) as written: every edge oriented
-// from its lower-numbered node, < 0 rejecting one way and > 0 the other
-__device__ __forceinline__ bool pp_in_triangle(const double *__restrict__ xs, const double *__restrict__ ys,
-                                               const int *__restrict__ p, int i, double x, double y)
-{
-    const int n[3] = {p[3 * i], p[3 * i + 1], p[3 * i + 2]};
-    const double X[3] = {xs[n[0]], xs[n[1]], xs[n[2]]}, Y[3] = {ys[n[0]], ys[n[1]], ys[n[2]]};
-    bool in = true;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int k = (j + 1) % 3;
-        if (n[k] > n[j]) {
-            const double z = (X[k] - X[j]) * (y - Y[j]) - (Y[k] - Y[j]) * (x - X[j]);
-            if (z < 0) in = false;
-        } else {
-            const double z = (X[j] - X[k]) * (y - Y[k]) - (Y[j] - Y[k]) * (x - X[k]);
-            if (z > 0) in = false;
-        }
-    }
-    return in;
-}
-
-// The cell grid and the oversize list as the search reads them
-struct PpLists {
-    const int *ptr, *cell_el, *big;
-    int nbig;
-};
-
-// The lowest-numbered element containing (x, y), or -1 when none does (or a
-// coordinate is NaN); ntests: the elements the point was tested against
-__device__ __forceinline__ int pp_find(const PpArgs &A, const PpGrid &G, const PpLists &L, double x, double y,
-                                       int &ntests)
-{
-    int k = 0x7fffffff;
-    ntests = 0;
-    if (x == x && y == y) {
-        const int c = pp_cell1(y, G.y0, G.ihy, G.ny) * G.nx + pp_cell1(x, G.x0, G.ihx, G.nx);
-        ntests = L.ptr[c + 1] - L.ptr[c] + L.nbig;
-        for (int m = L.ptr[c]; m < L.ptr[c + 1]; ++m) {
-            const int e = L.cell_el[m];
-            if (e < k && pp_in_triangle(A.x, A.y, A.p, e, x, y)) k = e;
-        }
-        for (int m = 0; m < L.nbig; ++m) {
-            const int e = L.big[m];
-            if (e < k && pp_in_triangle(A.x, A.y, A.p, e, x, y)) k = e;
-        }
-    }
-    return k == 0x7fffffff ? -1 : k;
 }
 
 // getPointValues(x, y, k) (epproc.cpp:434-469, hpproc.cpp:332-366) with
@@ -875,7 +806,7 @@ __global__ void __launch_bounds__(kBlock) k_pp_points(int n, PpArgs A, PpGrid G,
     const double x = px[t], y = py[t];
     int nt = 0;
     // given: elem[t] names the element on entry (checked by the host; -1: none)
-    const int k = given ? elem[t] : pp_find(A, G, L, x, y, nt);
+    const int k = given ? elem[t] : pp_find(A.x, A.y, A.p, G, L, x, y, nt);
     // (diagnostics: the elements this point is tested against)
     if (ntests) ntests[t] = nt;
     double *o = out + 8 * (size_t)t;
@@ -941,7 +872,7 @@ __global__ void __launch_bounds__(kPotQBlock) k_pp_contour(int nc, PpArgs A, PpG
             pty += ni * 1.e-06;
         }
         int nt;
-        const int el = pp_find(A, G, L, ptx, pty, nt);
+        const int el = pp_find(A.x, A.y, A.p, G, L, ptx, pty, nt);
         if (dbg_xy) {
             dbg_xy[2 * (size_t)j] = ptx;
             dbg_xy[2 * (size_t)j + 1] = pty;
@@ -1243,7 +1174,24 @@ static int pp_mesh(xfk_problem *P)
                 }
         }
     }
-    // the grid over the bounding box: cells of twice the mean element area
+    pp_grid_dims(P, x.data(), y.data(), N, NE);
+    hipError_t e = upload(P->pp_x, x.data(), x.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_y, y.data(), y.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_q, P->pot_qmark.data(), P->pot_qmark.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_n2e_ptr, ptr.data(), ptr.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_n2e, lst.data(), lst.size(), s);
+    if (e == hipSuccess) e = upload(P->pp_class, cls.data(), cls.size(), s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the host vectors go out of scope)
+    XFK_CHECK(e);
+    P->pp_mesh_ready = true;
+    return XFK_OK;
+}
+
+}  // namespace xfk
+
+// the grid over the bounding box: cells of twice the mean element area
+void xfk::pp_grid_dims(xfk_problem *P, const double *x, const double *y, int N, int NE)
+{
     double xa = x[0], xb = x[0], ya = y[0], yb = y[0];
     for (int i = 1; i < N; ++i) {
         xa = std::min(xa, x[i]);
@@ -1268,25 +1216,10 @@ static int pp_mesh(xfk_problem *P)
     P->pp_y0 = ya;
     P->pp_ihx = W > 0 ? nx / W : 0.;
     P->pp_ihy = H > 0 ? ny / H : 0.;
-    hipError_t e = upload(P->pp_x, x.data(), x.size(), s);
-    if (e == hipSuccess) e = upload(P->pp_y, y.data(), y.size(), s);
-    if (e == hipSuccess) e = upload(P->pp_q, P->pot_qmark.data(), P->pot_qmark.size(), s);
-    if (e == hipSuccess) e = upload(P->pp_n2e_ptr, ptr.data(), ptr.size(), s);
-    if (e == hipSuccess) e = upload(P->pp_n2e, lst.data(), lst.size(), s);
-    if (e == hipSuccess) e = upload(P->pp_class, cls.data(), cls.size(), s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the host vectors go out of scope)
-    XFK_CHECK(e);
-    P->pp_mesh_ready = true;
-    return XFK_OK;
-}
-
-static PpGrid pp_grid_args(const xfk_problem *P)
-{
-    return PpGrid{P->pp_x0, P->pp_y0, P->pp_ihx, P->pp_ihy, P->pp_nx, P->pp_ny};
 }
 
 // count, exclusive scan, fill -- once per problem
-static int pp_grid(xfk_problem *P)
+int xfk::pp_grid_build(xfk_problem *P, const double *x, const double *y, const int *p)
 {
     if (P->pp_grid_ready) return XFK_OK;
     hipStream_t s = P->stream;
@@ -1297,8 +1230,7 @@ static int pp_grid(xfk_problem *P)
     XFK_CHECK(P->pp_cell_ptr.alloc((size_t)nc + 1));
     XFK_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)nc + 1), s));
     const int g = (NE + kBlock - 1) / kBlock;
-    k_pp_grid<0><<<g, kBlock, 0, s>>>(NE, G, P->pp_x.p, P->pp_y.p, P->pot_p.p, cnt.p, nullptr, nullptr, cnt.p + nc,
-                                      nullptr);
+    k_pp_grid<0><<<g, kBlock, 0, s>>>(NE, G, x, y, p, cnt.p, nullptr, nullptr, cnt.p + nc, nullptr);
     k_pp_scan<<<1, kPpScanBlock, 0, s>>>(nc, cnt.p, P->pp_cell_ptr.p);
     XFK_CHECK(hipGetLastError());
     int total = 0, nbig = 0;
@@ -1307,14 +1239,18 @@ static int pp_grid(xfk_problem *P)
     XFK_CHECK(P->pp_cell_el.alloc((size_t)std::max(1, total)));
     XFK_CHECK(P->pp_big.alloc((size_t)std::max(1, nbig)));
     XFK_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)nc + 1), s));
-    k_pp_grid<1><<<g, kBlock, 0, s>>>(NE, G, P->pp_x.p, P->pp_y.p, P->pot_p.p, cnt.p, P->pp_cell_ptr.p,
-                                      P->pp_cell_el.p, cnt.p + nc, P->pp_big.p);
+    k_pp_grid<1><<<g, kBlock, 0, s>>>(NE, G, x, y, p, cnt.p, P->pp_cell_ptr.p, P->pp_cell_el.p, cnt.p + nc,
+                                      P->pp_big.p);
     XFK_CHECK(hipGetLastError());
     XFK_CHECK(hipStreamSynchronize(s));
     P->pp_nbig = nbig;
     P->pp_grid_ready = true;
     return XFK_OK;
 }
+
+namespace xfk {
+
+static int pp_grid(xfk_problem *P) { return pp_grid_build(P, P->pp_x.p, P->pp_y.p, P->pot_p.p); }
 
 static int pp_fields(xfk_problem *P)
 {
@@ -1444,11 +1380,6 @@ static int pp_entry(xfk_problem *P, bool need_solution, F &&body)
         set_error("post-processing failed: unknown exception");
         return XFK_ERR_ARG;
     }
-}
-
-static PpLists pp_lists(const xfk_problem *P)
-{
-    return PpLists{P->pp_cell_ptr.p, P->pp_cell_el.p, P->pp_big.p, P->pp_nbig};
 }
 
 static int pp_launch_points(xfk_problem *P, int n, const double *px, const double *py, int smooth, double *o,
@@ -1711,19 +1642,6 @@ static int pp_stress_integrals(xfk_problem *P, double *out3)
 
 // --- contour integrals: host side ---------------------------------------------
 
-constexpr int kPpLineIntegralPoints = 400;   // d_LineIntegralPoints (PostProcessor.cpp:76)
-
-// A batch of contours checked and laid out for k_pp_contour
-struct PpContours {
-    int nc = 0, type = 0, smooth = 0, npts = 0;
-    std::vector<int> cptr, bptr;   // vertices and workgroups of each contour
-    DBuf<int> d_cptr, d_bptr;
-    DBuf<double> d_xy;             // the vertices: all x, then all y
-    DBuf<double> part;             // 3 per workgroup, then 3 per contour
-    int groups() const { return bptr.empty() ? 0 : bptr.back(); }
-    double *sums() { return part.p + 3 * (size_t)groups(); }
-};
-
 static int pp_contour_check(const xfk_problem *P, int nc, const int *ptr, const double *x, const double *y,
                             int type)
 {
@@ -1733,6 +1651,12 @@ static int pp_contour_check(const xfk_problem *P, int nc, const int *ptr, const 
                 "line integral type out of range: a heat-flow problem has types 0-3 (the stress tensor force and "
                 "torque, 3 and 4, are electrostatic)");
     XFK_REQUIRE(!P->electro || type <= 4, XFK_ERR_ARG, "line integral type out of range: an electrostatic problem has types 0-4");
+    return pp_contour_check(nc, ptr, x, y);
+}
+
+int xfk::pp_contour_check(int nc, const int *ptr, const double *x, const double *y)
+{
+    XFK_REQUIRE(nc >= 0, XFK_ERR_ARG, "negative number of contours");
     if (nc == 0) return XFK_OK;
     XFK_REQUIRE(ptr && x && y, XFK_ERR_ARG, "null contour arrays");
     XFK_REQUIRE(ptr[0] >= 0, XFK_ERR_ARG, "contour offsets must start at 0 or above and not decrease");
@@ -1752,9 +1676,8 @@ static int pp_contour_check(const xfk_problem *P, int nc, const int *ptr, const 
     return XFK_OK;
 }
 
-// types 1, 3, 4 (heat flow: 1, 3): the batch on the device, the fields and the grid ready
-static int pp_contour_prepare(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, int type,
-                              int smooth, int npts, PpContours &J)
+int xfk::pp_contour_layout(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, int type,
+                           int smooth, int npts, PpContours &J)
 {
     hipStream_t s = P->stream;
     J.nc = nc;
@@ -1772,9 +1695,6 @@ static int pp_contour_prepare(xfk_problem *P, int nc, const int *ptr, const doub
         J.cptr[c + 1] = ptr[c + 1] - ptr[0];
         J.bptr[c + 1] = (int)groups;
     }
-    int rc = J.smooth ? pp_corners(P, nullptr) : pp_fields(P);
-    if (rc == XFK_OK) rc = pp_grid(P);
-    if (rc != XFK_OK) return rc;
     const size_t nv = (size_t)J.cptr[nc];
     XFK_CHECK(J.d_xy.alloc(2 * nv));
     XFK_CHECK(hipMemcpyAsync(J.d_xy.p, x + ptr[0], sizeof(double) * nv, hipMemcpyHostToDevice, s));
@@ -1783,6 +1703,21 @@ static int pp_contour_prepare(xfk_problem *P, int nc, const int *ptr, const doub
     XFK_CHECK(upload(J.d_bptr, J.bptr.data(), J.bptr.size(), s));
     XFK_CHECK(J.part.alloc(3 * ((size_t)groups + nc)));
     return XFK_OK;
+}
+
+void xfk::launch_contour_sum(hipStream_t s, PpContours &J)
+{
+    k_pp_contour_sum<<<J.nc, kPotQBlock, 0, s>>>(J.d_bptr.p, J.part.p, J.sums());
+}
+
+// types 1, 3, 4 (heat flow: 1, 3): the batch on the device, the fields and the grid ready
+static int pp_contour_prepare(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, int type,
+                              int smooth, int npts, PpContours &J)
+{
+    int rc = pp_contour_layout(P, nc, ptr, x, y, type, smooth, npts, J);
+    if (rc == XFK_OK) rc = J.smooth ? pp_corners(P, nullptr) : pp_fields(P);
+    if (rc == XFK_OK) rc = pp_grid(P);
+    return rc;
 }
 
 // the sample kernel and the per-contour sums; dbg_xy, dbg_el: one contour's samples (may be null)
@@ -1801,7 +1736,7 @@ static int pp_contour_launch(xfk_problem *P, PpContours &J, double *dbg_xy, int 
         k_pp_contour<false><<<J.groups(), kPotQBlock, 0, s>>>(J.nc, A, G, L, J.d_cptr.p, J.d_bptr.p, cx, cy, J.npts,
                                                               J.type, J.smooth, P->pp_D.p, P->pp_d.p, J.part.p, dbg_xy,
                                                               dbg_el);
-    k_pp_contour_sum<<<J.nc, kPotQBlock, 0, s>>>(J.d_bptr.p, J.part.p, J.sums());
+    launch_contour_sum(s, J);
     XFK_CHECK(hipGetLastError());
     return XFK_OK;
 }

@@ -69,6 +69,8 @@ EXPORTED = (
     "xfk_mag_set_solution", "xfk_mag_set_depth", "xfk_mag_element_b", "xfk_mag_block_integrals",
     "xfk_mag_block_integral", "xfk_mag_time",
     "xfk_mag_make_mask", "xfk_mag_get_mask", "xfk_mag_mask_info", "xfk_mag_mask_problem", "xfk_mag_stress_time",
+    "xfk_mag_corner_b", "xfk_mag_point_values", "xfk_mag_point_values_at", "xfk_mag_line_integrals",
+    "xfk_mag_line_integral", "xfk_mag_contour_samples", "xfk_mag_point_time", "xfk_mag_contour_time",
     "xfk_amg_probe_create", "xfk_amg_probe_info", "xfk_amg_probe_level_size", "xfk_amg_probe_level_csr",
     "xfk_amg_probe_tiles", "xfk_amg_probe_vector", "xfk_amg_probe_trace", "xfk_amg_probe_apply",
     "xfk_amg_probe_refresh", "xfk_amg_probe_destroy",
@@ -358,6 +360,14 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_mag_mask_info.argtypes = [C.c_void_p, dptr]
     L.xfk_mag_mask_problem.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.xfk_mag_stress_time.argtypes = [C.c_void_p, C.c_int, dptr]
+    L.xfk_mag_corner_b.argtypes = [C.c_void_p, dptr]
+    L.xfk_mag_point_values.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, iptr, dptr]
+    L.xfk_mag_point_values_at.argtypes = [C.c_void_p, C.c_int, dptr, dptr, iptr, C.c_int, dptr]
+    L.xfk_mag_line_integrals.argtypes = [C.c_void_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_int, C.c_int, dptr, iptr]
+    L.xfk_mag_line_integral.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, C.c_int, C.c_int, dptr, iptr]
+    L.xfk_mag_contour_samples.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, C.c_int, dptr, iptr]
+    L.xfk_mag_point_time.argtypes = [C.c_void_p, C.c_int, dptr, dptr, C.c_int, dptr]
+    L.xfk_mag_contour_time.argtypes = [C.c_void_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_int, C.c_int, C.c_int, dptr]
     L.xfk_sort_elements.argtypes = [C.c_int, C.POINTER(C.c_uint), C.c_int, iptr]
     L.xfk_magdir_eval.argtypes = [C.c_char_p, C.c_int, iptr, dptr, dptr, C.c_int, C.c_double, dptr]
     L.xfk_lua_run.argtypes = [C.c_char_p, C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong)]
@@ -567,8 +577,9 @@ def age_element_matrix(ci: float, co: float, K: float, Ki: float) -> np.ndarray:
 
 class _MagPostProc:
     """Post-processing of a magnetostatic problem (the xfk_mag_ entry points):
-    fpproc's element flux density, its block integrals that need no mask, and
-    the weighted stress tensor force and torque (types 18-23) over its mask.
+    fpproc's element flux density, its block integrals that need no mask, the
+    weighted stress tensor force and torque (types 18-23) over its mask, and
+    its point values and contour integrals.
     The subclass provides _h, n_nodes, n_elems and n_labels.  A harmonic or a
     sharded problem is refused by the library with its cause."""
 
@@ -724,6 +735,125 @@ class _MagPostProc:
         ms = C.c_double()
         _check(_lib.xfk_mag_stress_time(self._h, int(repeats), C.byref(ms)))
         return ms.value
+
+    # -- point values and contour integrals (GetNodalB, GetPointValues, LineIntegral) --
+
+    # the values of xfk_mag_point_values per point, in its order
+    MAG_POINT_NAMES = ("A", "B1", "B2", "mu1", "mu2", "H1", "H2", "Js", "c", "E", "Hc_re", "Hc_im", "ff")
+
+    def corner_b(self) -> np.ndarray:
+        """GetNodalB of every element, (n_elems, 3, 2): (b1, b2) of its
+        corners (xfk_mag_corner_b)."""
+        b = np.zeros(6 * max(1, self.n_elems))
+        _check(_lib.xfk_mag_corner_b(self._h, b.ctypes.data_as(dptr)))
+        return b[:6 * self.n_elems].reshape(-1, 3, 2)
+
+    @staticmethod
+    def _mag_points(x, y):
+        x = np.ascontiguousarray(np.atleast_1d(x), dtype=np.float64)
+        y = np.ascontiguousarray(np.atleast_1d(y), dtype=np.float64)
+        if x.shape != y.shape or x.ndim != 1:
+            raise ValueError("x and y must be one-dimensional and of one length")
+        return x, y
+
+    def _mag_point_dict(self, el, o):
+        r = {"elem": el, "raw": o}
+        for k, name in enumerate(self.MAG_POINT_NAMES):
+            r[name] = o[:, k].copy()
+        r["Hc"] = r.pop("Hc_re") + 1j * r.pop("Hc_im")
+        # 0 at Frequency 0; the keys of mo_getpointvalues
+        for name in ("Je", "Ph", "Pe"):
+            r[name] = np.zeros(len(el))
+        return r
+
+    def point_values(self, x, y, smooth: bool = True) -> dict:
+        """GetPointValues at the points (x, y), in the problem's length units:
+        elem (the lowest-numbered containing element, -1 outside the mesh: its
+        values are NaN), raw (n, 13) and the reference's point-value fields by
+        name (MAG_POINT_NAMES, Hc complex; Je, Ph and Pe are 0 at Frequency 0)."""
+        x, y = self._mag_points(x, y)
+        n = len(x)
+        el = np.zeros(max(1, n), np.int32)
+        o = np.zeros((max(1, n), 13))
+        _check(_lib.xfk_mag_point_values(self._h, n, x.ctypes.data_as(dptr), y.ctypes.data_as(dptr), int(bool(smooth)),
+                                         el.ctypes.data_as(iptr), o.ctypes.data_as(dptr)))
+        return self._mag_point_dict(el[:n], o[:n])
+
+    def point_values_at(self, x, y, elem, smooth: bool = True) -> dict:
+        """point_values with the element of every point given (xfk_mag_point_values_at)."""
+        x, y = self._mag_points(x, y)
+        el = np.ascontiguousarray(np.atleast_1d(elem), dtype=np.int32)
+        n = len(x)
+        o = np.zeros((max(1, n), 13))
+        _check(_lib.xfk_mag_point_values_at(self._h, n, x.ctypes.data_as(dptr), y.ctypes.data_as(dptr),
+                                            el.ctypes.data_as(iptr), int(bool(smooth)), o.ctypes.data_as(dptr)))
+        return self._mag_point_dict(el[:n], o[:n])
+
+    @staticmethod
+    def _mag_contours(contours):
+        xy = [_PotentialPostProc._contour_xy(c) for c in contours]
+        ptr = np.zeros(len(xy) + 1, np.int32)
+        ptr[1:] = np.cumsum([len(x) for x, _ in xy])
+        x = np.ascontiguousarray(np.concatenate([x for x, _ in xy] + [np.zeros(1)]))
+        y = np.ascontiguousarray(np.concatenate([y for _, y in xy] + [np.zeros(1)]))
+        return len(xy), ptr, x, y
+
+    def line_integrals(self, contours, kind: int, smooth: bool = True, points: int = 400) -> dict:
+        """fpproc's LineIntegral of type `kind` (0 B.n, 1 H.t, 2 length, 3
+        stress tensor force, 4 torque, 5 (B.n)^2) over a batch of contours:
+        each a Contour, a sequence of (x, y) or of complex points, in the
+        problem's length units.  raw: (n, 2), the two results per contour;
+        missed: per contour the samples no element contains (they add
+        nothing).  Every contour's result has the bits it has when integrated
+        alone.  Type 4 is 0 on an axisymmetric problem."""
+        n, ptr, x, y = self._mag_contours(contours)
+        o = np.zeros((max(1, n), 2))
+        missed = np.zeros(max(1, n), np.int32)
+        _check(_lib.xfk_mag_line_integrals(self._h, n, ptr.ctypes.data_as(iptr), x.ctypes.data_as(dptr),
+                                           y.ctypes.data_as(dptr), int(kind), int(bool(smooth)), int(points),
+                                           o.ctypes.data_as(dptr), missed.ctypes.data_as(iptr)))
+        return {"raw": o[:n], "missed": missed[:n]}
+
+    def line_integral(self, contour, kind: int, smooth: bool = True, points: int = 400) -> complex:
+        """One contour's LineIntegral of type `kind`: the two results as a
+        complex number (xfk_mag_line_integral)."""
+        x, y = _PotentialPostProc._contour_xy(contour)
+        o = np.zeros(2)
+        _check(_lib.xfk_mag_line_integral(self._h, len(x), x.ctypes.data_as(dptr), y.ctypes.data_as(dptr), int(kind),
+                                          int(bool(smooth)), int(points), o.ctypes.data_as(dptr), None))
+        return complex(o[0], o[1])
+
+    def contour_samples(self, contour, kind: int, points: int = 400) -> dict:
+        """Diagnostic: the samples of one contour as the kernel makes them, xy
+        (n, 2) and the element each took, -1 for none (xfk_mag_contour_samples)."""
+        x, y = _PotentialPostProc._contour_xy(contour)
+        ns = max(0, len(x) - 1) * (int(points) if points > 0 else 400)
+        xy = np.zeros((max(1, ns), 2))
+        el = np.zeros(max(1, ns), np.int32)
+        _check(_lib.xfk_mag_contour_samples(self._h, len(x), x.ctypes.data_as(dptr), y.ctypes.data_as(dptr), int(kind),
+                                            int(points), xy.ctypes.data_as(dptr), el.ctypes.data_as(iptr)))
+        return {"xy": xy[:ns], "elem": el[:ns]}
+
+    def time_points(self, x, y, repeats: int = 5) -> dict:
+        """Diagnostic: HIP-event ms (medians after a warm-up) of the corner
+        kernel, the cell grid and the point kernel on these points with
+        smoothing off and on (xfk_mag_point_time)."""
+        x, y = self._mag_points(x, y)
+        ms = np.zeros(4)
+        _check(_lib.xfk_mag_point_time(self._h, len(x), x.ctypes.data_as(dptr), y.ctypes.data_as(dptr), int(repeats),
+                                       ms.ctypes.data_as(dptr)))
+        return dict(corner=float(ms[0]), grid=float(ms[1]), points=float(ms[2]), points_smooth=float(ms[3]))
+
+    def time_contours(self, contours, kind: int, smooth: bool = True, points: int = 400, repeats: int = 5) -> float:
+        """Diagnostic: HIP-event ms (median) of the contour kernel and its sums
+        over the batch (xfk_mag_contour_time)."""
+        n, ptr, x, y = self._mag_contours(contours)
+        ms = C.c_double()
+        _check(_lib.xfk_mag_contour_time(self._h, n, ptr.ctypes.data_as(iptr), x.ctypes.data_as(dptr),
+                                         y.ctypes.data_as(dptr), int(kind), int(bool(smooth)), int(points),
+                                         int(repeats), C.byref(ms)))
+        return ms.value
+
 
 
 class Static2DProblem(_MagPostProc):
