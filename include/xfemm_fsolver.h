@@ -47,9 +47,10 @@ int xfemm_fsolver_set_delete_mesh_files(xfemm_fsolver *s, int delete_files);
  * files (after the collective solve, so every rank has read them).  The
  * communicator stays the caller's.  NULL: one device (the default). */
 int xfemm_fsolver_set_comm(xfemm_fsolver *s, xfk_comm *comm);
-/* keep != 0: a static single-device solve leaves its solved device problem
- * alive, with the .fem's [Depth] set (xfk_mag_set_depth), for the xfk_mag_
- * post-processing entry points of xfemm_kernels.h; xfemm_fsolver_problem
+/* keep != 0: a single-device solve leaves its solved device problem alive,
+ * with the .fem's [Depth] set (xfk_mag_set_depth), for the post-processing
+ * entry points of xfemm_kernels.h (xfk_mag_ after a static solve, xfk_mag_ac_
+ * after a harmonic one); xfemm_fsolver_problem
  * returns it (NULL: none).  The solver owns it: it is destroyed by the next
  * solve and with the solver. */
 int xfemm_fsolver_set_keep_problem(xfemm_fsolver *s, int keep);

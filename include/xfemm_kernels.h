@@ -401,6 +401,9 @@ typedef struct {
                                       permeability of a wound region of a LamType > 2 block
                                       (harmonic2d.cpp:664-668); read for those labels only;
                                       NULL: 1 for every label */
+    int prev_type;              /* [PrevType] of the file the problem was loaded from (0: none).  The
+                                   solve does not read it; xfk_mag_ac_* refuses a problem with
+                                   prev_type != 0 (incremental permeability is not post-processed) */
 } xfk_harmonic_desc;
 
 int xfk_problem_create_harmonic(const xfk_problem_desc *desc, const xfk_harmonic_desc *ac, int device,
@@ -883,6 +886,62 @@ int xfk_mag_element_b(xfk_problem *prob, double *B1, double *B2);
 int xfk_mag_block_integrals(xfk_problem *prob, const unsigned char *label_selected, double *out);
 int xfk_mag_block_integral(xfk_problem *prob, const unsigned char *label_selected, int type, double *out2);
 int xfk_mag_time(xfk_problem *prob, int repeats, double *ms);
+
+/* ---------------------------------------------------------------------------
+ * Post-processing of a time-harmonic problem (xfk_problem_create_harmonic,
+ * planar or axisymmetric, one device): the complex element flux density and
+ * fpproc's block integrals at Frequency != 0 (FPProc::GetElementB,
+ * fpproc.cpp:2970-3082; GetJA, 3495-3578; BlockIntegral, 3642-3963;
+ * OpenDocument's mu_fdx / mu_fdy, 1703-1758; CMMaterialProp::GetMu(CComplex)
+ * and GetH(CComplex), CMaterialProp.cpp:722-772, 493-519), after xfk_harmonic2d
+ * or xfk_mag_ac_set_solution.  The entry points above keep refusing a harmonic
+ * problem; these refuse a static one.  fpproc's arithmetic in its operation
+ * order; the sums per workgroup, then over the workgroups in a fixed order: a
+ * call repeats bit for bit.  Depth: xfk_mag_set_depth.
+ *
+ * A label's Case / J / dVolts are the solve's circuit results
+ * (xfk_get_circuits_complex), as the .ans label lines carry them: a Case-2
+ * circuit (a specified current in a conducting region) is written as Case 0
+ * with its solved voltage gradient (harmonic2d.cpp:988-990).  A nonlinear
+ * block's permeability is evaluated over the curve the descriptor carries
+ * (GetSlopes(omega)).  Where the label's conductivity is 0, fpproc's
+ * sig = 1e6 / Re(1 / o) of type 4 is 0 / 0; no loss is added there.
+ *
+ * xfk_mag_ac_set_solution: A[2 n_nodes], interleaved (re, im), as the .ans
+ * carries it (what xfk_get_solution_complex returns) replaces the solution for
+ * post-processing; the next xfk_harmonic2d replaces it again.
+ * xfk_mag_ac_element_b: B1[2 n_elems], B2[2 n_elems], interleaved (either may
+ * be NULL); answered whatever the blocks are.
+ * xfk_mag_ac_block_integrals: label_selected[n_labels]; out[52]: (re, im) of
+ * inttype 0 .. 25:
+ *    0 A.conj(J)        1 A                 2 stored energy (time average)
+ *    3 hysteresis and lamination loss       4 resistive loss     5 area
+ *    6 total loss (3 + 4)                   7 total current      8 9 B over the volume
+ *   10 volume          11 12 steady Lorentz force (11: 0 when axisymmetric)
+ *   13 14 double-frequency Lorentz force (13: planar only)
+ *   15 steady Lorentz torque, 16 its double-frequency part (planar only)
+ *   17 coenergy (= 2)  24 moment of inertia 25 centroid (0 / 0 = NaN with nothing selected)
+ * Types 18-23 need the weighted stress tensor mask, which stays refused for
+ * harmonic problems: they are answered with 0.
+ * xfk_mag_ac_block_integral: one type into out2[2].
+ * xfk_mag_ac_time: HIP-event ms of the element-B launch (ms[0]) and of the
+ * integral launch with its sum, every answerable label selected (ms[1]): the
+ * median of `repeats` runs after a warm-up.
+ *
+ * Refused before any launch, with the cause in xfk_last_error, the problem
+ * staying usable: a static problem ("use xfk_mag_*") and a scalar-potential
+ * problem (XFK_ERR_ARG); a sharded problem and one created with
+ * prev_type != 0 (XFK_ERR_UNSUPPORTED); no solution yet and none set
+ * (XFK_ERR_ARG); by both integral calls and for every type, a selection holding
+ * a label whose block has LamType > 2 (XFK_ERR_UNSUPPORTED: its J, conductivity
+ * and permeability need FPProc::GetFillFactor, whose wire data the descriptor
+ * does not carry); an unknown type (XFK_ERR_ARG).
+ * ------------------------------------------------------------------------- */
+int xfk_mag_ac_set_solution(xfk_problem *prob, const double *A_re_im);
+int xfk_mag_ac_element_b(xfk_problem *prob, double *B1_re_im, double *B2_re_im);
+int xfk_mag_ac_block_integrals(xfk_problem *prob, const unsigned char *label_selected, double *out);
+int xfk_mag_ac_block_integral(xfk_problem *prob, const unsigned char *label_selected, int type, double *out2);
+int xfk_mag_ac_time(xfk_problem *prob, int repeats, double *ms);
 
 /* The weighted stress tensor force and torque of a magnetostatic problem:
  * fpproc's block integrals 18-23 (fpproc.cpp:3966-4079, HenrotteVector

@@ -702,7 +702,12 @@ int FSolver::Harmonic2D()
         prox[2 * k + 1] = labellist[k].ProxMu_im;
     }
     xfk_harmonic_desc ac{Frequency, bac.data(), lac.empty() ? nullptr : lac.data(),
-                         cac.empty() ? nullptr : cac.data(), ACSolver, prox.data()};
+                         cac.empty() ? nullptr : cac.data(), ACSolver, prox.data(),
+                         previousSolutionFile.empty() ? 0 : PrevType};
+    if (problem) {   // (a kept problem of the last solve)
+        xfk_problem_destroy(problem);
+        problem = nullptr;
+    }
     xfk_problem *prob = nullptr;
     int rc = comm ? xfk_problem_create_harmonic_dist(&ds.d, &ac, device, comm, &prob)
                   : xfk_problem_create_harmonic(&ds.d, &ac, device, &prob);
@@ -735,6 +740,10 @@ int FSolver::Harmonic2D()
         }
     }
     if (rc != XFK_OK) warn(std::string("GPU solver error: ") + xfk_last_error() + "\n");
+    if (rc == XFK_OK && keepProblem && !comm && xfk_mag_set_depth(prob, Depth) == XFK_OK) {
+        problem = prob;   // post-processed by the caller (the xfk_mag_ac_ entry points)
+        prob = nullptr;
+    }
     if (prob) xfk_problem_destroy(prob);
     ms_phase[3] = ms_since(t);
     return rc == XFK_OK;

@@ -1530,6 +1530,7 @@ int create_harmonic(const xfk_problem_desc *d, const xfk_harmonic_desc *ac, int 
     P->ext_ri = G.ext_ri;
     P->ext_zo = G.ext_zo;
     P->hcircs = circ;
+    if (!comm) mag_ac_host_tables(P, d, ac, G, blk);   // (post-processing: xfk_magpost_ac.hip)
     P->nhpt = (int)pt_nodes.size();
     hipStream_t s = P->stream;
     hipError_t e = hipSuccess;
@@ -1596,6 +1597,7 @@ static int harmonic2d_run(xfk_problem *P, int flags, xfk_result *res)
     XFK_REQUIRE(P && P->harmonic, XFK_ERR_ARG, "not a harmonic problem (xfk_problem_create_harmonic)");
     XFK_CHECK(hipSetDevice(P->device));
     hipStream_t s = P->stream;
+    P->mag_A_ready = false;   // (xfk_magpost_ac.hip: its A no longer belongs to the solution)
     ScopedEvents<3> ev;
     XFK_CHECK(ev.create());
     hipEvent_t e0 = ev[0], e1 = ev[1], e2 = ev[2];

@@ -195,6 +195,20 @@ struct DevCircAC {
     int ccase, pad;
 };
 
+// A block as fpproc holds it at Frequency != 0 (xfk_magpost_ac.hip): mu_fdx,
+// mu_fdy of OpenDocument (fpproc.cpp:1703-1758), the complex source current,
+// the bulk conductivity GetJA and the resistive loss read (0 in an in-plane
+// lamination with Lam_d != 0), and the block's knots in the problem's
+// complex curve tables (hbh_B, hbh_H, hbh_S)
+struct MagAcBlock {
+    double2 mu_fdx, mu_fdy;
+    double2 J;          // MA/m^2
+    double Cduct;       // MS/m, as the block carries it
+    int lam;            // Lam_d != 0 && LamType == 0
+    int LamType;
+    int bh_n, bh_off;
+};
+
 // State of the complex-symmetric Chronopoulos-Gear COCG (xfk_harmonic.hip)
 struct CcgState {
     double bb;            // |b|^2
@@ -696,6 +710,15 @@ struct xfk_problem {
     xfk::DBuf<int> mag_clab;                     // per entry of the label table: the descriptor's label, its "same material" class
     xfk::DBuf<unsigned char> mag_pj;             // N: mag_point_j
 
+    // post-processing of a time-harmonic problem (xfk_magpost_ac.hip): the
+    // mag_ group above holds the rest -- the host tables (filled when the
+    // problem is created), the coordinates, Depth, and with twice the length
+    // mag_A (interleaved re, im), mag_B (B1 then B2, each interleaved) and
+    // mag_part; mag_A_ready is cleared by harmonic2d_run
+    std::vector<xfk::MagAcBlock> mag_ac_hblk;    // host: per block what fpproc derives at Frequency != 0
+    int mag_prev_type = 0;                       // [PrevType] of the descriptor: != 0 is refused
+    xfk::DBuf<xfk::MagAcBlock> mag_ac_blk;       // the same on the device
+
     // live SpMV launch timing (XFK_TIME_SPMV)
     bool time_spmv = false;
     std::vector<hipEvent_t> spmv_ev;   // pairs
@@ -813,6 +836,11 @@ int mask_aux_solve(xfk_problem *P, xfk_result *res);
 void mask_set_info(xfk_problem *P, const xfk_result &res, double ms_create, double ms_rules, double ms_total);
 int launch_mask_exterior(hipStream_t s, int N, int NE, const int *p, const int *n2e_ptr, const int *n2e,
                          unsigned char *ext);
+// xfk_magpost_ac.hip: the host tables a harmonic problem's post-processing
+// reads (the mag_ group of P), from the descriptors it is created from; blk:
+// the solver's block table (its knots in the complex curve tables)
+void mag_ac_host_tables(xfk_problem *P, const xfk_problem_desc *d, const xfk_harmonic_desc *ac, const GlobalPrep &G,
+                        const std::vector<DevBlockAC> &blk);
 // wall-clock milliseconds since t0
 inline double wall_ms(std::chrono::steady_clock::time_point t0)
 {

@@ -34,6 +34,9 @@
 
 #pragma clang fp contract(off)
 
+// (what the time-harmonic post-processor, xfk_magpost_ac.hip, reads too: the
+// unit tables, MagLabel, MagArgs, GetElementB, Ctr, ElmArea, AECF, k_mag_xy)
+#include "xfk_magpost.h"
 #include "xfk_ppsearch.h"
 
 #include <array>
@@ -42,92 +45,14 @@
 
 namespace xfk {
 
-// FPProc's LengthConv[]: user length units -> m; and the solver's: -> cm
-static const double kMagLengthConv[] = {0.0254, 0.001, 0.01, 1., 2.54e-5, 1.e-6};
-static const double kMagUnitCm[] = {2.54, 0.1, 1., 100., 0.00254, 1.e-04};
-
 // the sums one pass makes, in this order
 enum {
     MS_AJ, MS_A, MS_ENERGY, MS_AREA, MS_CURRENT, MS_B1, MS_B2, MS_VOLUME, MS_FX, MS_FY, MS_TORQUE, MS_COENERGY,
     MS_INERTIA, MS_CX, MS_CY, kMagSums
 };
-constexpr int kMagTypes = 26;   // inttype 0 .. 25
-
-// What GetJA and the energy read of a block label: the circuit columns are
-// the ones the .ans label lines carry (fpproc.cpp:1289-1308)
-struct MagLabel {
-    double J, dV;           // blocklist[lbl].J (Case 1), dVolts (Case 0)
-    double cos_m, sin_m;    // exp(I PI magdir / 180)
-    int blk;
-    int ccase;              // blocklist[lbl].Case; -1: InCircuit < 0
-    int wound;              // FillFactor > 0: no bulk conductivity
-    int external;
-    int sel;
-    int pad;
-};
-
-struct MagArgs {
-    const double *x, *y, *A;       // user length units; the .ans solution
-    const int *p, *lbl;
-    const MagLabel *labels;
-    const DevBlock *blocks;
-    const double *bhB, *bhH, *bhS;
-    double lc, lc2;                // LengthConv[LengthUnits] and its pow(., 2.)
-    double depth;                  // Depth in m
-    double ext_ro, ext_ri, ext_zo; // user units
-};
 
 // abs(CComplex) (femmcomplex.cpp:749-757)
 static inline double mag_cabs_host(double re, double im) { return pp_cabs(re, im); }
-__device__ __forceinline__ double mag_cabs(double re, double im)
-{
-    if ((re == 0) && (im == 0)) return 0.;
-    if (fabs(re) > fabs(im)) return fabs(re) * sqrt(1. + (im / re) * (im / re));
-    return fabs(im) * sqrt(1. + (re / im) * (re / im));
-}
-
-// FPProc::GetElementB (fpproc.cpp:2970-3082), without the incremental columns
-template <bool AXI>
-__device__ __forceinline__ void mag_element_b(double lc, const double (&X)[3], const double (&Y)[3],
-                                              const double (&A)[3], double &B1, double &B2)
-{
-    double b[3], c[3];
-    b[0] = Y[1] - Y[2];
-    b[1] = Y[2] - Y[0];
-    b[2] = Y[0] - Y[1];
-    c[0] = X[2] - X[1];
-    c[1] = X[0] - X[2];
-    c[2] = X[1] - X[0];
-    double da = (b[0] * c[1] - b[1] * c[0]);
-    if (!AXI) {
-        B1 = 0;
-        B2 = 0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            B1 += A[i] * c[i] / (da * lc);
-            B2 -= A[i] * b[i] / (da * lc);
-        }
-        return;
-    }
-    double v[6], r = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) r += X[i] / 3.;
-    v[0] = A[0];
-    v[2] = A[1];
-    v[4] = A[2];
-    // mid-side values
-    if ((X[0] < 1.e-06) && (X[1] < 1.e-06)) v[1] = (v[0] + v[2]) / 2.;
-    else v[1] = (X[1] * (3. * v[0] + v[2]) + X[0] * (v[0] + 3. * v[2])) / (4. * (X[0] + X[1]));
-    if ((X[1] < 1.e-06) && (X[2] < 1.e-06)) v[3] = (v[2] + v[4]) / 2.;
-    else v[3] = (X[2] * (3. * v[2] + v[4]) + X[1] * (v[2] + 3. * v[4])) / (4. * (X[1] + X[2]));
-    if ((X[2] < 1.e-06) && (X[0] < 1.e-06)) v[5] = (v[4] + v[0]) / 2.;
-    else v[5] = (X[0] * (3. * v[4] + v[0]) + X[2] * (v[4] + 3. * v[0])) / (4. * (X[2] + X[0]));
-    const double dp = (-v[0] + v[2] + 4. * v[3] - 4. * v[5]) / 3.;
-    const double dq = (-v[0] - 4. * v[1] + 4. * v[3] + v[4]) / 3.;
-    da *= 2. * kPI * r * lc * lc;
-    B1 = -(c[1] * dp + c[2] * dq) / da;
-    B2 = (b[1] * dp + b[2] * dq) / da;
-}
 
 // CMMaterialProp::GetH(double) on B >= 0 (CMaterialProp.cpp:488-519): the
 // section search is a loop over the block's BHpoints knots
@@ -265,9 +190,7 @@ struct MagElem {
 template <bool AXI>
 __device__ __forceinline__ double mag_aecf(const MagArgs &M, const MagLabel &lab, double cx, double cy)
 {
-    if (!(AXI && lab.external)) return 1.;
-    const double q = mag_cabs(cx, cy - M.ext_zo);
-    return (q * q * M.ext_ri) / (M.ext_ro * M.ext_ro * M.ext_ro);
+    return mag_aecf_of<AXI>(M.ext_ro, M.ext_ri, M.ext_zo, lab.external, cx, cy);
 }
 
 __device__ __forceinline__ void mag_load(const MagArgs &M, int e, MagElem &E)
@@ -306,7 +229,9 @@ __device__ __forceinline__ void mag_integrands(const MagArgs &M, const MagElem &
     const double lc = M.lc, Depth = M.depth;
     double B1, B2;
     mag_element_b<AXI>(lc, E.X, E.Y, E.A, B1, B2);
-    // Ctr
+    // Ctr (kept inline, as is ElmArea below: mag_ctr and mag_area of
+    // xfk_magpost.h are the same operations, but this kernel's instruction
+    // stream is held to what it was before the header existed)
     double cx = 0., cy = 0.;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -1070,16 +995,6 @@ __global__ void __launch_bounds__(kPotQBlock) k_mag_contour(int nc, int NE, MagA
     block_sums<3>(v, part);
 }
 
-// user-unit coordinates
-static __global__ void k_mag_xy(int N, const double *__restrict__ x, const double *__restrict__ y, double u,
-                                double *__restrict__ mx, double *__restrict__ my)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= N) return;
-    mx[i] = x[i] / u;
-    my[i] = y[i] / u;
-}
-
 // A as xfk_get_solution gives it: V c, then (x 0.01 2 PI) on an axisymmetric problem
 static __global__ void k_mag_a(int N, int axi, const double *__restrict__ V, const double *__restrict__ xcm,
                                double *__restrict__ A)
@@ -1123,19 +1038,7 @@ static int mag_entry(xfk_problem *P, F &&body)
     }
 }
 
-// coordinates in user units (once)
-static int mag_prepare_xy(xfk_problem *P)
-{
-    const int N = P->N, G = (N + kBlock - 1) / kBlock;
-    if (P->mag_xy_ready) return XFK_OK;
-    XFK_CHECK(P->mag_x.alloc((size_t)N));
-    XFK_CHECK(P->mag_y.alloc((size_t)N));
-    k_mag_xy<<<G, kBlock, 0, P->stream>>>(N, P->x.p, P->y.p, kMagUnitCm[P->length_units], P->mag_x.p, P->mag_y.p);
-    XFK_CHECK(hipGetLastError());
-    P->mag_xy_ready = true;
-    return XFK_OK;
-}
-
+// (coordinates in user units, once: mag_prepare_xy of xfk_magpost.h)
 // ... and A of the solution in V (after a solve)
 static int mag_prepare(xfk_problem *P)
 {
@@ -1157,23 +1060,12 @@ static int mag_prepare(xfk_problem *P)
 
 static MagArgs mag_args(const xfk_problem *P)
 {
-    MagArgs M = {};
-    M.x = P->mag_x.p;
-    M.y = P->mag_y.p;
-    M.A = P->mag_A.p;
-    M.p = P->p_raw.p;
-    M.lbl = P->lbl_raw.p;
+    MagArgs M = mag_mesh_args(P);
     M.labels = reinterpret_cast<const MagLabel *>(P->mag_lab.p);
     M.blocks = P->blocks.p;
     M.bhB = P->bhB.p;
     M.bhH = P->bhH.p;
     M.bhS = P->bhS.p;
-    M.lc = kMagLengthConv[P->length_units];
-    M.lc2 = std::pow(M.lc, 2.);
-    M.depth = P->mag_depth;
-    M.ext_ro = P->mag_ext_user[0];
-    M.ext_ri = P->mag_ext_user[1];
-    M.ext_zo = P->mag_ext_user[2];
     return M;
 }
 
@@ -1753,13 +1645,17 @@ int xfk_mag_set_solution(xfk_problem *P, const double *A)
 
 int xfk_mag_set_depth(xfk_problem *P, double depth)
 {
-    return mag_entry(P, [&]() -> int {
-        XFK_REQUIRE(depth > 0 || depth == -1, XFK_ERR_ARG,
-                    "depth must be positive (length units), or -1 for the reference's default of 1 m");
-        // fpproc.cpp:1618-1619
-        P->mag_depth = depth == -1 ? 1. : depth * kMagLengthConv[P->length_units];
-        return XFK_OK;
-    });
+    // (a time-harmonic problem too: xfk_mag_ac_* reads the same Depth; nothing is launched)
+    XFK_REQUIRE(P, XFK_ERR_ARG, "null problem");
+    XFK_REQUIRE(!P->electro && !P->heat, XFK_ERR_ARG,
+                "not a magnetics problem: xfk_mag_set_depth sets the depth of a magnetics problem");
+    XFK_REQUIRE(!P->comm, XFK_ERR_UNSUPPORTED,
+                "sharded problem: magnetics post-processing needs the whole mesh on one device");
+    XFK_REQUIRE(depth > 0 || depth == -1, XFK_ERR_ARG,
+                "depth must be positive (length units), or -1 for the reference's default of 1 m");
+    // fpproc.cpp:1618-1619
+    P->mag_depth = depth == -1 ? 1. : depth * kMagLengthConv[P->length_units];
+    return XFK_OK;
 }
 
 int xfk_mag_element_b(xfk_problem *P, double *B1, double *B2)

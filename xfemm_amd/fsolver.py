@@ -151,13 +151,14 @@ class FSolver:
         _lib.xfemm_fsolver_set_comm(self._h, comm._h if comm is not None else None)
 
     def keep_problem(self, keep: bool = True):
-        """Have a static single-device runSolver leave its solved device
-        problem alive for post-processing (xfemm_fsolver_set_keep_problem)."""
+        """Have a single-device runSolver, static or harmonic, leave its solved
+        device problem alive for post-processing (xfemm_fsolver_set_keep_problem)."""
         _lib.xfemm_fsolver_set_keep_problem(self._h, int(bool(keep)))
 
     def problem(self):
         """The kept problem of the last solve as a post-processing view
-        (kernels._MagPostProc: element_b, block_integrals, ...), with the
+        (kernels._MagPostProc: element_b, block_integrals, ...; after a
+        harmonic solve element_b_complex, block_integrals_complex, ...), with the
         file's [Depth] and the solve's circuit table; None without one.  The
         solver owns it: the view is valid until the next solve or the
         solver's end."""

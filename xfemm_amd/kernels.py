@@ -68,6 +68,8 @@ EXPORTED = (
     "xfk_pot_line_integrals", "xfk_pot_line_integral", "xfk_pot_contour_samples", "xfk_pot_contour_time",
     "xfk_mag_set_solution", "xfk_mag_set_depth", "xfk_mag_element_b", "xfk_mag_block_integrals",
     "xfk_mag_block_integral", "xfk_mag_time",
+    "xfk_mag_ac_set_solution", "xfk_mag_ac_element_b", "xfk_mag_ac_block_integrals", "xfk_mag_ac_block_integral",
+    "xfk_mag_ac_time",
     "xfk_mag_make_mask", "xfk_mag_get_mask", "xfk_mag_mask_info", "xfk_mag_mask_problem", "xfk_mag_stress_time",
     "xfk_mag_corner_b", "xfk_mag_point_values", "xfk_mag_point_values_at", "xfk_mag_line_integrals",
     "xfk_mag_line_integral", "xfk_mag_contour_samples", "xfk_mag_point_time", "xfk_mag_contour_time",
@@ -355,6 +357,11 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_mag_block_integrals.argtypes = [C.c_void_p, ubptr, dptr]
     L.xfk_mag_block_integral.argtypes = [C.c_void_p, ubptr, C.c_int, dptr]
     L.xfk_mag_time.argtypes = [C.c_void_p, C.c_int, dptr]
+    L.xfk_mag_ac_set_solution.argtypes = [C.c_void_p, dptr]
+    L.xfk_mag_ac_element_b.argtypes = [C.c_void_p, dptr, dptr]
+    L.xfk_mag_ac_block_integrals.argtypes = [C.c_void_p, ubptr, dptr]
+    L.xfk_mag_ac_block_integral.argtypes = [C.c_void_p, ubptr, C.c_int, dptr]
+    L.xfk_mag_ac_time.argtypes = [C.c_void_p, C.c_int, dptr]
     L.xfk_mag_make_mask.argtypes = [C.c_void_p, ubptr, dptr, ubptr]
     L.xfk_mag_get_mask.argtypes = [C.c_void_p, dptr, dptr]
     L.xfk_mag_mask_info.argtypes = [C.c_void_p, dptr]
@@ -643,6 +650,60 @@ class _MagPostProc:
         label selected (xfk_mag_time)."""
         ms = np.zeros(2)
         _check(_lib.xfk_mag_time(self._h, int(repeats), ms.ctypes.data_as(dptr)))
+        return dict(element_b=float(ms[0]), block_integrals=float(ms[1]))
+
+    # -- a time-harmonic problem (the xfk_mag_ac_ entry points) --
+
+    # inttype -> name of the types answered at Frequency != 0 (18-23 are 0)
+    MAG_AC_INTEGRALS = {0: "AJ", 1: "A", 2: "energy", 3: "hysteresis_loss", 4: "resistive_loss", 5: "area",
+                        6: "total_loss", 7: "current", 8: "B1", 9: "B2", 10: "volume", 11: "force_x", 12: "force_y",
+                        13: "force_x_2f", 14: "force_y_2f", 15: "torque", 16: "torque_2f", 17: "coenergy",
+                        24: "inertia", 25: "centroid"}
+
+    def set_solution_complex(self, A):
+        """Post-process a given harmonic solution (one complex value per node
+        as the .ans carries it: A, or the flux 2 pi r A on an axisymmetric
+        problem) without solving (xfk_mag_ac_set_solution)."""
+        a = np.ascontiguousarray(A, dtype=np.complex128)
+        if a.shape != (self.n_nodes,):
+            raise ValueError("expected one value per node (%d), got shape %s" % (self.n_nodes, a.shape))
+        _check(_lib.xfk_mag_ac_set_solution(self._h, a.view(np.float64).ctypes.data_as(dptr)))
+
+    def element_b_complex(self) -> np.ndarray:
+        """The complex flux density of every element, (n_elems, 2) (xfk_mag_ac_element_b)."""
+        B1 = np.zeros(self.n_elems, np.complex128)
+        B2 = np.zeros(self.n_elems, np.complex128)
+        _check(_lib.xfk_mag_ac_element_b(self._h, B1.view(np.float64).ctypes.data_as(dptr),
+                                         B2.view(np.float64).ctypes.data_as(dptr)))
+        return np.stack([B1, B2], axis=1)
+
+    def block_integrals_complex(self, selected_labels) -> dict:
+        """Every block integral of a harmonic solution over the elements of
+        the selected labels, from one pass over the mesh: the named types of
+        MAG_AC_INTEGRALS as complex values, and "raw", indexed by the
+        reference's inttype (26 of them; 18-23 are 0)."""
+        keep, mp = self._mag_mask(selected_labels)
+        o = np.zeros(52)
+        _check(_lib.xfk_mag_ac_block_integrals(self._h, mp, o.ctypes.data_as(dptr)))
+        raw = o[0::2] + 1j * o[1::2]
+        r = {name: complex(raw[t]) for t, name in self.MAG_AC_INTEGRALS.items()}
+        r["raw"] = raw
+        return r
+
+    def block_integral_complex(self, selected_labels, kind: int) -> complex:
+        """One block integral of a harmonic solution in the reference's
+        numbering (xfk_mag_ac_block_integral)."""
+        keep, mp = self._mag_mask(selected_labels)
+        o = np.zeros(2)
+        _check(_lib.xfk_mag_ac_block_integral(self._h, mp, int(kind), o.ctypes.data_as(dptr)))
+        return complex(o[0], o[1])
+
+    def time_postproc_complex(self, repeats: int = 5) -> dict:
+        """Diagnostic: HIP-event times (ms, medians after a warm-up) of the
+        complex element-B launch and of the block-integral launch with its
+        sum, every answerable label selected (xfk_mag_ac_time)."""
+        ms = np.zeros(2)
+        _check(_lib.xfk_mag_ac_time(self._h, int(repeats), ms.ctypes.data_as(dptr)))
         return dict(element_b=float(ms[0]), block_integrals=float(ms[1]))
 
     # -- the weighted stress tensor force and torque (block integrals 18-23) --
@@ -1727,7 +1788,7 @@ class CircuitAcDesc(C.Structure):
 class HarmonicDesc(C.Structure):
     _fields_ = [("frequency", C.c_double), ("blocks", C.POINTER(BlockAcDesc)), ("lines", C.POINTER(LineAcDesc)),
                 ("circs", C.POINTER(CircuitAcDesc)), ("ac_solver", C.c_int),
-                ("label_prox_mu", C.POINTER(C.c_double))]
+                ("label_prox_mu", C.POINTER(C.c_double)), ("prev_type", C.c_int)]
 
 
 class Harmonic2DProblem(_MagPostProc):
@@ -1736,15 +1797,19 @@ class Harmonic2DProblem(_MagPostProc):
     AC fields: blocks J_im, Theta_hx, Theta_hy, Lam_d; lines c0_im, c1_im, Mu,
     Sig (BdryFormat 1); circuits amps_im, dvolts_im.  The post-processing
     methods it shares with Static2DProblem are refused: they are built for
-    magnetostatic problems only."""
+    magnetostatic problems only.  Its own are set_solution_complex,
+    element_b_complex, block_integrals_complex, block_integral_complex and
+    time_postproc_complex (the xfk_mag_ac_ entry points), with set_depth."""
 
     def __init__(self, *, x, y, p, lbl, blocks: Sequence[dict], labels: Sequence[dict], frequency: float,
                  lines: Sequence[dict] = (), points: Sequence[dict] = (), circuits: Sequence[dict] = (),
                  marker=None, e=None, pbc=None, precision=1e-8, length_units=0, coords=0, relax=1.0, device=0,
                  problem_type: int = 0, ext_zo: float = 0.0, ext_ro: float = 0.0, ext_ri: float = 0.0,
                  precond: str = "amg", ages: Sequence[dict] = (), ac_solver: int = 0,
-                 comm: Optional["Comm"] = None):
-        """precond: "amg" (V-cycle of the real SPD surrogate Re A +- Im A, the
+                 comm: Optional["Comm"] = None, prev_type: int = 0):
+        """prev_type: [PrevType] of the file the problem came from; the solve
+        does not read it, the harmonic post-processing refuses != 0.
+        precond: "amg" (V-cycle of the real SPD surrogate Re A +- Im A, the
         sign making Im A positive semi-definite, applied to the real and
         imaginary parts; default) or "jacobi" (complex Jacobi).  ac_solver:
         [ACSolver], 0 successive approximation, 1 Newton (KludgeSolve).
@@ -1772,7 +1837,7 @@ class Harmonic2DProblem(_MagPostProc):
         for k, l in enumerate(labels):
             z = complex(l.get("prox_mu", 1.0))
             prox[2 * k], prox[2 * k + 1] = z.real, z.imag
-        H = HarmonicDesc(frequency, ba, la, ca, int(ac_solver), keep.d(prox))
+        H = HarmonicDesc(frequency, ba, la, ca, int(ac_solver), keep.d(prox), int(prev_type))
         keep.extend([ba, la, ca])
         self._keep = keep
         self.n_nodes = D.n_nodes
