@@ -1112,6 +1112,23 @@ void xfk_amg_probe_destroy(xfk_amg_probe *probe);
 
 /* Device views for the bench / tests (stream-ordered on the problem's stream). */
 int xfk_get_csr(xfk_problem *prob, int *rowptr, int *col, double *val, double *b);
+/* The system of a Newton pass at a given iterate, without solving (a static
+ * planar or axisymmetric problem).  V is npass x n_nodes, in the solver's own
+ * unit (the V of b - K V: xfk_get_solution / c, axisymmetric: before the
+ * 2 pi r factor).  The iteration-0 system is assembled from V = 0 as the first
+ * pass of xfk_static2d does; then for k = 0 .. npass-1 row k of V is the
+ * iterate of Newton pass k + 1, which reads the permeability state pass k
+ * wrote.  npass == 0 gives the iteration-0 system.  xfk_get_csr then shows the
+ * last pass's system and xfk_get_element_state the state it wrote.  Any
+ * earlier solution is gone afterwards; a later xfk_static2d is unaffected.
+ * XFK_ERR_ARG on a null, electrostatic, heat-flow, harmonic or mask problem,
+ * XFK_ERR_UNSUPPORTED on a sharded one. */
+int xfk_static2d_assemble_at(xfk_problem *prob, int npass, const double *V);
+/* The per-element permeability state (mu1, mu2; n_elems each, the caller's
+ * element order) the last pass wrote -- what the next pass would read.
+ * XFK_ERR_ARG before the first pass and on a linear problem, which keeps no
+ * state. */
+int xfk_get_element_state(xfk_problem *prob, double *mu1, double *mu2);
 long long xfk_get_nnz(xfk_problem *prob);
 /* Column-index bytes per nonzero the last solve's PCG SpMV read: 2 with the
    AMG's 16-bit tile offsets (plus 2 for every nonzero of a tile whose columns

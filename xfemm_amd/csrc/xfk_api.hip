@@ -2624,6 +2624,64 @@ int xfk_static2d(xfk_problem *P, int flags, xfk_result *res)
     return rc;
 }
 
+static int static_probe_check(xfk_problem *P)
+{
+    XFK_REQUIRE(P, XFK_ERR_ARG, "null problem");
+    XFK_REQUIRE(!P->electro, XFK_ERR_ARG, "electrostatic problem: no Newton pass to assemble");
+    XFK_REQUIRE(!P->heat, XFK_ERR_ARG, "heat-flow problem: use xfk_heatflow_assemble");
+    XFK_REQUIRE(!P->harmonic, XFK_ERR_ARG, "harmonic problem: no static Newton pass to assemble");
+    XFK_REQUIRE(!P->mask, XFK_ERR_ARG, "mask problem: no Newton pass to assemble");
+    XFK_REQUIRE(!P->comm, XFK_ERR_UNSUPPORTED, "sharded problem: the halo of V is not handled here");
+    return XFK_OK;
+}
+
+int xfk_static2d_assemble_at(xfk_problem *P, int npass, const double *V)
+{
+    int rc = static_probe_check(P);
+    if (rc != XFK_OK) return rc;
+    XFK_REQUIRE(npass >= 0 && (npass == 0 || V), XFK_ERR_ARG, "npass passes need npass x n_nodes iterates");
+    ArenaScope arena_scope(&P->arena);
+    XFK_CHECK(hipSetDevice(P->device));
+    hipStream_t s = P->stream;
+    P->mag_A_ready = false;   // (as a solve: V no longer holds the solution)
+    P->mask_ready = false;
+    if (!P->symbolic_ready) rc = build_symbolic(P);
+    if (rc == XFK_OK && hipMemsetAsync(P->V.p, 0, sizeof(double) * P->NL, s) != hipSuccess) {
+        set_error("clearing V failed");
+        rc = XFK_ERR_HIP;
+    }
+    if (rc == XFK_OK) rc = assemble(P, 0);
+    for (int k = 0; k < npass && rc == XFK_OK; ++k) {
+        // (pageable host memory: the copy has left V's row before the call returns)
+        if (hipMemcpyAsync(P->V.p, V + (size_t)k * P->N, sizeof(double) * P->N, hipMemcpyHostToDevice, s) != hipSuccess) {
+            set_error("upload of the iterate failed");
+            rc = XFK_ERR_HIP;
+        } else {
+            rc = assemble(P, k + 1);
+        }
+    }
+    if (rc == XFK_OK && hipStreamSynchronize(s) != hipSuccess) {
+        set_error("assembly at the given iterate failed");
+        rc = XFK_ERR_HIP;
+    }
+    problem_recycle(P);
+    return rc;
+}
+
+int xfk_get_element_state(xfk_problem *P, double *mu1, double *mu2)
+{
+    const int rc = static_probe_check(P);
+    if (rc != XFK_OK) return rc;
+    XFK_REQUIRE(mu1 && mu2, XFK_ERR_ARG, "null argument");
+    XFK_REQUIRE(P->any_nonlinear, XFK_ERR_ARG, "linear problem: it keeps no permeability state");
+    XFK_REQUIRE(P->symbolic_ready, XFK_ERR_ARG, "no assembled pass yet");
+    XFK_CHECK(hipSetDevice(P->device));
+    // (assemble() swapped the buffers: mu1 / mu2 are what the last pass wrote)
+    XFK_CHECK(d2h(mu1, P->mu1.p, sizeof(double) * P->NE, P->stream));
+    XFK_CHECK(d2h(mu2, P->mu2.p, sizeof(double) * P->NE, P->stream));
+    return XFK_OK;
+}
+
 }  // extern "C"
 
 namespace xfk {

@@ -669,7 +669,8 @@ __device__ void get_bh_props(const DevBlock &m, const double *__restrict__ Bt, c
     double l = (Bd[i + 1] - Bd[i]);
     double z = (b - Bd[i]) / l;
     double z2 = z * z;
-    double h = (1. - 3. * z2 + 2. * z2 * z) * Hd[i] + z * (1. - 2. * z + z2) * l * sl[i] +
+    // (the first two products: one contraction for every kernel, see planar_element)
+    double h = fma(1. - 3. * z2 + 2. * z2 * z, Hd[i], z * (1. - 2. * z + z2) * l * sl[i]) +
                z2 * (3. - 2. * z) * Hd[i + 1] + z2 * (z - 1.) * l * sl[i + 1];
     double dh = 6. * z * (z - 1.) * Hd[i] / l + (1. - 4. * z + 3. * z * z) * sl[i] +
                 6. * z * (1. - z) * Hd[i + 1] / l + z * (3. * z - 2.) * sl[i + 1];
@@ -823,7 +824,7 @@ __device__ __forceinline__ bool planar_newton_state(const AssembleArgs &A, const
     } else {
         for (int j = 0; j < 3; ++j) { B1 += (Vn[j] * q[j]) / f; B2 += Vn[j] * p[j]; }
     }
-    const double B = kC * sqrt(B1 * B1 + B2 * B2) / (0.02 * a);
+    const double B = kC * sqrt(fma(B1, B1, B2 * B2)) / (0.02 * a);   // (one contraction, see planar_element)
     double mu = 0;
     get_bh_props(bp, A.bhB, A.bhH, A.bhS, B, mu, dv);
     mu = 1. / (kMUO * mu);
@@ -862,8 +863,10 @@ __device__ __forceinline__ void planar_newton_terms(const DevBlock &bp, const do
             }
         }
         const double Kn = -100. * kC * kC * kC * dv / (a);
+        // (one contraction for every instantiation, see planar_element; the
+        // upper triangle is the one assemble_rows reads)
         for (int j = 0; j < 3; ++j)
-            for (int w = 0; w < 3; ++w) Mn[j][w] = Kn * (v[j] * u[w] + v[w] * u[j]);
+            for (int w = 0; w < 3; ++w) Mn[j][w] = Kn * fma(v[j], u[w], v[w] * u[j]);
     }
 }
 
@@ -873,7 +876,7 @@ __device__ __forceinline__ double planar_geometry(const double (&X)[3], const do
 {
     p[0] = Y[1] - Y[2]; p[1] = Y[2] - Y[0]; p[2] = Y[0] - Y[1];
     q[0] = X[2] - X[1]; q[1] = X[0] - X[2]; q[2] = X[1] - X[0];
-    return (p[0] * q[1] - p[1] * q[0]) / 2.;
+    return fma(p[0], q[1], -(p[1] * q[0])) / 2.;   // (one contraction, see planar_element)
 }
 
 // FSolver::Static2D element (static2d.cpp:352-805): Me / be before the sign
@@ -911,7 +914,8 @@ __device__ __forceinline__ void planar_element(int eb, const AssembleArgs &A, co
             const DevLine ln = A.lines[ej];
             if (ln.format != 2) continue;
             int k = (j + 1) % 3;
-            double lj = sqrt(pow(X[k] - X[j], 2.) + pow(Y[k] - Y[j], 2.));
+            const double dx = X[k] - X[j], dy = Y[k] - Y[j];
+            double lj = sqrt(fma(dx, dx, dy * dy));
             double Kb = -0.0001 * kC * ln.c0 * lj / 6.;
             Me[j][j] += Kb * 2.;
             Me[k][k] += Kb * 2.;
@@ -938,7 +942,7 @@ __device__ __forceinline__ void planar_element(int eb, const AssembleArgs &A, co
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             int k = (j + 1) % 3;
-            double Km = 0.0001 * bp.H_c * (lab.cos_m * (X[k] - X[j]) + lab.sin_m * (Y[k] - Y[j])) / 2.;
+            double Km = 0.0001 * bp.H_c * fma(lab.cos_m, X[k] - X[j], lab.sin_m * (Y[k] - Y[j])) / 2.;
             be[j] += Km;
             be[k] += Km;
         }
@@ -962,12 +966,16 @@ __device__ __forceinline__ void planar_element(int eb, const AssembleArgs &A, co
     // element matrix, v12 == 0 outside incremental problems (static2d.cpp:799-805)
     // (two reciprocals instead of 18 f64 divisions: within an ulp of the
     // reference's Mx / m2 + My / m1, far inside the assembly tolerance)
+    // (a sum of two products has two contractions, fma(a, b, c d) and
+    // fma(c, d, a b), and which one the backend takes differed between the
+    // instantiations of this function -- k_assemble_rows_pre and the per-row
+    // arm gave matrices 1-4 ulp apart; written out, every kernel rounds alike)
     const double im1 = 1.0 / m1, im2 = 1.0 / m2;
 #pragma unroll
     for (int j = 0; j < 3; ++j)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            Me[j][k] += (Mx[j][k] * im2 + My[j][k] * im1 + Mn[j][k]);
+            Me[j][k] += (fma(Mx[j][k], im2, My[j][k] * im1) + Mn[j][k]);
             be[j] += Mn[j][k] * Vn[k];
         }
 

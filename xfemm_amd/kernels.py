@@ -46,6 +46,7 @@ XFK_OPT_HEAT_MAX_PASSES = 13
 EXPORTED = (
     "xfk_last_error", "xfk_age_element_matrix", "xfk_device_count", "xfk_device_init", "xfk_problem_create", "xfk_problem_destroy",
     "xfk_static2d", "xfk_get_solution", "xfk_get_circuits", "xfk_get_csr", "xfk_get_nnz", "xfk_spmv_col_bytes",
+    "xfk_static2d_assemble_at", "xfk_get_element_state",
     "xfk_get_stream", "xfk_pcg_solve_csr", "xfk_pcg_solve_csr_pc", "xfk_pcg_time", "xfk_phase_profile",
     "xfk_alloc_stats", "xfk_problem_memory", "xfk_cache_stats", "xfk_release_cache",
     "xfk_amg_forget_hints",
@@ -263,6 +264,8 @@ def load_library(path: str = KERNELS_SO):
     L.xfk_get_solution.argtypes = [C.c_void_p, dptr]
     L.xfk_get_circuits.argtypes = [C.c_void_p, iptr, dptr, dptr]
     L.xfk_get_csr.argtypes = [C.c_void_p, iptr, iptr, dptr, dptr]
+    L.xfk_static2d_assemble_at.argtypes = [C.c_void_p, C.c_int, dptr]
+    L.xfk_get_element_state.argtypes = [C.c_void_p, dptr, dptr]
     L.xfk_get_nnz.argtypes = [C.c_void_p]
     L.xfk_get_nnz.restype = C.c_longlong
     L.xfk_spmv_col_bytes.argtypes = [C.c_void_p]
@@ -1040,6 +1043,26 @@ class Static2DProblem(_MagPostProc):
         _check(_lib.xfk_get_circuits(self._h, cc.ctypes.data_as(iptr), J.ctypes.data_as(dptr),
                                      dV.ctypes.data_as(dptr)))
         return cc[:n], J[:n], dV[:n]
+
+    def assemble_at(self, V_list=()):
+        """The system of Newton pass len(V_list) without solving
+        (xfk_static2d_assemble_at): the iteration-0 system from V = 0, then one
+        pass per iterate of V_list, each reading the permeability state the
+        pass before wrote.  The iterates are in the solver's own unit (planar:
+        solution() / c with c = 4e-5 pi); csr() and element_state() then show
+        the last pass."""
+        V = np.ascontiguousarray(np.asarray(V_list, dtype=np.float64).reshape(len(V_list), -1 if len(V_list) else 0))
+        if len(V) and V.shape[1] != self.n_nodes:
+            raise XfkError("every iterate needs n_nodes values")
+        _check(_lib.xfk_static2d_assemble_at(self._h, len(V), V.ctypes.data_as(dptr) if len(V) else None))
+
+    def element_state(self):
+        """(mu1, mu2) per element, the caller's element order: the permeability
+        state the last pass wrote (xfk_get_element_state; nonlinear problems)."""
+        mu1 = np.zeros(self.n_elems)
+        mu2 = np.zeros(self.n_elems)
+        _check(_lib.xfk_get_element_state(self._h, mu1.ctypes.data_as(dptr), mu2.ctypes.data_as(dptr)))
+        return mu1, mu2
 
     def spmv_col_bytes(self) -> float:
         """Column-index bytes per nonzero of the last solve's PCG SpMV (2: the
