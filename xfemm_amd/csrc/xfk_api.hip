@@ -1808,7 +1808,8 @@ int xfk_device_init(int device)
     XFK_CHECK(hipFree(nullptr));
     for (hipError_t (*w)() : {warm_module_device, warm_module_pcg, warm_module_amg, warm_module_amg_spgemm,
                               warm_module_amg_dense, warm_module_amg_cycle, warm_module_harmonic, warm_module_sort,
-                              warm_module_comm, warm_module_electro, warm_module_heat, warm_module_postproc})
+                              warm_module_comm, warm_module_electro, warm_module_heat, warm_module_postproc,
+                              warm_module_mask})
         XFK_CHECK(w());
     hipStream_t s[3] = {};   // a problem's solve stream, the AMG's side stream and the sort's
     for (hipStream_t &q : s) XFK_CHECK(stream_acquire(&q));

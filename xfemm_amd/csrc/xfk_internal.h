@@ -347,6 +347,7 @@ hipError_t warm_module_comm();
 hipError_t warm_module_device();
 hipError_t warm_module_electro();
 hipError_t warm_module_harmonic();
+hipError_t warm_module_mask();
 hipError_t warm_module_heat();
 hipError_t warm_module_pcg();
 hipError_t warm_module_postproc();
@@ -625,7 +626,7 @@ struct xfk_problem {
     bool pp_mesh_ready = false, pp_grid_ready = false, pp_fields_ready = false, pp_corner_ready = false;
     xfk::DBuf<double> pp_x, pp_y;                // N: coordinates in user units
     xfk::DBuf<int> pp_q;                         // N: pot_qmark
-    xfk::DBuf<int> pp_n2e_ptr, pp_n2e;           // node -> elements of the mesh's own connectivity, counter-clockwise
+    xfk::DBuf<int> pp_n2e_ptr, pp_n2e;           // node -> elements of the mesh's own connectivity, each list sorted by angle about its node
     xfk::DBuf<int> pp_class;                     // block -> its "same material" class
     xfk::DBuf<double> pp_D, pp_E, pp_d;          // 2 NE, 2 NE: element fields; 6 NE: smoothed corner values
     xfk::DBuf<int> pp_cell_ptr, pp_cell_el, pp_big;   // the cell grid: lists per cell, and the oversize elements
@@ -637,8 +638,8 @@ struct xfk_problem {
     xfk::DBuf<int> pp_pel;                       // ... and the element of each point
 
     // the weighted stress tensor mask of an electrostatic problem
-    // (PostProcessor::makeMask, xfk_postproc.hip) or of a magnetostatic one
-    // (FPProc::MakeMask, xfk_magpost.hip): a Laplace problem of its own
+    // (PostProcessor::makeMask) or of a magnetostatic one (FPProc::MakeMask),
+    // made by xfk_mask.hip for either: a Laplace problem of its own
     // on the mesh's connectivity, kept in an auxiliary problem (mask_aux: no
     // conductors, no periodic pairs, coordinates in user units) that is created
     // at the first xfk_pot_make_mask / xfk_mag_make_mask and destroyed with
@@ -648,7 +649,8 @@ struct xfk_problem {
     xfk_problem *mask_aux = nullptr;
     bool mask_ready = false, mask_ext_ready = false;
     std::vector<unsigned char> mask_sel;         // host: the label selection the mask was made for
-    xfk::DBuf<unsigned char> mask_point;         // N: pot_has_point
+    xfk::DBuf<unsigned char> mask_point;         // N: the node carries a point property (pot_has_point or mag_has_point)
+    xfk::DBuf<unsigned char> mask_lflag;         // per entry of the label table: selected, then not air
     xfk::DBuf<unsigned char> mask_ext;           // N: the node ends an exterior edge (FindBoundaryEdges)
     xfk::DBuf<unsigned char> mask_nsel;          // N: the selected nodes
     xfk::DBuf<double> mask_area;                 // per label: MaxArea
@@ -700,7 +702,6 @@ struct xfk_problem {
     // ... its weighted stress tensor mask (the mask_ group above holds the rest)
     std::vector<unsigned char> mag_has_point;    // host, N: the node carries a point property (marker >= 0)
     xfk::DBuf<int> mag_n2e_ptr, mag_n2e;         // node -> elements of p_raw, ascending
-    xfk::DBuf<unsigned char> mag_mlab;           // per entry of the label table: selected, then not air
     // ... its point values and contour integrals: the element B and the
     // smoothed corner values follow the solution (dropped where mag_A is
     // replaced); the cell grid is the pp_ group's, over mag_x, mag_y, p_raw
@@ -824,9 +825,10 @@ int reserve_first_solve(xfk_problem **out);
 void launch_electro_rows(hipStream_t s, xfk_problem *P);
 // xfk_heat.hip: the same with the heat-flow element (reads P->hf_vo; writes every entry of val and b)
 void launch_heat_rows(hipStream_t s, xfk_problem *P);
-// xfk_postproc.hip: the same with the element of the weighted stress tensor mask (an auxiliary problem, P->mask)
+// xfk_mask.hip: the same with the element of the weighted stress tensor mask (an auxiliary problem, P->mask)
 void launch_mask_rows(hipStream_t s, xfk_problem *P);
-// xfk_postproc.hip, shared by the electrostatic and the magnetostatic mask (xfk_magpost.hip):
+// xfk_mask.hip, the weighted stress tensor mask of the electrostatic (xfk_postproc.hip) and the
+// magnetostatic (xfk_magpost.hip) post-processor:
 // the mask's auxiliary problem of P over a mesh in user units (lab: one entry per label of lbl), once
 int mask_aux_create(xfk_problem *P, const std::vector<double> &x, const std::vector<double> &y,
                     const std::vector<int> &p, const std::vector<int> &lbl, const std::vector<PotLabel> &lab,
@@ -836,6 +838,32 @@ int mask_aux_solve(xfk_problem *P, xfk_result *res);
 void mask_set_info(xfk_problem *P, const xfk_result &res, double ms_create, double ms_rules, double ms_total);
 int launch_mask_exterior(hipStream_t s, int N, int NE, const int *p, const int *n2e_ptr, const int *n2e,
                          unsigned char *ext);
+// the point marks (host, N) and FindBoundaryEdges of the device mesh into P->mask_point and P->mask_ext, once
+int mask_mesh_marks(xfk_problem *P, const int *p, const int *n2e_ptr, const int *n2e, const unsigned char *point);
+// What a caller hands mask_make, with its auxiliary problem created (P->mask_aux)
+struct MaskInputs {
+    const double *x;                  // device, N: r (x) in user units
+    const int *p, *lbl;               // device: the mesh's own connectivity, each element's entry of the label table
+    const int *n2e_ptr, *n2e;         // device: node -> elements of p, every list in any order
+    const unsigned char *lflag;       // host, 2 per entry of the label table: selected, then not air
+    const double *area;               // host, per entry: MaxArea (<= 0: the element's own area weights it)
+    size_t nentries;
+    const int *q;                     // device, N: the conductor marks (-2: none), or null: no conductors
+    const unsigned char *nsel;        // host, N: the selected nodes, or null
+    const unsigned char *point;       // host, N: the node carries a point property
+    const unsigned char *sel;         // host: the caller's selection, kept for mask_matches
+    size_t nsel_labels;
+    const char *invalid;              // the caller's message for a selection that abuts a region which is not air
+    // mask_info's windows are the caller's: when its make_mask began, when its rules began (its air test is
+    // part of them), and what creating the auxiliary problem took in this call (0: it existed)
+    std::chrono::steady_clock::time_point t_all, t_rules;
+    double ms_create;
+};
+// makeMask / MakeMask for one selection: the fixed values by the reference's rules, the validity check, the
+// Laplace solve and the threshold into P->mask_msk; fills P->mask_info
+int mask_make(xfk_problem *P, const MaskInputs &I);
+// the mask P holds was made for the selection sel of n labels
+bool mask_matches(const xfk_problem *P, const unsigned char *sel, size_t n);
 // xfk_magpost_ac.hip: the host tables a harmonic problem's post-processing
 // reads (the mag_ group of P), from the descriptors it is created from; blk:
 // the solver's block table (its knots in the complex curve tables)

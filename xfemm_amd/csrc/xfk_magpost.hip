@@ -10,8 +10,8 @@
 //                     DoCoEnergy (CMaterialProp.cpp:488-519, 537-677)
 //   block integrals   FPProc::BlockIntegral types 0 1 2 5 7 8 9 10 11 12 15 17
 //                     24 25 (3642-4092)
-//   the mask          FPProc::MakeMask, IsKosher (makemask.cpp:48-414),
-//                     FindBoundaryEdges (fpproc.cpp:5356-5415)
+//   the mask          FPProc::MakeMask (makemask.cpp:48-414): the air test
+//                     here (108-132), the rest in xfk_mask.hip
 //   force and torque  HenrotteVector (3614-3640), BlockIntegral types 18-23
 //                     (3966-4079)
 //   point values      GetNodalB (2704-2967), GetPointB (2669-2702),
@@ -50,9 +50,6 @@ enum {
     MS_AJ, MS_A, MS_ENERGY, MS_AREA, MS_CURRENT, MS_B1, MS_B2, MS_VOLUME, MS_FX, MS_FY, MS_TORQUE, MS_COENERGY,
     MS_INERTIA, MS_CX, MS_CY, kMagSums
 };
-
-// abs(CComplex) (femmcomplex.cpp:749-757)
-static inline double mag_cabs_host(double re, double im) { return pp_cabs(re, im); }
 
 // CMMaterialProp::GetH(double) on B >= 0 (CMaterialProp.cpp:488-519): the
 // section search is a loop over the block's BHpoints knots
@@ -380,90 +377,6 @@ __global__ void __launch_bounds__(kPotQBlock) k_mag_integrands(int NE, MagArgs M
         if (lab.sel) mag_integrands<AXI>(M, E, lab, v);
     }
     block_sums<kMagSums>(v, part);
-}
-
-// --- the weighted stress tensor mask (FPProc::MakeMask, makemask.cpp:48-379) ---
-//
-// WeightingScheme 0.  The rules that fix nodal values are independent per node
-// apart from their order, so a thread per node applies them in the reference's
-// order; the Laplace problem is the one of xfk_postproc.hip (mask_aux_create,
-// MaskPhys), solved on an auxiliary problem over the caller's connectivity.
-
-struct MagMaskArgs {
-    const double *x;               // user length units
-    const int *p, *lbl;
-    const int *n2e_ptr, *n2e;      // node -> elements of p, ascending
-    const unsigned char *mlab;     // per entry of the label table: selected, then not air (lblflag)
-    const unsigned char *ext;      // the node ends an exterior edge (FindBoundaryEdges, fpproc.cpp:5356-5415)
-    const unsigned char *point;    // the node carries a point property
-    int axi;
-};
-
-// bOnAxis (makemask.cpp:94-106): a selected element with a node at r < 1e-6;
-// flag[0] (zeroed by the caller) is set
-__global__ void __launch_bounds__(kBlock) k_mag_mask_on_axis(int NE, MagMaskArgs A, int *__restrict__ flag)
-{
-    const int e = blockIdx.x * kBlock + threadIdx.x;
-    if (e >= NE || !A.mlab[2 * A.lbl[e]]) return;
-    bool on = false;
-    for (int j = 0; j < 3; ++j) on |= A.x[A.p[3 * e + j]] < 1.e-6;
-    if (on) flag[0] = 1;
-}
-
-// L.V of makemask.cpp:136-201, one thread per node; -1: free
-__global__ void __launch_bounds__(kBlock) k_mag_mask_fix(int N, MagMaskArgs A, const int *__restrict__ flag,
-                                                         double *__restrict__ lv)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= N) return;
-    const int l0 = A.n2e_ptr[i], l1 = A.n2e_ptr[i + 1];
-    double v = -1.;
-    // the ends of exterior edges; with the selection on the axis only where IsKosher (makemask.cpp:383-414)
-    if (A.ext[i]) {
-        bool kosher = true;
-        if (flag[0] && A.axi && !(A.x[i] > 1.e-6)) {
-            int score = 0;
-            for (int m = l0; m < l1; ++m)
-                for (int j = 0; j < 3; ++j) {
-                    const int n = A.p[3 * A.n2e[m] + j];
-                    if ((n != i) && (A.x[n] < 1.e-6)) score++;
-                }
-            kosher = !(score > 1);
-        }
-        if (kosher) v = 0.;
-    }
-    // the nodes of selected elements 1, of unselected elements that are not
-    // air 0, in element order: the highest-numbered such element decides
-    int last = -1;
-    bool last_sel = false;
-    for (int m = l0; m < l1; ++m) {
-        const int e = A.n2e[m];
-        if (e < last) continue;
-        const unsigned char *f = A.mlab + 2 * A.lbl[e];
-        if (f[0] || f[1]) {
-            last = e;
-            last_sel = f[0] != 0;
-        }
-    }
-    if (last >= 0) v = last_sel ? 1. : 0.;
-    // a still-free node with a point property
-    if (A.point[i] && (v < 0)) v = 0.;
-    lv[i] = v;
-}
-
-// the consistency check (makemask.cpp:233-254): an unselected element that is
-// not air with a node not fixed at exactly 0 sets flag[1]
-__global__ void __launch_bounds__(kBlock) k_mag_mask_valid(int NE, MagMaskArgs A, const double *__restrict__ lv,
-                                                           int *__restrict__ flag)
-{
-    const int e = blockIdx.x * kBlock + threadIdx.x;
-    if (e >= NE) return;
-    const unsigned char *f = A.mlab + 2 * A.lbl[e];
-    if (f[0] || !f[1]) return;
-    int k = 0;
-    for (int j = 0; j < 3; ++j)
-        if (lv[A.p[3 * e + j]] == 0) k++;
-    if (k < 3) flag[1] = 1;
 }
 
 // BlockIntegral types 18-23 (fpproc.cpp:3966-4079) with HenrotteVector
@@ -1007,11 +920,11 @@ static __global__ void k_mag_a(int N, int axi, const double *__restrict__ V, con
 }
 
 // The problem kinds this post-processor answers; every other is refused with
-// its name.  body runs with the problem's device and arena active.
+// its name (post_entry: xfk_post.h)
 template <class F>
 static int mag_entry(xfk_problem *P, F &&body)
 {
-    try {
+    return post_entry(P, [&]() -> int {
         XFK_REQUIRE(P, XFK_ERR_ARG, "null problem");
         XFK_REQUIRE(!P->electro && !P->heat, XFK_ERR_ARG,
                     "not a magnetics problem: xfk_mag_* post-processes magnetostatic problems (xfk_pot_* is for "
@@ -1021,21 +934,8 @@ static int mag_entry(xfk_problem *P, F &&body)
                     "(Frequency 0)");
         XFK_REQUIRE(!P->comm, XFK_ERR_UNSUPPORTED,
                     "sharded problem: magnetics post-processing needs the whole mesh on one device");
-        XFK_CHECK(hipSetDevice(P->device));
-        int rc;
-        {
-            ArenaScope arena_scope(&P->arena);
-            rc = body();
-        }
-        problem_recycle(P);
-        return rc;
-    } catch (const std::exception &e) {
-        set_error(std::string("post-processing failed: ") + e.what());
-        return XFK_ERR_ARG;
-    } catch (...) {
-        set_error("post-processing failed: unknown exception");
-        return XFK_ERR_ARG;
-    }
+        return XFK_OK;
+    }, body);
 }
 
 // (coordinates in user units, once: mag_prepare_xy of xfk_magpost.h)
@@ -1143,13 +1043,8 @@ static int mag_conlist(xfk_problem *P, const std::vector<int> &p)
 {
     if (P->mag_n2e_ready) return XFK_OK;
     hipStream_t s = P->stream;
-    const int N = P->N, NE = P->NE;
-    std::vector<int> ptr(N + 1, 0);
-    for (size_t k = 0; k < 3 * (size_t)NE; ++k) ptr[p[k] + 1]++;
-    for (int i = 0; i < N; ++i) ptr[i + 1] += ptr[i];
-    std::vector<int> lst(3 * (size_t)NE), fill(ptr.begin(), ptr.end() - 1);
-    for (int e = 0; e < NE; ++e)
-        for (int j = 0; j < 3; ++j) lst[fill[p[3 * (size_t)e + j]]++] = e;
+    std::vector<int> ptr, lst;
+    node_elements(p.data(), P->N, P->NE, ptr, lst);
     XFK_CHECK(upload(P->mag_n2e_ptr, ptr.data(), ptr.size(), s));
     XFK_CHECK(upload(P->mag_n2e, lst.data(), lst.size(), s));
     XFK_CHECK(hipStreamSynchronize(s));   // (ptr and lst leave scope)
@@ -1174,16 +1069,13 @@ static int mag_mask_mesh(xfk_problem *P, double &ms_create)
     XFK_CHECK(d2h(p.data(), P->p_raw.p, sizeof(int) * 3 * (size_t)NE, s));
     XFK_CHECK(d2h(lbl.data(), P->lbl_raw.p, sizeof(int) * NE, s));
     int rc = mag_conlist(P, p);
-    if (rc != XFK_OK) return rc;
-    XFK_CHECK(upload(P->mask_point, P->mag_has_point.data(), (size_t)N, s));
-    XFK_CHECK(P->mask_ext.alloc((size_t)N));
-    rc = launch_mask_exterior(s, N, NE, P->p_raw.p, P->mag_n2e_ptr.p, P->mag_n2e.p, P->mask_ext.p);
+    if (rc == XFK_OK)
+        rc = mask_mesh_marks(P, P->p_raw.p, P->mag_n2e_ptr.p, P->mag_n2e.p, P->mag_has_point.data());
     if (rc != XFK_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const std::vector<PotLabel> lab(std::max<size_t>(1, P->mag_hlab.size()), PotLabel{0, 0});
     if ((rc = mask_aux_create(P, x, y, p, lbl, lab, P->length_units)) != XFK_OK) return rc;
     ms_create = wall_ms(t0);
-    P->mask_ext_ready = true;
     return XFK_OK;
 }
 
@@ -1194,17 +1086,15 @@ static int mag_make_mask(xfk_problem *P, const unsigned char *sel, const double 
 {
     XFK_REQUIRE(sel, XFK_ERR_ARG, "null selection mask (one byte per block label)");
     P->mask_ready = false;
-    const auto t_all = std::chrono::steady_clock::now();
+    MaskInputs I = {};
+    I.t_all = std::chrono::steady_clock::now();
     int rc = mag_prepare_xy(P);
     if (rc != XFK_OK) return rc;
-    hipStream_t s = P->stream;
-    const int N = P->N, NE = P->NE;
     const size_t nlab = P->mag_hlab.size();
-    double ms_create = 0.;
-    if ((rc = mag_mask_mesh(P, ms_create)) != XFK_OK) return rc;
+    if ((rc = mag_mask_mesh(P, I.ms_create)) != XFK_OK) return rc;
 
     // the air test per block and per label (makemask.cpp:108-132), the labels' MaxArea
-    auto t0 = std::chrono::steady_clock::now();
+    I.t_rules = std::chrono::steady_clock::now();
     std::vector<unsigned char> mlab(2 * std::max<size_t>(1, nlab), 0);
     std::vector<double> area(std::max<size_t>(1, nlab), 0.);
     for (size_t k = 0; k < nlab; ++k) {
@@ -1223,47 +1113,19 @@ static int mag_make_mask(xfk_problem *P, const unsigned char *sel, const double 
         mlab[2 * k + 1] = (unsigned char)f;
         if (max_area) area[k] = max_area[P->mag_lab_orig[k]];
     }
-    XFK_CHECK(upload(P->mag_mlab, mlab.data(), mlab.size(), s));
-    XFK_CHECK(upload(P->mask_area, area.data(), area.size(), s));
-    XFK_CHECK(P->mask_flag.alloc(2));
-    XFK_CHECK(P->mask_lv.alloc((size_t)N));
-    XFK_CHECK(P->mask_msk.alloc((size_t)N));
-    XFK_CHECK(hipMemsetAsync(P->mask_flag.p, 0, 2 * sizeof(int), s));
-    MagMaskArgs A = {};
-    A.x = P->mag_x.p;
-    A.p = P->p_raw.p;
-    A.lbl = P->lbl_raw.p;
-    A.n2e_ptr = P->mag_n2e_ptr.p;
-    A.n2e = P->mag_n2e.p;
-    A.mlab = P->mag_mlab.p;
-    A.ext = P->mask_ext.p;
-    A.point = P->mask_point.p;
-    A.axi = P->axi ? 1 : 0;
-    const int GE = (NE + kBlock - 1) / kBlock;
-    if (P->axi) k_mag_mask_on_axis<<<GE, kBlock, 0, s>>>(NE, A, P->mask_flag.p);
-    k_mag_mask_fix<<<(N + kBlock - 1) / kBlock, kBlock, 0, s>>>(N, A, P->mask_flag.p, P->mask_lv.p);
-    k_mag_mask_valid<<<GE, kBlock, 0, s>>>(NE, A, P->mask_lv.p, P->mask_flag.p);
-    XFK_CHECK(hipGetLastError());
-    int flag[2] = {0, 0};
-    XFK_CHECK(d2h(flag, P->mask_flag.p, sizeof(flag), s));   // (the stream is idle after this: mlab and area were read)
-    XFK_REQUIRE(!flag[1], XFK_ERR_ARG, kMagMaskInvalid);
-    const double ms_rules = wall_ms(t0);
-
-    xfk_result res{};
-    if ((rc = mask_aux_solve(P, &res)) != XFK_OK) return rc;
-    P->mask_sel.assign(sel, sel + P->mag_nlabels);
-    P->mask_ready = true;
-    mask_set_info(P, res, ms_create, ms_rules, wall_ms(t_all));
-    return XFK_OK;
-}
-
-// the mask P holds was made for the selection sel
-static bool mag_mask_matches(const xfk_problem *P, const unsigned char *sel)
-{
-    if (!P->mask_ready || !sel || (int)P->mask_sel.size() != P->mag_nlabels) return false;
-    for (size_t k = 0; k < P->mask_sel.size(); ++k)
-        if ((P->mask_sel[k] != 0) != (sel[k] != 0)) return false;
-    return true;
+    I.x = P->mag_x.p;
+    I.p = P->p_raw.p;
+    I.lbl = P->lbl_raw.p;
+    I.n2e_ptr = P->mag_n2e_ptr.p;
+    I.n2e = P->mag_n2e.p;
+    I.lflag = mlab.data();
+    I.area = area.data();
+    I.nentries = area.size();
+    I.point = P->mag_has_point.data();
+    I.sel = sel;
+    I.nsel_labels = (size_t)P->mag_nlabels;
+    I.invalid = kMagMaskInvalid;
+    return mask_make(P, I);
 }
 
 // mag_part: the partials and sums of the mask-free integrals, then those of
@@ -1310,7 +1172,7 @@ static int mag_block_integrals(xfk_problem *P, const unsigned char *sel, double 
     if (rc != XFK_OK) return rc;
     const int G = (P->NE + kPotQBlock - 1) / kPotQBlock;
     XFK_CHECK(P->mag_part.alloc(mag_part_size(G)));
-    const bool stress = mag_mask_matches(P, sel);   // types 18-23: with the mask of this very selection
+    const bool stress = mask_matches(P, sel, (size_t)P->mag_nlabels);   // types 18-23: with the mask of this very selection
     const MagArgs M = mag_args(P);
     if ((rc = mag_launch_integrals(P, M)) != XFK_OK || (stress && (rc = mag_launch_stress(P, M)) != XFK_OK)) {
         set_error("block integral launch failed");
@@ -1447,16 +1309,6 @@ static int mag_point_ready(xfk_problem *P, int smooth, bool grid)
     return rc;
 }
 
-// the points on the device (pp_pts: x, y, then kMagPointVals values each; pp_pel)
-static int mag_upload_points(xfk_problem *P, int n, const double *x, const double *y)
-{
-    XFK_CHECK(P->pp_pts.alloc((2 + kMagPointVals) * (size_t)n));
-    XFK_CHECK(P->pp_pel.alloc((size_t)n));
-    XFK_CHECK(hipMemcpyAsync(P->pp_pts.p, x, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
-    XFK_CHECK(hipMemcpyAsync(P->pp_pts.p + n, y, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
-    return XFK_OK;
-}
-
 static int mag_launch_points(xfk_problem *P, int n, int smooth, int given)
 {
     const MagArgs M = mag_args(P);
@@ -1474,10 +1326,10 @@ static int mag_launch_points(xfk_problem *P, int n, int smooth, int given)
     return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
 }
 
-static int mag_contour_type_check(int type)
+static int mag_contour_check(const xfk_problem *, int nc, const int *ptr, const double *x, const double *y, int type)
 {
     XFK_REQUIRE(type >= 0 && type <= 5, XFK_ERR_ARG, "line integral type out of range: a magnetostatic problem has types 0-5");
-    return XFK_OK;
+    return pp_contour_check(nc, ptr, x, y);
 }
 
 // types 1, 3, 4, 5: the batch on the device, the fields and the grid ready
@@ -1513,14 +1365,9 @@ static int mag_contour_launch(xfk_problem *P, PpContours &J, double *dbg_xy, int
 static void mag_contour_length(const xfk_problem *P, int n, const double *x, const double *y, double &len, double &area)
 {
     const double lc = kMagLengthConv[P->length_units];
-    len = 0;
-    area = 0;
-    for (int i = 0; i < n - 1; ++i) len += mag_cabs_host(x[i + 1] - x[i], y[i + 1] - y[i]);
+    polyline_sums(n, x, y, P->axi, len, area);
     len *= lc;
-    if (P->axi) {
-        for (int i = 0; i < n - 1; ++i) area += (kPI * (x[i] + x[i + 1]) * mag_cabs_host(x[i + 1] - x[i], y[i + 1] - y[i]));
-        area *= std::pow(lc, 2.);
-    }
+    if (P->axi) area *= std::pow(lc, 2.);
 }
 
 // LineIntegral type 0: A at the two end points through the point kernel, then the reference's arithmetic
@@ -1530,14 +1377,9 @@ static int mag_contour_ends(xfk_problem *P, int nc, const int *ptr, const double
     int rc = mag_point_ready(P, 0, true);
     if (rc != XFK_OK) return rc;
     const int n = 2 * nc;
-    std::vector<double> ex(n), ey(n), val(kMagPointVals * (size_t)n);
-    for (int c = 0; c < nc; ++c) {
-        ex[2 * c] = x[ptr[c]];
-        ey[2 * c] = y[ptr[c]];
-        ex[2 * c + 1] = x[ptr[c + 1] - 1];
-        ey[2 * c + 1] = y[ptr[c + 1] - 1];
-    }
-    if ((rc = mag_upload_points(P, n, ex.data(), ey.data())) != XFK_OK) return rc;
+    std::vector<double> ex, ey, val(kMagPointVals * (size_t)n);
+    contour_end_points(nc, ptr, x, y, ex, ey);
+    if ((rc = upload_points(P, n, ex.data(), ey.data(), kMagPointVals)) != XFK_OK) return rc;
     if ((rc = mag_launch_points(P, n, 0, 0)) != XFK_OK) return rc;
     std::vector<int> el(n);
     XFK_CHECK(d2h(el.data(), P->pp_pel.p, sizeof(int) * (size_t)n, P->stream));
@@ -1564,8 +1406,7 @@ static int mag_contour_ends(xfk_problem *P, int nc, const int *ptr, const double
 static int mag_line_integrals(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, int type,
                               int smooth, int npts, double *out, int *missed)
 {
-    int rc = mag_contour_type_check(type);
-    if (rc == XFK_OK) rc = pp_contour_check(nc, ptr, x, y);
+    int rc = mag_contour_check(P, nc, ptr, x, y, type);
     if (rc != XFK_OK || nc == 0) return rc;
     XFK_REQUIRE(out, XFK_ERR_ARG, "null output");
     if (type == 0) return mag_contour_ends(P, nc, ptr, x, y, out, missed);
@@ -1597,28 +1438,6 @@ static int mag_line_integrals(xfk_problem *P, int nc, const int *ptr, const doub
         out[2 * c + 1] = r1;
         if (missed) missed[c] = (int)sums[3 * (size_t)c + 2];
     }
-    return XFK_OK;
-}
-
-// f() between two events on the stream, repeats + 1 times (the first a warm-up): the median in ms
-template <class F>
-static int mag_timed(xfk_problem *P, int repeats, F f, double &out)
-{
-    ScopedEvents<2> ev;
-    XFK_CHECK(ev.create());
-    std::vector<double> t;
-    for (int k = 0; k <= repeats; ++k) {
-        XFK_CHECK(hipEventRecord(ev[0], P->stream));
-        const int r = f();
-        if (r != XFK_OK) return r;
-        XFK_CHECK(hipEventRecord(ev[1], P->stream));
-        XFK_CHECK(hipEventSynchronize(ev[1]));
-        float m = 0;
-        XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
-        if (k) t.push_back(m);
-    }
-    std::sort(t.begin(), t.end());
-    out = t[t.size() / 2];
     return XFK_OK;
 }
 
@@ -1687,7 +1506,7 @@ int xfk_mag_block_integral(xfk_problem *P, const unsigned char *label_selected, 
 {
     return mag_entry(P, [&]() -> int {
         XFK_REQUIRE(type >= 0 && type < kMagTypes, XFK_ERR_ARG, "block integral type out of range (0-25)");
-        XFK_REQUIRE(type < 18 || type > 23 || mag_mask_matches(P, label_selected), XFK_ERR_ARG,
+        XFK_REQUIRE(type < 18 || type > 23 || mask_matches(P, label_selected, (size_t)P->mag_nlabels), XFK_ERR_ARG,
                     "block integral types 18-23 (weighted stress tensor force and torque) need the mask of this "
                     "very selection: xfk_mag_make_mask");
         XFK_REQUIRE(out2, XFK_ERR_ARG, "null output");
@@ -1721,26 +1540,7 @@ int xfk_mag_time(xfk_problem *P, int repeats, double *ms)
         XFK_CHECK(P->mag_part.alloc(mag_part_size(G)));
         XFK_CHECK(P->mag_B.alloc(2 * (size_t)NE));
         const MagArgs M = mag_args(P);
-        ScopedEvents<2> ev;
-        XFK_CHECK(ev.create());
-        std::vector<double> t;
-        // f() between two events on the stream, repeats + 1 times (the first a warm-up)
-        auto timed = [&](auto f, double &out) -> int {
-            for (int k = 0; k <= repeats; ++k) {
-                XFK_CHECK(hipEventRecord(ev[0], s));
-                const int r = f();
-                if (r != XFK_OK) return r;
-                XFK_CHECK(hipEventRecord(ev[1], s));
-                XFK_CHECK(hipEventSynchronize(ev[1]));
-                float m = 0;
-                XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
-                if (k) t.push_back(m);
-            }
-            std::sort(t.begin(), t.end());
-            out = t[t.size() / 2];
-            t.clear();
-            return XFK_OK;
-        };
+        auto timed = [&](auto f, double &out) { return timed_median(s, repeats, f, out); };
         rc = timed([&] {
             if (P->axi) k_mag_element_b<true><<<GB, kBlock, 0, s>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
             else k_mag_element_b<false><<<GB, kBlock, 0, s>>>(NE, M, P->mag_B.p, P->mag_B.p + NE);
@@ -1797,25 +1597,10 @@ int xfk_mag_stress_time(xfk_problem *P, int repeats, double *ms)
         int rc = mag_labels(P, P->mask_sel.data(), false);
         if (rc == XFK_OK) rc = mag_prepare(P);
         if (rc != XFK_OK) return rc;
-        hipStream_t s = P->stream;
         const int G = (P->NE + kPotQBlock - 1) / kPotQBlock;
         XFK_CHECK(P->mag_part.alloc(mag_part_size(G)));
         const MagArgs M = mag_args(P);
-        ScopedEvents<2> ev;
-        XFK_CHECK(ev.create());
-        std::vector<double> t;
-        for (int k = 0; k <= repeats; ++k) {   // (the first a warm-up)
-            XFK_CHECK(hipEventRecord(ev[0], s));
-            if ((rc = mag_launch_stress(P, M)) != XFK_OK) return rc;
-            XFK_CHECK(hipEventRecord(ev[1], s));
-            XFK_CHECK(hipEventSynchronize(ev[1]));
-            float m = 0;
-            XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
-            if (k) t.push_back(m);
-        }
-        std::sort(t.begin(), t.end());
-        *ms = t[t.size() / 2];
-        return XFK_OK;
+        return timed_median(P->stream, repeats, [&] { return mag_launch_stress(P, M); }, *ms);
     });
 }
 
@@ -1837,7 +1622,7 @@ int xfk_mag_point_values(xfk_problem *P, int n, const double *x, const double *y
         if (n == 0) return XFK_OK;
         XFK_REQUIRE(x && y && elem && out, XFK_ERR_ARG, "null point arrays");
         int rc = mag_point_ready(P, smooth, true);
-        if (rc == XFK_OK) rc = mag_upload_points(P, n, x, y);
+        if (rc == XFK_OK) rc = upload_points(P, n, x, y, kMagPointVals);
         if (rc == XFK_OK) rc = mag_launch_points(P, n, smooth, 0);
         if (rc != XFK_OK) return rc;
         XFK_CHECK(d2h(elem, P->pp_pel.p, sizeof(int) * (size_t)n, P->stream));
@@ -1856,7 +1641,7 @@ int xfk_mag_point_values_at(xfk_problem *P, int n, const double *x, const double
         for (int i = 0; i < n; ++i)
             XFK_REQUIRE(elem[i] >= -1 && elem[i] < P->NE, XFK_ERR_ARG, "a point's element is outside the element range");
         int rc = mag_point_ready(P, smooth, false);
-        if (rc == XFK_OK) rc = mag_upload_points(P, n, x, y);
+        if (rc == XFK_OK) rc = upload_points(P, n, x, y, kMagPointVals);
         if (rc != XFK_OK) return rc;
         XFK_CHECK(hipMemcpyAsync(P->pp_pel.p, elem, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, P->stream));
         if ((rc = mag_launch_points(P, n, smooth, 1)) != XFK_OK) return rc;
@@ -1887,24 +1672,8 @@ int xfk_mag_contour_samples(xfk_problem *P, int n, const double *x, const double
                             int *elem)
 {
     return mag_entry(P, [&]() -> int {
-        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of contour points");
-        const int ptr[2] = {0, n};
-        int rc = mag_contour_type_check(type);
-        if (rc == XFK_OK) rc = pp_contour_check(1, ptr, x, y);
-        if (rc != XFK_OK) return rc;
-        XFK_REQUIRE(type != 0 && type != 2, XFK_ERR_ARG, "line integral types 0 and 2 take no samples");
-        XFK_REQUIRE(xy && elem, XFK_ERR_ARG, "null output");
-        PpContours J;
-        if ((rc = mag_contour_prepare(P, 1, ptr, x, y, type, 0, npts, J)) != XFK_OK) return rc;
-        const size_t ns = (size_t)(n - 1) * J.npts;
-        DBuf<double> dxy;
-        DBuf<int> del;
-        XFK_CHECK(dxy.alloc(2 * ns));
-        XFK_CHECK(del.alloc(ns));
-        if ((rc = mag_contour_launch(P, J, dxy.p, del.p)) != XFK_OK) return rc;
-        XFK_CHECK(d2h(xy, dxy.p, sizeof(double) * 2 * ns, P->stream));
-        XFK_CHECK(d2h(elem, del.p, sizeof(int) * ns, P->stream));
-        return XFK_OK;
+        return contour_samples(P, n, x, y, type, npts, xy, elem, mag_contour_check, mag_contour_prepare,
+                               mag_contour_launch);
     });
 }
 
@@ -1915,15 +1684,15 @@ int xfk_mag_point_time(xfk_problem *P, int n, const double *x, const double *y, 
                     "xfk_mag_point_time needs points, repeats > 0 and its output");
         int rc = mag_point_ready(P, 1, true);
         if (rc != XFK_OK) return rc;
-        if ((rc = mag_timed(P, repeats, [&] { return mag_launch_corners(P, nullptr); }, ms4[0])) != XFK_OK) return rc;
-        rc = mag_timed(P, repeats, [&] {
+        if ((rc = timed_median(P->stream, repeats, [&] { return mag_launch_corners(P, nullptr); }, ms4[0])) != XFK_OK) return rc;
+        rc = timed_median(P->stream, repeats, [&] {
             P->pp_grid_ready = false;
             return pp_grid_build(P, P->mag_x.p, P->mag_y.p, P->p_raw.p);
         }, ms4[1]);
         if (rc != XFK_OK) return rc;
-        if ((rc = mag_upload_points(P, n, x, y)) != XFK_OK) return rc;
+        if ((rc = upload_points(P, n, x, y, kMagPointVals)) != XFK_OK) return rc;
         for (int smooth = 0; smooth < 2; ++smooth)
-            if ((rc = mag_timed(P, repeats, [&] { return mag_launch_points(P, n, smooth, 0); }, ms4[2 + smooth])) != XFK_OK)
+            if ((rc = timed_median(P->stream, repeats, [&] { return mag_launch_points(P, n, smooth, 0); }, ms4[2 + smooth])) != XFK_OK)
                 return rc;
         return XFK_OK;
     });
@@ -1935,13 +1704,8 @@ int xfk_mag_contour_time(xfk_problem *P, int n_contours, const int *ptr, const d
     return mag_entry(P, [&]() -> int {
         XFK_REQUIRE(repeats > 0 && ms && n_contours > 0, XFK_ERR_ARG,
                     "xfk_mag_contour_time needs contours, repeats > 0 and its output");
-        int rc = mag_contour_type_check(type);
-        if (rc == XFK_OK) rc = pp_contour_check(n_contours, ptr, x, y);
-        if (rc != XFK_OK) return rc;
-        XFK_REQUIRE(type != 0 && type != 2, XFK_ERR_ARG, "line integral types 0 and 2 launch no contour kernel");
-        PpContours J;
-        if ((rc = mag_contour_prepare(P, n_contours, ptr, x, y, type, smooth, npts, J)) != XFK_OK) return rc;
-        return mag_timed(P, repeats, [&] { return mag_contour_launch(P, J, nullptr, nullptr); }, *ms);
+        return contour_time(P, n_contours, ptr, x, y, type, smooth, npts, repeats, ms, mag_contour_check,
+                            mag_contour_prepare, mag_contour_launch);
     });
 }
 

@@ -27,6 +27,7 @@
 #pragma clang fp contract(off)
 
 #include "xfk_magpost.h"
+#include "xfk_post.h"
 
 #include <cmath>
 
@@ -553,11 +554,11 @@ void mag_ac_host_tables(xfk_problem *P, const xfk_problem_desc *d, const xfk_har
 }
 
 // The problem kinds this post-processor answers; every other is refused with
-// its name.  body runs with the problem's device and arena active.
+// its name (post_entry: xfk_post.h)
 template <class F>
 static int mag_ac_entry(xfk_problem *P, F &&body)
 {
-    try {
+    return post_entry(P, [&]() -> int {
         XFK_REQUIRE(P, XFK_ERR_ARG, "null problem");
         XFK_REQUIRE(!P->electro && !P->heat, XFK_ERR_ARG,
                     "not a magnetics problem: xfk_mag_ac_* post-processes time-harmonic magnetics problems (xfk_pot_* "
@@ -570,21 +571,8 @@ static int mag_ac_entry(xfk_problem *P, F &&body)
         XFK_REQUIRE(P->mag_prev_type == 0, XFK_ERR_UNSUPPORTED,
                     "the problem was loaded with PrevType != 0 (incremental permeability about a previous solution): "
                     "its post-processing is not built");
-        XFK_CHECK(hipSetDevice(P->device));
-        int rc;
-        {
-            ArenaScope arena_scope(&P->arena);
-            rc = body();
-        }
-        problem_recycle(P);
-        return rc;
-    } catch (const std::exception &e) {
-        set_error(std::string("post-processing failed: ") + e.what());
-        return XFK_ERR_ARG;
-    } catch (...) {
-        set_error("post-processing failed: unknown exception");
-        return XFK_ERR_ARG;
-    }
+        return XFK_OK;
+    }, body);
 }
 
 // coordinates in user units, A of the solution, the block table on the device
@@ -794,26 +782,7 @@ int xfk_mag_ac_time(xfk_problem *P, int repeats, double *ms)
         XFK_CHECK(P->mag_B.alloc(4 * NE));
         const MagArgs M = mag_mesh_args(P);
         const MagAcArgs C = mag_ac_args(P);
-        ScopedEvents<2> ev;
-        XFK_CHECK(ev.create());
-        std::vector<double> t;
-        // f() between two events on the stream, repeats + 1 times (the first a warm-up)
-        auto timed = [&](auto f, double &out) -> int {
-            for (int k = 0; k <= repeats; ++k) {
-                XFK_CHECK(hipEventRecord(ev[0], s));
-                const int r = f();
-                if (r != XFK_OK) return r;
-                XFK_CHECK(hipEventRecord(ev[1], s));
-                XFK_CHECK(hipEventSynchronize(ev[1]));
-                float m = 0;
-                XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
-                if (k) t.push_back(m);
-            }
-            std::sort(t.begin(), t.end());
-            out = t[t.size() / 2];
-            t.clear();
-            return XFK_OK;
-        };
+        auto timed = [&](auto f, double &out) { return timed_median(s, repeats, f, out); };
         rc = timed([&] { return mag_ac_launch_element_b(P, M); }, ms[0]);
         if (rc != XFK_OK) return rc;
         return timed([&] { return mag_ac_launch_integrals(P, M, C); }, ms[1]);

@@ -7,11 +7,10 @@
 //   corner fields     getNodalD (PostProcessor.cpp:894-1092)
 //   block integrals   blockIntegral types 0-4 (epproc.cpp:268-397,
 //                     hpproc.cpp:584-646)
-//   the mask          makeMask (PostProcessor.cpp:497-725) with isKosher
-//                     (400-430), FindBoundaryEdges (1097-1150) and
-//                     isSelectionOnAxis (epproc.cpp:471-487); HenrotteVector
-//                     (742-768) and blockIntegral types 5 and 6
-//                     (epproc.cpp:329-389): electrostatics only
+//   force and torque  HenrotteVector (PostProcessor.cpp:742-768) and
+//                     blockIntegral types 5 and 6 (epproc.cpp:329-389) over the
+//                     mask of makeMask (xfk_mask.hip; the air test is
+//                     CSMaterialProp::isAir): electrostatics only
 //   point values      InTriangleTest (PostProcessor.cpp:359-398), getPointD
 //                     (1153-1188), getPointValues (epproc.cpp:434-469,
 //                     hpproc.cpp:332-366) over a uniform cell grid
@@ -405,195 +404,6 @@ __global__ void __launch_bounds__(kPotQBlock) k_pp_integrals_seq(int NE, PpArgs 
         __syncthreads();
     }
     if (threadIdx.x < 7) out[threadIdx.x] = s;
-}
-
-// --- the weighted stress tensor mask (PostProcessor::makeMask) ---------------
-//
-// A second finite-element problem on the same mesh: a Laplacian weighted per
-// element by its label's mesh-size specification, nodal values fixed by the
-// rules of PostProcessor.cpp:545-629, solved and thresholded at 0.5 into a 0/1
-// nodal mask; the force and the torque then sum a stress expression against
-// the gradient of that mask over all elements (epproc.cpp:329-389).  The
-// rules are independent per node apart from their order, so a thread per node
-// applies them in that order; the solve is the static driver's, on an
-// auxiliary problem over the mesh's own connectivity (no conductors, no
-// periodic pairs, as the reference).
-
-// CSMaterialProp::isAir (CMaterialProp.cpp:1603-1609)
-__device__ __forceinline__ bool pp_is_air(const EsBlock &b) { return (b.ex == 1) && (b.ey == 1) && (b.qv == 0); }
-
-// FindBoundaryEdges (PostProcessor.cpp:1097-1150): one thread per (element,
-// side).  Side j runs from p[(j + 1) % 3] to p[(j + 2) % 3]; it is exterior
-// when no other element around its first node holds its second.  ext (zeroed
-// by the caller) marks both ends; every store writes the same 1.
-__global__ void __launch_bounds__(kBlock) k_mask_exterior(int NE, const int *__restrict__ p,
-                                                          const int *__restrict__ n2e_ptr,
-                                                          const int *__restrict__ n2e, unsigned char *__restrict__ ext)
-{
-    const int t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= 3 * NE) return;
-    const int e = t / 3, j = t - 3 * e;
-    const int org = p[3 * e + (j + 1) % 3], dest = p[3 * e + (j + 2) % 3];
-    bool done = false;
-    for (int m = n2e_ptr[org]; m < n2e_ptr[org + 1] && !done; ++m) {
-        const int ei = n2e[m];
-        if (ei == e) continue;
-        done = p[3 * ei] == dest || p[3 * ei + 1] == dest || p[3 * ei + 2] == dest;
-    }
-    if (!done) {
-        ext[org] = 1;
-        ext[dest] = 1;
-    }
-}
-
-// isSelectionOnAxis (epproc.cpp:471-487, PostProcessor.cpp:479-494), for an
-// axisymmetric problem: a selected element or a selected node at r < 1e-6.
-// One thread per element and per node; flag[0] (zeroed by the caller) is set.
-__global__ void __launch_bounds__(kBlock) k_mask_on_axis(int NE, int N, PpArgs A,
-                                                         const unsigned char *__restrict__ sel,
-                                                         const unsigned char *__restrict__ nsel,
-                                                         int *__restrict__ flag)
-{
-    const int t = blockIdx.x * kBlock + threadIdx.x;
-    bool on = false;
-    if (t < NE && sel[A.lbl[t]])
-        for (int j = 0; j < 3; ++j) on |= A.x[A.p[3 * t + j]] < 1.e-6;
-    if (t < N && nsel && nsel[t]) on |= A.x[t] < 1.e-6;
-    if (on) flag[0] = 1;
-}
-
-// The fixed values L.V of makeMask (PostProcessor.cpp:545-629), one thread per
-// node, the rules in the reference's order so that a later one overwrites an
-// earlier one as the sequential code does; -1: free.
-__global__ void __launch_bounds__(kBlock) k_mask_fix(int N, PpArgs A, const int *__restrict__ Q,
-                                                     const int *__restrict__ n2e_ptr, const int *__restrict__ n2e,
-                                                     const unsigned char *__restrict__ ext,
-                                                     const unsigned char *__restrict__ sel,
-                                                     const unsigned char *__restrict__ point,
-                                                     const unsigned char *__restrict__ nsel,
-                                                     const int *__restrict__ flag, double *__restrict__ lv)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= N) return;
-    const int l0 = n2e_ptr[i], l1 = n2e_ptr[i + 1];
-    // a fixed point property or any conductor node
-    double v = (Q[i] != -2) ? 0. : -1.;
-    // the ends of exterior edges; with the selection on the axis only where isKosher (PostProcessor.cpp:400-430)
-    if (ext[i]) {
-        bool kosher = true;
-        if (flag[0] && A.axi && !(A.x[i] > 1.e-6)) {
-            int score = 0;
-            for (int m = l0; m < l1; ++m)
-                for (int j = 0; j < 3; ++j) {
-                    const int n = A.p[3 * n2e[m] + j];
-                    if ((n != i) && (A.x[n] < 1.e-6)) score++;
-                }
-            kosher = !(score > 1);
-        }
-        if (kosher) v = 0.;
-    }
-    // the nodes of selected elements 1, of unselected elements that are not
-    // air 0, in element order: the highest-numbered such element decides
-    int last = -1;
-    bool last_sel = false;
-    for (int m = l0; m < l1; ++m) {
-        const int e = n2e[m];
-        if (e < last) continue;
-        const int lb = A.lbl[e];
-        const bool s = sel[lb] != 0;
-        if (s || !pp_is_air(A.es[A.labels[lb].blk])) {
-            last = e;
-            last_sel = s;
-        }
-    }
-    if (last >= 0) v = last_sel ? 1. : 0.;
-    // a still-free node with a point property
-    if (point[i] && (v < 0)) v = 0.;
-    // a selected node
-    if (nsel && nsel[i]) v = 1.;
-    lv[i] = v;
-}
-
-// makeMask's consistency check (PostProcessor.cpp:655-671): an unselected
-// element that is not air with a node not fixed at exactly 0 sets flag[1]
-__global__ void __launch_bounds__(kBlock) k_mask_valid(int NE, PpArgs A, const unsigned char *__restrict__ sel,
-                                                       const double *__restrict__ lv, int *__restrict__ flag)
-{
-    const int e = blockIdx.x * kBlock + threadIdx.x;
-    if (e >= NE) return;
-    const int lb = A.lbl[e];
-    if (sel[lb] || pp_is_air(A.es[A.labels[lb].blk])) return;
-    int k = 0;
-    for (int j = 0; j < 3; ++j)
-        if (lv[A.p[3 * e + j]] == 0) k++;
-    if (k < 3) flag[1] = 1;
-}
-
-// One element of makeMask (PostProcessor.cpp:631-708) for the row gather of
-// xfk_potential.h: Me = v (p_j p_k + q_j q_k) / area with v the square root of
-// the label's MaxArea (of the element's area when that is <= 0), prescribed
-// values eliminated per element.  The reference stores the negated system
-// (L.Put(L.Get - Me), b -= be), which is what the gather's "-=" builds; the
-// element hands it -Me and -be, so the assembled system is the positive
-// definite one the PCG needs.  It has the same solution.  The mask Laplacian
-// is planar for both problem types.
-struct MaskPhys {
-    struct Args {
-        const double *lv, *max_area;
-    };
-
-    template <bool AXI>
-    static __device__ __forceinline__ void element(int e, const int (&g)[3], const RowArgs &A, const Args &S,
-                                                   const double (&X)[3], const double (&Y)[3], const PotLabel &,
-                                                   double (&Me)[3][3], double (&be)[3])
-    {
-        double p[3], q[3];
-        p[0] = Y[1] - Y[2]; p[1] = Y[2] - Y[0]; p[2] = Y[0] - Y[1];
-        q[0] = X[2] - X[1]; q[1] = X[0] - X[2]; q[2] = X[1] - X[0];
-        const double area = (p[0] * q[1] - p[1] * q[0]) / 2.;
-        double v = S.max_area ? S.max_area[A.lbl[e]] : 0.;
-        if (v <= 0) v = sqrt(area);
-        else v = sqrt(v);
-        const double V[3] = {S.lv[g[0]], S.lv[g[1]], S.lv[g[2]]};
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            be[j] = 0.;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) Me[j][k] = v * (p[j] * p[k] + q[j] * q[k]) / area;
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            if (V[j] >= 0) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    if (j != k) {
-                        be[k] -= Me[k][j] * V[j];
-                        Me[k][j] = 0.;
-                        Me[j][k] = 0.;
-                    }
-                }
-                be[j] = V[j] * Me[j][j];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            be[j] = -be[j];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) Me[j][k] = -Me[j][k];
-        }
-    }
-};
-
-void launch_mask_rows(hipStream_t s, xfk_problem *P)
-{
-    launch_pot_rows<MaskPhys>(s, P, MaskPhys::Args{P->mask_lv_p, P->mask_area_p});
-}
-
-__global__ void __launch_bounds__(kBlock) k_mask_threshold(int N, const double *__restrict__ W,
-                                                           double *__restrict__ msk)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < N) msk[i] = (W[i] > 0.5) ? 1. : 0.;
 }
 
 // blockIntegral types 5 and 6 (epproc.cpp:329-389) with HenrotteVector
@@ -1102,12 +912,8 @@ static int pp_mesh(xfk_problem *P)
         x[i] = x[i] / u;
         y[i] = y[i] / u;
     }
-    std::vector<int> ptr(N + 1, 0);
-    for (size_t k = 0; k < 3 * (size_t)NE; ++k) ptr[p[k] + 1]++;
-    for (int i = 0; i < N; ++i) ptr[i + 1] += ptr[i];
-    std::vector<int> lst(3 * (size_t)NE), fill(ptr.begin(), ptr.end() - 1);
-    for (int e = 0; e < NE; ++e)
-        for (int j = 0; j < 3; ++j) lst[fill[p[3 * (size_t)e + j]]++] = e;
+    std::vector<int> ptr, lst;
+    node_elements(p.data(), N, NE, ptr, lst);
     std::atomic<bool> failed{false};   // (an exception must not leave a worker thread)
     host_par_for(N, 1 << 14, [&](long long a, long long b) {
       try {
@@ -1351,35 +1157,18 @@ hipError_t xfk::warm_module_postproc()
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_pp_scan));
 }
 
-// One post-processing entry point: no C++ exception crosses the C boundary
-// (the host tables allocate; the sorting workers catch their own), the
-// problem's device and arena are active while body runs, and blocks retired
-// meanwhile (scratch, the old block of a grown buffer) become reusable once
-// the stream is idle, as at the end of a solve.
+// The problem kinds this post-processor answers (post_entry: xfk_post.h)
 template <class F>
 static int pp_entry(xfk_problem *P, bool need_solution, F &&body)
 {
-    try {
+    return post_entry(P, [&]() -> int {
         XFK_REQUIRE(P, XFK_ERR_ARG, "null problem");
         XFK_REQUIRE(P->electro || P->heat, XFK_ERR_ARG,
                     "not a scalar-potential problem: post-processing is for electrostatic and heat-flow problems");
         XFK_REQUIRE(!need_solution || P->pot_solved, XFK_ERR_ARG,
                     "no solution yet (solve the problem or xfk_pot_set_solution)");
-        XFK_CHECK(hipSetDevice(P->device));
-        int rc;
-        {
-            ArenaScope arena_scope(&P->arena);
-            rc = body();
-        }
-        problem_recycle(P);
-        return rc;
-    } catch (const std::exception &e) {
-        set_error(std::string("post-processing failed: ") + e.what());
-        return XFK_ERR_ARG;
-    } catch (...) {
-        set_error("post-processing failed: unknown exception");
-        return XFK_ERR_ARG;
-    }
+        return XFK_OK;
+    }, body);
 }
 
 static int pp_launch_points(xfk_problem *P, int n, const double *px, const double *py, int smooth, double *o,
@@ -1400,82 +1189,9 @@ static int pp_launch_points(xfk_problem *P, int n, const double *px, const doubl
     return XFK_OK;
 }
 
-// the points on the device: x, y, then 8 values each
-static int pp_upload_points(xfk_problem *P, int n, const double *x, const double *y)
-{
-    XFK_CHECK(P->pp_pts.alloc(10 * (size_t)n));
-    XFK_CHECK(P->pp_pel.alloc((size_t)n));
-    XFK_CHECK(hipMemcpyAsync(P->pp_pts.p, x, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
-    XFK_CHECK(hipMemcpyAsync(P->pp_pts.p + n, y, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
-    return XFK_OK;
-}
+// --- the weighted stress tensor mask: host side (the rest is xfk_mask.hip) -------
 
-// --- the weighted stress tensor mask: host side --------------------------------
-
-// The auxiliary problem of the mask, owned by P (P->mask_aux): the mesh's own
-// connectivity p (a floating conductor's nodes stay apart), coordinates in
-// user units, no boundary data at all -- the element eliminates the prescribed
-// values itself.  lab: a table the length of the problem's labels (the mask's
-// element reads none of it).  Created once and kept with P.
-int xfk::mask_aux_create(xfk_problem *P, const std::vector<double> &x, const std::vector<double> &y,
-                    const std::vector<int> &p, const std::vector<int> &lbl, const std::vector<PotLabel> &lab,
-                    int length_units)
-{
-    if (P->mask_aux) return XFK_OK;
-    const int N = P->N, NE = P->NE;
-    GlobalPrep G;
-    G.blk.assign(1, DevBlock{});
-    G.lab.assign(1, DevLabel{});
-    G.lin.assign(1, DevLine{});
-    G.circ.assign(1, DevCirc{});
-    G.hB.assign(1, 0.);
-    G.hH.assign(1, 0.);
-    G.hS.assign(1, 0.);
-    G.ebits.assign(NE, 0);
-    G.fixed.assign(N, 0);
-    G.first.assign(N, 0.0);
-    G.last = G.first;
-    xfk_problem_desc md = {};
-    md.n_nodes = N;
-    md.x = x.data();
-    md.y = y.data();
-    md.n_elems = NE;
-    md.p = p.data();
-    md.lbl = lbl.data();
-    md.n_blocks = 1;
-    md.n_labels = (int)lab.size();
-    md.precision = P->precision;
-    md.length_units = length_units;
-    md.relax = 1.0;
-    md.problem_type = XFK_PLANAR;
-    xfk_problem *Q = nullptr;
-    int rc = build_local(&md, G, nullptr, P->device, nullptr, &Q);
-    if (rc != XFK_OK) return rc;
-    {
-        ArenaScope arena_scope(&Q->arena);
-        const std::vector<unsigned char> none(N, 0);
-        hipError_t e = upload(Q->pot_p, p.data(), p.size(), Q->stream);
-        if (e == hipSuccess) e = upload(Q->pot_labels, lab.data(), lab.size(), Q->stream);
-        if (e == hipSuccess) e = upload(Q->pot_slave, none.data(), none.size(), Q->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(Q->stream);
-        if (e != hipSuccess) {
-            set_error(std::string("upload failed: ") + hipGetErrorString(e));
-            xfk_problem_destroy(Q);
-            return XFK_ERR_HIP;
-        }
-    }
-    Q->mask = true;
-    Q->pot_depth = 1;
-    rc = reserve_first_solve(&Q);
-    if (rc != XFK_OK) {
-        xfk_problem_destroy(Q);
-        return rc;
-    }
-    P->mask_aux = Q;
-    return XFK_OK;
-}
-
-// ... of a scalar-potential problem: from its post-processing mesh tables
+// the mask's auxiliary problem of a scalar-potential problem: from its post-processing mesh tables
 static int pot_mask_aux_create(xfk_problem *P)
 {
     if (P->mask_aux) return XFK_OK;
@@ -1492,129 +1208,59 @@ static int pot_mask_aux_create(xfk_problem *P)
     return mask_aux_create(P, x, y, p, lbl, lab, P->pot_length_units);
 }
 
-// The Laplace solve of the mask on P's auxiliary problem, from the fixed
-// values in P->mask_lv and the labels' MaxArea in P->mask_area: symbolic phase
-// (first call), row gather, AMG-PCG to the problem's Precision; then the
-// threshold into P->mask_msk.  Host-synchronising.
-int xfk::mask_aux_solve(xfk_problem *P, xfk_result *res)
-{
-    xfk_problem *Q = P->mask_aux;
-    hipStream_t s = P->stream;
-    const int N = P->N;
-    Q->mask_lv_p = P->mask_lv.p;
-    Q->mask_area_p = P->mask_area.p;
-    Q->precision = P->precision;
-    Q->precond = P->precond;
-    int rc;
-    {
-        ArenaScope arena_scope(&Q->arena);
-        rc = static2d_run(Q, 0, res);
-        problem_recycle(Q);
-    }
-    if (rc != XFK_OK) return rc;
-    k_mask_threshold<<<(N + kBlock - 1) / kBlock, kBlock, 0, s>>>(N, Q->V.p, P->mask_msk.p);
-    XFK_CHECK(hipGetLastError());
-    XFK_CHECK(hipStreamSynchronize(s));
-    return XFK_OK;
-}
-
-// what xfk_pot_mask_info / xfk_mag_mask_info report of the last mask
-void xfk::mask_set_info(xfk_problem *P, const xfk_result &res, double ms_create, double ms_rules, double ms_total)
-{
-    double *o = P->mask_info;
-    o[0] = (double)res.cg_iters;
-    o[1] = ms_create;
-    o[2] = ms_rules;
-    o[3] = res.ms_symbolic;
-    o[4] = res.ms_assemble;
-    o[5] = res.ms_amg_setup;
-    o[6] = res.ms_solve;
-    o[7] = ms_total;
-}
-
-// FindBoundaryEdges into ext[N] (zeroed here) for a mesh and its node -> element lists
-int xfk::launch_mask_exterior(hipStream_t s, int N, int NE, const int *p, const int *n2e_ptr, const int *n2e,
-                         unsigned char *ext)
-{
-    XFK_CHECK(hipMemsetAsync(ext, 0, (size_t)N, s));
-    k_mask_exterior<<<(3 * NE + kBlock - 1) / kBlock, kBlock, 0, s>>>(NE, p, n2e_ptr, n2e, ext);
-    XFK_CHECK(hipGetLastError());
-    return XFK_OK;
-}
-
 static const char *const kMaskInvalid =
     "The selected region is invalid. A valid selection cannot abut a region which is not free space.";
+
+// CSMaterialProp::isAir (CMaterialProp.cpp:1603-1609)
+static bool pp_is_air(const EsBlock &b) { return (b.ex == 1) && (b.ey == 1) && (b.qv == 0); }
 
 // PostProcessor::makeMask for the selection (one byte per label; nsel, one
 // byte per node, may be null; max_area, one double per label, may be null: the
 // element areas weight the Laplacian)
-static int mask_make(xfk_problem *P, const unsigned char *sel, const unsigned char *nsel, const double *max_area)
+static int pot_make_mask(xfk_problem *P, const unsigned char *sel, const unsigned char *nsel, const double *max_area)
 {
     XFK_REQUIRE(P->electro, XFK_ERR_ARG,
                 "the weighted stress tensor mask is for electrostatic problems: heat-flow problems have no "
                 "integrals 5 and 6");
     XFK_REQUIRE(sel, XFK_ERR_ARG, "null selection mask (one byte per block label)");
     P->mask_ready = false;
-    const auto t_all = std::chrono::steady_clock::now();
+    MaskInputs I = {};
+    I.t_all = std::chrono::steady_clock::now();
     int rc = pp_mesh(P);
     if (rc != XFK_OK) return rc;
-    hipStream_t s = P->stream;
-    const int N = P->N, NE = P->NE;
     const size_t nlab = P->pot_labels.n;
-    auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = std::chrono::steady_clock::now();
     const bool fresh = !P->mask_aux;
     if ((rc = pot_mask_aux_create(P)) != XFK_OK) return rc;
-    const double ms_create = fresh ? wall_ms(t0) : 0.;
-
-    // the fixed values and the validity of the selection
-    t0 = std::chrono::steady_clock::now();
-    const PpArgs A = pp_args(P);
-    XFK_CHECK(P->pp_sel.alloc(nlab));
-    XFK_CHECK(hipMemcpyAsync(P->pp_sel.p, sel, nlab, hipMemcpyHostToDevice, s));
+    I.ms_create = fresh ? wall_ms(t0) : 0.;
+    // the rules begin: selected, and not air by the label's block
+    I.t_rules = std::chrono::steady_clock::now();
+    std::vector<PotLabel> lab(nlab);
+    std::vector<EsBlock> blk(P->es_blocks.n);
+    XFK_CHECK(d2h(lab.data(), P->pot_labels.p, sizeof(PotLabel) * nlab, P->stream));
+    XFK_CHECK(d2h(blk.data(), P->es_blocks.p, sizeof(EsBlock) * blk.size(), P->stream));
+    std::vector<unsigned char> lflag(2 * nlab);
+    for (size_t k = 0; k < nlab; ++k) {
+        lflag[2 * k] = sel[k] ? 1 : 0;
+        lflag[2 * k + 1] = pp_is_air(blk[lab[k].blk]) ? 0 : 1;
+    }
     std::vector<double> area(nlab, 0.);
     if (max_area) area.assign(max_area, max_area + nlab);
-    XFK_CHECK(upload(P->mask_area, area.data(), area.size(), s));
-    if (nsel) XFK_CHECK(upload(P->mask_nsel, nsel, (size_t)N, s));
-    const unsigned char *nsel_dev = nsel ? P->mask_nsel.p : nullptr;
-    if (!P->mask_ext_ready) {   // (the exterior edges and the point marks are the mesh's)
-        XFK_CHECK(upload(P->mask_point, P->pot_has_point.data(), (size_t)N, s));
-        XFK_CHECK(P->mask_ext.alloc((size_t)N));
-        if ((rc = launch_mask_exterior(s, N, NE, P->pot_p.p, P->pp_n2e_ptr.p, P->pp_n2e.p, P->mask_ext.p)) != XFK_OK)
-            return rc;
-        P->mask_ext_ready = true;
-    }
-    XFK_CHECK(P->mask_flag.alloc(2));
-    XFK_CHECK(P->mask_lv.alloc((size_t)N));
-    XFK_CHECK(P->mask_msk.alloc((size_t)N));
-    XFK_CHECK(hipMemsetAsync(P->mask_flag.p, 0, 2 * sizeof(int), s));
-    if (P->axi)
-        k_mask_on_axis<<<(std::max(NE, N) + kBlock - 1) / kBlock, kBlock, 0, s>>>(NE, N, A, P->pp_sel.p, nsel_dev,
-                                                                                 P->mask_flag.p);
-    k_mask_fix<<<(N + kBlock - 1) / kBlock, kBlock, 0, s>>>(N, A, P->pp_q.p, P->pp_n2e_ptr.p, P->pp_n2e.p,
-                                                            P->mask_ext.p, P->pp_sel.p, P->mask_point.p, nsel_dev,
-                                                            P->mask_flag.p, P->mask_lv.p);
-    k_mask_valid<<<(NE + kBlock - 1) / kBlock, kBlock, 0, s>>>(NE, A, P->pp_sel.p, P->mask_lv.p, P->mask_flag.p);
-    XFK_CHECK(hipGetLastError());
-    int flag[2] = {0, 0};
-    XFK_CHECK(d2h(flag, P->mask_flag.p, sizeof(flag), s));   // (the stream is idle after this: area and nsel were read)
-    XFK_REQUIRE(!flag[1], XFK_ERR_ARG, kMaskInvalid);
-    const double ms_rules = wall_ms(t0);
-
-    xfk_result res{};
-    if ((rc = mask_aux_solve(P, &res)) != XFK_OK) return rc;
-    P->mask_sel.assign(sel, sel + nlab);
-    P->mask_ready = true;
-    mask_set_info(P, res, ms_create, ms_rules, wall_ms(t_all));
-    return XFK_OK;
-}
-
-// the mask P holds was made for the selection sel
-static bool mask_matches(const xfk_problem *P, const unsigned char *sel)
-{
-    if (!P->mask_ready || !sel || P->mask_sel.size() != P->pot_labels.n) return false;
-    for (size_t k = 0; k < P->mask_sel.size(); ++k)
-        if ((P->mask_sel[k] != 0) != (sel[k] != 0)) return false;
-    return true;
+    I.x = P->pp_x.p;
+    I.p = P->pot_p.p;
+    I.lbl = P->lbl_raw.p;
+    I.n2e_ptr = P->pp_n2e_ptr.p;
+    I.n2e = P->pp_n2e.p;
+    I.lflag = lflag.data();
+    I.area = area.data();
+    I.nentries = nlab;
+    I.q = P->pp_q.p;
+    I.nsel = nsel;
+    I.point = P->pot_has_point.data();
+    I.sel = sel;
+    I.nsel_labels = nlab;
+    I.invalid = kMaskInvalid;
+    return mask_make(P, I);
 }
 
 // the three sums of k_pp_stress over all elements, in a fixed order: the x and
@@ -1642,8 +1288,8 @@ static int pp_stress_integrals(xfk_problem *P, double *out3)
 
 // --- contour integrals: host side ---------------------------------------------
 
-static int pp_contour_check(const xfk_problem *P, int nc, const int *ptr, const double *x, const double *y,
-                            int type)
+static int pot_contour_check(const xfk_problem *P, int nc, const int *ptr, const double *x, const double *y,
+                             int type)
 {
     XFK_REQUIRE(nc >= 0, XFK_ERR_ARG, "negative number of contours");
     XFK_REQUIRE(type >= 0, XFK_ERR_ARG, "line integral type out of range (negative)");
@@ -1749,14 +1395,9 @@ static int pp_contour_ends(xfk_problem *P, int nc, const int *ptr, const double 
     if (rc == XFK_OK) rc = pp_grid(P);
     if (rc != XFK_OK) return rc;
     const int n = 2 * nc;
-    std::vector<double> ex(n), ey(n), val(8 * (size_t)n);
-    for (int c = 0; c < nc; ++c) {
-        ex[2 * c] = x[ptr[c]];
-        ey[2 * c] = y[ptr[c]];
-        ex[2 * c + 1] = x[ptr[c + 1] - 1];
-        ey[2 * c + 1] = y[ptr[c + 1] - 1];
-    }
-    if ((rc = pp_upload_points(P, n, ex.data(), ey.data())) != XFK_OK) return rc;
+    std::vector<double> ex, ey, val(8 * (size_t)n);
+    contour_end_points(nc, ptr, x, y, ex, ey);
+    if ((rc = upload_points(P, n, ex.data(), ey.data(), 8)) != XFK_OK) return rc;
     double *px = P->pp_pts.p, *o = px + 2 * (size_t)n;
     if ((rc = pp_launch_points(P, n, px, px + n, 0, o, nullptr)) != XFK_OK) return rc;
     std::vector<int> el(n);
@@ -1777,22 +1418,16 @@ static void pp_contour_length(const xfk_problem *P, int n, const double *x, cons
 {
     const double lc = kPpLengthConv[P->pot_length_units];
     const double depth = P->pot_depth_user == -1 ? 1 : P->pot_depth_user * lc;
-    out2[0] = 0;
-    out2[1] = 0;
-    for (int i = 0; i < n - 1; ++i) out2[0] += pp_cabs(x[i + 1] - x[i], y[i + 1] - y[i]);
-    out2[0] *= lc;
-    if (P->axi) {
-        for (int i = 0; i < n - 1; ++i) out2[1] += (kPI * (x[i] + x[i + 1]) * pp_cabs(x[i + 1] - x[i], y[i + 1] - y[i]));
-        out2[1] *= P->heat ? std::pow(lc, 2.) : lc * lc;
-    } else {
-        out2[1] = out2[0] * depth;
-    }
+    double len, area;
+    polyline_sums(n, x, y, P->axi, len, area);
+    out2[0] = len * lc;
+    out2[1] = P->axi ? area * (P->heat ? std::pow(lc, 2.) : lc * lc) : out2[0] * depth;
 }
 
 static int pp_line_integrals(xfk_problem *P, int nc, const int *ptr, const double *x, const double *y, int type,
                              int smooth, int npts, double *out, int *missed)
 {
-    int rc = pp_contour_check(P, nc, ptr, x, y, type);
+    int rc = pot_contour_check(P, nc, ptr, x, y, type);
     if (rc != XFK_OK || nc == 0) return rc;
     XFK_REQUIRE(out, XFK_ERR_ARG, "null output");
     if (type == 0) return pp_contour_ends(P, nc, ptr, x, y, out, missed);
@@ -1844,23 +1479,8 @@ int xfk_pot_contour_samples(xfk_problem *P, int n, const double *x, const double
                             int *elem)
 {
     return pp_entry(P, true, [&]() -> int {
-        XFK_REQUIRE(n >= 0, XFK_ERR_ARG, "negative number of contour points");
-        const int ptr[2] = {0, n};
-        int rc = pp_contour_check(P, 1, ptr, x, y, type);
-        if (rc != XFK_OK) return rc;
-        XFK_REQUIRE(type != 0 && type != 2, XFK_ERR_ARG, "line integral types 0 and 2 take no samples");
-        XFK_REQUIRE(xy && elem, XFK_ERR_ARG, "null output");
-        PpContours J;
-        if ((rc = pp_contour_prepare(P, 1, ptr, x, y, type, 0, npts, J)) != XFK_OK) return rc;
-        const size_t ns = (size_t)(n - 1) * J.npts;
-        DBuf<double> dxy;
-        DBuf<int> del;
-        XFK_CHECK(dxy.alloc(2 * ns));
-        XFK_CHECK(del.alloc(ns));
-        if ((rc = pp_contour_launch(P, J, dxy.p, del.p)) != XFK_OK) return rc;
-        XFK_CHECK(d2h(xy, dxy.p, sizeof(double) * 2 * ns, P->stream));
-        XFK_CHECK(d2h(elem, del.p, sizeof(int) * ns, P->stream));
-        return XFK_OK;
+        return contour_samples(P, n, x, y, type, npts, xy, elem, pot_contour_check, pp_contour_prepare,
+                               pp_contour_launch);
     });
 }
 
@@ -1870,26 +1490,8 @@ int xfk_pot_contour_time(xfk_problem *P, int n_contours, const int *ptr, const d
     return pp_entry(P, true, [&]() -> int {
         XFK_REQUIRE(repeats > 0 && ms && n_contours > 0, XFK_ERR_ARG,
                     "xfk_pot_contour_time needs contours, repeats > 0 and its output");
-        int rc = pp_contour_check(P, n_contours, ptr, x, y, type);
-        if (rc != XFK_OK) return rc;
-        XFK_REQUIRE(type != 0 && type != 2, XFK_ERR_ARG, "line integral types 0 and 2 launch no contour kernel");
-        PpContours J;
-        if ((rc = pp_contour_prepare(P, n_contours, ptr, x, y, type, smooth, npts, J)) != XFK_OK) return rc;
-        ScopedEvents<2> ev;
-        XFK_CHECK(ev.create());
-        std::vector<double> t;
-        for (int k = 0; k <= repeats; ++k) {   // (the first a warm-up)
-            XFK_CHECK(hipEventRecord(ev[0], P->stream));
-            if ((rc = pp_contour_launch(P, J, nullptr, nullptr)) != XFK_OK) return rc;
-            XFK_CHECK(hipEventRecord(ev[1], P->stream));
-            XFK_CHECK(hipEventSynchronize(ev[1]));
-            float m = 0;
-            XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
-            if (k) t.push_back(m);
-        }
-        std::sort(t.begin(), t.end());
-        *ms = t[t.size() / 2];
-        return XFK_OK;
+        return contour_time(P, n_contours, ptr, x, y, type, smooth, npts, repeats, ms, pot_contour_check,
+                            pp_contour_prepare, pp_contour_launch);
     });
 }
 
@@ -1961,7 +1563,7 @@ int xfk_pot_block_integral(xfk_problem *P, const unsigned char *label_selected, 
         XFK_REQUIRE(type <= 4 || P->electro, XFK_ERR_ARG,
                     "block integral types 5 and 6 (weighted stress tensor force and torque) are not supported "
                     "on a heat-flow problem: the reference's hpproc has none");
-        XFK_REQUIRE(type <= 4 || mask_matches(P, label_selected), XFK_ERR_ARG,
+        XFK_REQUIRE(type <= 4 || mask_matches(P, label_selected, P->pot_labels.n), XFK_ERR_ARG,
                     "block integral types 5 and 6 (weighted stress tensor force and torque) need the mask of a "
                     "Laplace solve of their own, made for this label selection and this solution: call "
                     "xfk_pot_make_mask");
@@ -1990,7 +1592,7 @@ int xfk_pot_block_integral(xfk_problem *P, const unsigned char *label_selected, 
 int xfk_pot_make_mask(xfk_problem *P, const unsigned char *label_selected, const unsigned char *node_selected,
                       const double *label_max_area)
 {
-    return pp_entry(P, true, [&]() -> int { return mask_make(P, label_selected, node_selected, label_max_area); });
+    return pp_entry(P, true, [&]() -> int { return pot_make_mask(P, label_selected, node_selected, label_max_area); });
 }
 
 int xfk_pot_get_mask(xfk_problem *P, double *W, double *msk)
@@ -2105,21 +1707,7 @@ int xfk_pot_stress_time(xfk_problem *P, int repeats, double *ms)
         int rc = pp_fields(P);
         if (rc != XFK_OK) return rc;
         XFK_CHECK(P->pp_part.alloc(7 * ((size_t)(P->NE + kPotQBlock - 1) / kPotQBlock + 1)));
-        ScopedEvents<2> ev;
-        XFK_CHECK(ev.create());
-        std::vector<double> t;
-        for (int k = 0; k <= repeats; ++k) {   // (the first a warm-up)
-            XFK_CHECK(hipEventRecord(ev[0], P->stream));
-            if ((rc = pp_launch_stress(P)) != XFK_OK) return rc;
-            XFK_CHECK(hipEventRecord(ev[1], P->stream));
-            XFK_CHECK(hipEventSynchronize(ev[1]));
-            float m = 0;
-            XFK_CHECK(hipEventElapsedTime(&m, ev[0], ev[1]));
-            if (k) t.push_back(m);
-        }
-        std::sort(t.begin(), t.end());
-        *ms = t[t.size() / 2];
-        return XFK_OK;
+        return timed_median(P->stream, repeats, [&] { return pp_launch_stress(P); }, *ms);
     });
 }
 
@@ -2131,7 +1719,7 @@ int xfk_pot_point_values(xfk_problem *P, int n, const double *x, const double *y
         XFK_REQUIRE(x && y && elem && out, XFK_ERR_ARG, "null point arrays");
         int rc = smooth ? pp_corners(P, nullptr) : pp_fields(P);
         if (rc == XFK_OK) rc = pp_grid(P);
-        if (rc == XFK_OK) rc = pp_upload_points(P, n, x, y);
+        if (rc == XFK_OK) rc = upload_points(P, n, x, y, 8);
         if (rc != XFK_OK) return rc;
         double *px = P->pp_pts.p, *o = px + 2 * (size_t)n;
         rc = pp_launch_points(P, n, px, px + n, smooth, o, nullptr);
@@ -2152,7 +1740,7 @@ int xfk_pot_point_values_at(xfk_problem *P, int n, const double *x, const double
         for (int i = 0; i < n; ++i)
             XFK_REQUIRE(elem[i] >= -1 && elem[i] < P->NE, XFK_ERR_ARG, "a point's element is outside the element range");
         int rc = smooth ? pp_corners(P, nullptr) : pp_fields(P);
-        if (rc == XFK_OK) rc = pp_upload_points(P, n, x, y);
+        if (rc == XFK_OK) rc = upload_points(P, n, x, y, 8);
         if (rc != XFK_OK) return rc;
         XFK_CHECK(hipMemcpyAsync(P->pp_pel.p, elem, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, P->stream));
         double *px = P->pp_pts.p, *o = px + 2 * (size_t)n;
@@ -2196,39 +1784,18 @@ int xfk_pot_time(xfk_problem *P, int n, const double *x, const double *y, int re
         XFK_REQUIRE(n > 0 && x && y && repeats > 0 && ms7 && tests_per_point, XFK_ERR_ARG,
                     "xfk_pot_time needs points, repeats > 0 and its outputs");
         hipStream_t s = P->stream;
-        ScopedEvents<2> ev;
-        XFK_CHECK(ev.create());
-        std::vector<double> t;
-        auto median = [&]() {
-            std::sort(t.begin(), t.end());
-            const double m = t[t.size() / 2];
-            t.clear();
-            return m;
-        };
-        // f() between two events on the stream, repeats + 1 times (the first a warm-up)
-        auto timed = [&](auto f, double &out) -> int {
-            for (int k = 0; k <= repeats; ++k) {
-                XFK_CHECK(hipEventRecord(ev[0], s));
-                const int rc = f();
-                if (rc != XFK_OK) return rc;
-                XFK_CHECK(hipEventRecord(ev[1], s));
-                XFK_CHECK(hipEventSynchronize(ev[1]));
-                float ms = 0;
-                XFK_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-                if (k) t.push_back(ms);
-            }
-            out = median();
-            return XFK_OK;
-        };
+        auto timed = [&](auto f, double &out) { return timed_median(s, repeats, f, out); };
         int rc;
         // the host build of the mesh tables (wall clock: downloads, the sort, uploads)
+        std::vector<double> t;
         for (int k = 0; k <= repeats; ++k) {
             P->pp_mesh_ready = false;
             const auto t0 = std::chrono::steady_clock::now();
             if ((rc = pp_mesh(P)) != XFK_OK) return rc;
             if (k) t.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         }
-        ms7[0] = median();
+        std::sort(t.begin(), t.end());
+        ms7[0] = t[t.size() / 2];
         if ((rc = timed([&] { P->pp_grid_ready = false; return pp_grid(P); }, ms7[1])) != XFK_OK) return rc;
         if ((rc = timed([&] { P->pp_fields_ready = false; return pp_fields(P); }, ms7[2])) != XFK_OK) return rc;
         if ((rc = timed([&] { P->pp_corner_ready = false; return pp_corners(P, nullptr); }, ms7[3])) != XFK_OK) return rc;
@@ -2249,7 +1816,7 @@ int xfk_pot_time(xfk_problem *P, int n, const double *x, const double *y, int re
             return hipGetLastError() == hipSuccess ? XFK_OK : XFK_ERR_HIP;
         }, ms7[4]);
         if (rc != XFK_OK) return rc;
-        if ((rc = pp_upload_points(P, n, x, y)) != XFK_OK) return rc;
+        if ((rc = upload_points(P, n, x, y, 8)) != XFK_OK) return rc;
         double *px = P->pp_pts.p, *o = px + 2 * (size_t)n;
         for (int smooth = 0; smooth < 2; ++smooth)
             if ((rc = timed([&] { return pp_launch_points(P, n, px, px + n, smooth, o, nullptr); }, ms7[5 + smooth])) != XFK_OK)
